@@ -7,7 +7,12 @@ One "step" = one full FGMRES solve (to the prm's stop rule) of the synthetic
 with every operator and vector already resident in HBM when the timed region
 starts.  value = outer FGMRES iterations per second over the K timed solves.
 
-  python bench.py [--gpus N] [--steps K] [--warmup W] [--n-cells 74]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--n-cells 74] [--dump-outputs DIR] [--full]
+
+A plain run sets up, warms up, times the K solves and prints the line.  --full adds what takes runs of its own:
+the instrumented solve of the whole-solve roofline, the general-matrix and no-sharing legs, the reference-shaped
+leg, and the CPU baseline with the parity check against the oracle at the bench size.  --dump-outputs DIR writes
+what the last timed solve hands a caller (solution blocks, residual history, counts) as float64 .npy files.
 
 N > 1: one rank per GPU.  Launched by torch.distributed.run (the driver's contract), or directly --
 bench.py then starts its own N ranks as child processes before anything touches a GPU.  The SAME global
@@ -26,6 +31,8 @@ ROOT = os.path.dirname(os.path.abspath(__file__))
 sys.path.insert(0, ROOT)
 
 HBM_PEAK_GBS = 8000.0  # MI355X_MICROARCH.md: HBM3E 8 TB/s spec
+DUMP_BUDGET_BYTES = 64_000_000  # --dump-outputs: all files together
+DUMP_SEED = 20261016             # --dump-outputs: sample of a solution block too large to write whole
 
 
 def log(msg):
@@ -72,7 +79,7 @@ def main():
     ap.add_argument("--bricks", default="16,4,1",
                     help="row blocks of the A-SpMV: nodes of an a x b x c patch of the velocity grid (0 = runs of the numbering)")
     ap.add_argument("--general-steps", type=int, default=1,
-                    help="extra timed solves with the dictionary-free 10 B/nnz SpMV kernel and with translate sharing off (0 = skip)")
+                    help="--full: extra timed solves with the dictionary-free 10 B/nnz SpMV kernel and with translate sharing off (0 = skip)")
     ap.add_argument("--inner-prec", choices=["chebyshev", "multilevel"],
                     default=os.environ.get("ALFD_BENCH_PREC", "multilevel"))
     ap.add_argument("--hierarchy", choices=["geometric", "aggregation"], default=os.environ.get("ALFD_BENCH_HIERARCHY", "geometric"),
@@ -93,12 +100,20 @@ def main():
                     help="multi-GPU transport: RCCL over xGMI (default) or host buffers through a gloo group "
                          "(alfd_comm_init_host; slower, for boxes where RCCL cannot start)")
     ap.add_argument("--reference-shaped-n", type=int, default=int(os.environ.get("ALFD_BENCH_REFSHAPE_N", "64")),
-                    help="cells per direction of the reference-shaped leg (cell-wise assembled block (0,0) in a Cuthill-McKee "
-                         "numbering, as handed over and after the front end's renumbering); 0 = skip")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+                    help="--full: cells per direction of the reference-shaped leg (cell-wise assembled block (0,0) in a "
+                         "Cuthill-McKee numbering, as handed over and after the front end's renumbering); 0 = skip")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="--full: skip the CPU baseline and the parity check")
+    ap.add_argument("--full", action="store_true",
+                    help="also the figures that take runs of their own: whole-solve roofline, general-matrix, no-sharing "
+                         "and reference-shaped legs, CPU baseline + parity against the oracle at the bench size")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="after the timed solves, write what the last one computed (solution blocks, residual history, "
+                         "counts) to DIR/<name>.npy, float64, at most 64 MB in all")
     ap.add_argument("--profile-only-spmv", type=int, default=0,
                     help="skip the solve; run this many back-to-back A SpMV launches (for rocprofv3)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     if "WORLD_SIZE" not in os.environ and args.gpus > 1:
         self_launch(args.gpus)          # does not return
@@ -257,6 +272,16 @@ def main():
         dt = float(tt.item())
     tim = ctx.timing()
     ctx.enable_timing(False)
+    if args.dump_outputs:
+        # before anything else runs on the context: the solution and history are still those of the last timed solve
+        x = ctx.download_solution()
+        if world > 1:
+            parts = [None] * world if rank == 0 else None
+            dist.gather_object(x, parts, dst=0)
+            if rank == 0:
+                x = [np.concatenate([part[b] for part in parts]) for b in range(len(x))]
+        if rank == 0:
+            dump_outputs(args.dump_outputs, x, ctx.history(), last)
     nnz_A_global = int(pb.mats["A"].nnz)
     if world > 1:
         tn = torch.tensor([nnz_A_global], dtype=torch.int64)
@@ -269,7 +294,7 @@ def main():
     # ---- the whole solve against the HBM roofline: one more solve with HIP events around EVERY kernel class;
     # bytes from that run, time from the uninstrumented timed solves above
     whole = None
-    if world == 1:
+    if world == 1 and args.full:
         ctx.enable_timing(2)
         ctx.solve_resident()
         tall = ctx.timing()
@@ -320,7 +345,7 @@ def main():
 
     # ---- the same solve with the dictionary-free kernel (what a matrix with unrelated values gets)
     general = None
-    if world == 1 and info["value_indexed"] and args.general_steps > 0:
+    if world == 1 and args.full and info["value_indexed"] and args.general_steps > 0:
         ctx.set_tunable("value_index", 0)
         ctx.solve_resident()                                   # warm-up of this leg
         ctx.enable_timing(True)
@@ -345,7 +370,7 @@ def main():
     # ---- and with translate sharing off: every row stored (3.1 B/nnz), what a matrix whose values repeat but whose
     # rows are no translates of one another (unstructured mesh) gets from the batch-major kernel
     unshared = None
-    if world == 1 and info["batch_major"] and args.general_steps > 0:
+    if world == 1 and args.full and info["batch_major"] and args.general_steps > 0:
         ctx.set_tunable("batch_major_share", 0)
         ctx.set_matrix(_abi.A, pb.mats["A"])                    # A is re-planned; setup rebuilds the hierarchy
         ctx.setup(pb.block_sizes)
@@ -449,12 +474,12 @@ def main():
         "general_matrix_leg": general,
         "no_translate_sharing_leg": unshared,
     }
-    if world == 1 and args.reference_shaped_n > 0 and args.inner_prec == "multilevel" and geometric:
+    if world == 1 and args.full and args.reference_shaped_n > 0 and args.inner_prec == "multilevel" and geometric:
         out["reference_shaped_leg"] = reference_shaped_leg(args.reference_shaped_n, cfg, args.bricks)
 
     # ----------------------------------------------------------- CPU baseline + parity at the size the bench runs
     rc_exit = 0
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if rank == 0 and world == 1 and args.full and not args.no_cpu_baseline:
         base, prefix = cpu_baseline(pb, cfg, rhs, [(lv[0], lv[1]) for lv in levels] if levels else None,
                                     outer_per, inner_per)
         out["cpu_baseline"] = base
@@ -487,6 +512,41 @@ def main():
         dist.destroy_process_group()
     if rc_exit:
         raise SystemExit(rc_exit)
+
+
+def dump_outputs(path, blocks, history, res):
+    """--dump-outputs: what the last timed solve hands a caller, as float64 .npy files in `path` -- the solution blocks
+    (solution_u, solution_p, solution_lambda), the outer residual history and solve_counts = [outer, inner,
+    pressure-mass iterations, initial residual, final residual].  Where the whole solution does not fit in
+    DUMP_BUDGET_BYTES, a block that does not fit in its share is written as solution_<name>_sample: the entries
+    at sorted indices drawn with DUMP_SEED from the block's length alone (the same entries in every run with the same
+    arguments), with solution_<name>_stats = [length, sum, 2-norm, max |x|] of the whole block beside it."""
+    import numpy as np
+
+    os.makedirs(path, exist_ok=True)
+    names = ["u", "p", "lambda"] if len(blocks) == 3 else [str(b) for b in range(len(blocks))]
+    blocks = [np.ascontiguousarray(b, np.float64) for b in blocks]
+    files = {"residual_history": np.asarray(history, np.float64),
+             "solve_counts": np.array([res.outer_iterations, res.inner_iterations, res.mp_iterations,
+                                       res.initial_residual, res.last_residual], np.float64)}
+    budget = DUMP_BUDGET_BYTES - 1_000_000           # 1 MB kept for the history, the counts and the stats
+    order = sorted(range(len(blocks)), key=lambda b: blocks[b].size)
+    for k, b in enumerate(order):                    # smallest first; each takes at most an equal share of what is left
+        x = blocks[b]
+        share = budget // (8 * (len(order) - k))
+        if x.size <= share:
+            files[f"solution_{names[b]}"] = x
+        else:
+            idx = np.sort(np.random.default_rng(DUMP_SEED).choice(x.size, size=share, replace=False))
+            files[f"solution_{names[b]}_sample"] = x[idx]
+            files[f"solution_{names[b]}_stats"] = np.array(
+                [x.size, x.sum(), np.sqrt(np.dot(x, x)), np.abs(x).max()], np.float64)
+        budget -= 8 * min(x.size, share)
+    total = 0
+    for nm, arr in files.items():
+        np.save(os.path.join(path, nm + ".npy"), arr)
+        total += arr.nbytes
+    log(f"outputs of the last timed solve: {len(files)} arrays, {total / 1e6:.1f} MB in {path}")
 
 
 def reference_shaped_leg(n, cfg, bricks):

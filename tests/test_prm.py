@@ -1,11 +1,13 @@
 """PRM subset reader against the reference's own parameter files (text embedded
-here as minimal excerpts of the solver-control keys; the full files live in
-/root/reference and are parsed too when that directory is available)."""
+here as minimal excerpts of the solver-control keys; every parameter file of the
+reference is parsed too, from the settings-only copies in tests/golden/reference_prm)."""
 import os
 
 import pytest
 
 from fictitious_domain_al_preconditioners_amd import _abi, prm
+
+REFERENCE_PRM = os.path.join(os.path.dirname(os.path.abspath(__file__)), "golden", "reference_prm")
 
 STOKES_3D = """
 subsection Distributed Lagrange<2,3>
@@ -90,10 +92,9 @@ def test_immersed_laplace_and_elliptic_sections():
         prm.config_from_prm(bad)
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="reference tree not present (GPU box)")
 def test_every_reference_prm_parses():
     n = 0
-    for dirpath, _, files in os.walk("/root/reference"):
+    for dirpath, _, files in os.walk(REFERENCE_PRM):
         for f in files:
             if f.endswith(".prm"):
                 path = os.path.join(dirpath, f)
@@ -107,10 +108,10 @@ def test_every_reference_prm_parses():
                 n += 1
     assert n >= 15
     # BASELINE cfg 5: parameters_elliptic_interface/elasticity.prm (modified AL, exact W^-1, Lame 2,1 / 20,10)
-    cfg, info = prm.config_from_prm(prm.parse_file("/root/reference/parameters_elliptic_interface/elasticity.prm"))
+    cfg, info = prm.config_from_prm(prm.parse_file(os.path.join(REFERENCE_PRM, "parameters_elliptic_interface", "elasticity.prm")))
     assert cfg.variant == _abi.AL_ELL_MODIFIED and (cfg.gamma, cfg.gamma2) == (10.0, 1e-2)
     assert cfg.w_inverse == _abi.W_MASS_INV_SQUARED and (cfg.outer.reduce, cfg.outer.tol) == (1e-6, 1e-10)
     assert info["elasticity"] == {"lambda_background": 2.0, "mu_background": 1.0, "lambda_immersed": 20.0,
                                   "mu_immersed": 10.0}
-    cfg, info = prm.config_from_prm(prm.parse_file("/root/reference/parameters_stokes_3d.prm"))
+    cfg, info = prm.config_from_prm(prm.parse_file(os.path.join(REFERENCE_PRM, "parameters_stokes_3d.prm")))
     assert info["unsupported"] == [] and cfg.outer.tol == 1e-8 and cfg.inner.tol == 1e-2

@@ -1,5 +1,5 @@
-"""bench/reference_cmake: the log scraper on a synthetic deal.II log, and the export-hook injection on the real
-reference sources when they are present (authoring container only; nothing is copied, the output goes to tmp)."""
+"""bench/reference_cmake: the log scraper on a synthetic deal.II log, and the export-hook injection on synthetic
+drivers shaped like the reference's at the lines the injection looks for (the output goes to tmp)."""
 import os
 import subprocess
 import sys
@@ -52,25 +52,67 @@ def test_scraper_reads_the_librarys_own_log_lines():
     assert r["outer"]["steps"] == 9 and r["outer"]["converged"]
 
 
-@pytest.mark.skipif(not os.path.exists("/root/reference/stokes_immersed_boundary.cc"), reason="reference sources absent")
+# Stand-ins for the two drivers: only the lines inject_export.cmake looks for are shaped like the reference's (the
+# outer FGMRES solver object, and for the Stokes driver the dim / spacedim line of main() with the 3-D one commented out)
+SYNTHETIC_DRIVER = {
+    "stokes_immersed_boundary": """\
+#include <deal.II/lac/solver_fgmres.h>
+
+template <int dim, int spacedim>
+void Problem<dim, spacedim>::solve()
+{
+  SolverControl outer_solver_control(1000, 1e-8);
+  {
+      SolverFGMRES<BlockVector<double>> solver_fgmres(outer_solver_control);
+      solver_fgmres.solve(system, solution, rhs, preconditioner);
+  }
+}
+
+int main()
+{
+  const unsigned int dim = 1, spacedim = 2;
+  // const unsigned int dim = 2, spacedim = 3;
+  Problem<dim, spacedim> problem;
+  problem.run();
+}
+""",
+    "immersed_laplace": """\
+#include <deal.II/lac/solver_fgmres.h>
+
+template <int dim, int spacedim>
+void Problem<dim, spacedim>::solve()
+{
+  SolverControl schur_solver_control(1000, 1e-10);
+  {
+    SolverFGMRES<BlockVector<double>>
+      solver_fgmres(schur_solver_control);
+    solver_fgmres.solve(system, solution, rhs, preconditioner);
+  }
+}
+""",
+}
+
+
 @pytest.mark.parametrize("driver,hook", [("stokes_immersed_boundary", "ALFD_EXPORT_STOKES_HOOK"),
                                          ("immersed_laplace", "ALFD_EXPORT_LAPLACE_HOOK")])
 def test_export_hook_injection_finds_its_anchor(tmp_path, driver, hook):
-    """inject_export.cmake on the real driver: exactly one hook in front of the FGMRES solver object, the #include on
-    top, the 3-D switch applied -- and otherwise the file is the reference's, byte for byte."""
+    """inject_export.cmake on a driver: exactly one hook in front of the FGMRES solver object, the #include on
+    top, the 3-D switch applied -- and otherwise the file is the input's, byte for byte."""
+    src = tmp_path / f"{driver}_in.cc"
+    src.write_text(SYNTHETIC_DRIVER[driver])
     out = tmp_path / f"{driver}.cc"
-    p = subprocess.run(["cmake", f"-DIN=/root/reference/{driver}.cc", f"-DOUT={out}", f"-DDRIVER={driver}",
+    p = subprocess.run(["cmake", f"-DIN={src}", f"-DOUT={out}", f"-DDRIVER={driver}",
                         "-DSTOKES_3D=ON", "-P", os.path.join(HARNESS, "inject_export.cmake")],
                        capture_output=True, text=True)
     assert p.returncode == 0, p.stderr
     gen = out.read_text()
-    ref = open(f"/root/reference/{driver}.cc").read()
+    ref = src.read_text()
     assert gen.startswith('#include "alfd_export_hook.hpp"\n') and gen.count(hook) == 1
     i = gen.index(hook)
     assert "SolverFGMRES<BlockVector<double>>" in gen[i:i + 200]          # right in front of the solver object
     if driver == "stokes_immersed_boundary":
         assert "const unsigned int dim = 2, spacedim = 3;" in gen
-    # removing what was inserted gives back the reference
+    # removing what was inserted gives back the input
     back = gen[len('#include "alfd_export_hook.hpp"\n'):]
     j = back.index(hook)
     k = back.index("SolverFGMRES<BlockVector<double>>", j)
