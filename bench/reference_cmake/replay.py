@@ -4,11 +4,12 @@ prints both iteration counts side by side -- the one route by which parity with 
 pinned (needs a deal.II install, which this repository's pipeline does not have).
 
     python bench/reference_cmake/replay.py run/stokes_immersed_boundary.alfd [--reference-log run/stokes.log]
-                                           [--inner-prec multilevel|chebyshev] [--support-points points.npy]
+                                           [--inner-prec multilevel|sa-multilevel|chebyshev] [--support-points points.npy]
 
 The inner preconditioner differs from the reference's by construction (Trilinos ML there; here the algebraic aggregation
-of alfd_build_aggregates on the dumped A, or geometric transfers when the caller supplies them), so OUTER counts are the
-comparable quantity: both inner solvers stop at the same absolute tolerance (parameters_stokes_3d.prm:23-24)."""
+of alfd_build_aggregates on the dumped A, or geometric transfers when the caller supplies them; sa-multilevel builds
+ML's algorithm, smoothed aggregation, from the dumped operators with alfd_build_smoothed_aggregation), so OUTER counts
+are the comparable quantity: both inner solvers stop at the same absolute tolerance (parameters_stokes_3d.prm:23-24)."""
 import argparse
 import json
 import os
@@ -23,7 +24,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("alfd_file")
     ap.add_argument("--reference-log", help="stdout of the reference run (scrape_deallog.py)")
-    ap.add_argument("--inner-prec", choices=["multilevel", "chebyshev"], default="multilevel")
+    ap.add_argument("--inner-prec", choices=["multilevel", "sa-multilevel", "chebyshev"], default="multilevel")
     ap.add_argument("--inner-max", type=int, default=0, help="override the inner CG cap of the dump (0 = keep)")
     ap.add_argument("--support-points", help=".npy with one support point per row of block 0: front-end renumbering + mesh bricks")
     ap.add_argument("--block-size", type=int, default=0, help="components per node of block 0 (default: 3 for Stokes dumps, else 1)")
@@ -59,12 +60,18 @@ def main():
         ctx.set_matrix(slot, m)
     for slot, d in diags.items():
         ctx.set_diag(slot, d)
-    if args.inner_prec == "multilevel" and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
+    if args.inner_prec in ("multilevel", "sa-multilevel") and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
         cfg.inner_prec = _abi.PREC_MULTILEVEL
         cfg.ml_smooth_degree, cfg.ml_smooth_ratio, cfg.ml_coarse_degree = 4, 256.0, 10
         ctx.configure(cfg)
-        levels = ctx.build_aggregates(block_size=bs, threshold=0.02, max_aggregate_nodes=8, min_coarse=3000)
-        print(f"algebraic aggregation (ML's threshold 0.02, utilities.h:312): levels {[nc for _, nc in levels]}")
+        if args.inner_prec == "sa-multilevel":
+            levels, omega = ctx.build_smoothed_aggregation(block_size=bs, threshold=0.02, max_aggregate_nodes=8,
+                                                           damping=4.0 / 3.0, min_coarse=3000, return_omega=True)
+            print(f"smoothed aggregation (ML's threshold 0.02 and damping 4/3, utilities.h:304-317): levels "
+                  f"{[nc for _, nc in levels]}, omega {[float(o) for o in omega]}")
+        else:
+            levels = ctx.build_aggregates(block_size=bs, threshold=0.02, max_aggregate_nodes=8, min_coarse=3000)
+            print(f"algebraic aggregation (ML's threshold 0.02, utilities.h:312): levels {[nc for _, nc in levels]}")
     else:
         cfg.inner_prec = _abi.PREC_CHEBYSHEV
     ctx.configure(cfg)

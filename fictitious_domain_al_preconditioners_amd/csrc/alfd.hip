@@ -4343,6 +4343,264 @@ static int product(alfd_ctx *ctx, const HostCsr &A, const HostCsr &Pm, HostCsr &
   return ALFD_OK;
 }
 
+// ======================================================================
+// Smoothed aggregation (alfd_build_smoothed_aggregation, alfd_host_smoothed_prolongator): per level
+//   P = P_tent - omega D^-1 Aug P_tent,  Aug = A + gamma Ct diag(w) C,  C = Ct^T,  D = diag(Aug),
+// P_tent the piecewise-constant prolongator of aggregate_level.  The operator the level's cycle smooths with is the one
+// that is smoothed here (ML receives the augmented block in the reference).  Canonical order:
+//   d_i  = fma(gamma, s_i, a_ii), s_i a sequential fma over row i of Ct of (w_k c_ik) c_ik   (diag_plus)
+//   pen  = Ct Tw, Tw_kJ = (gamma w_k) T_kJ, T = C P_tent                                   (spgemm canonical order)
+//   P_iJ = fma(-omega / d_i, s, [J == agg_i]),  s = (sum of a_ik over row i in CSR order with agg_k == J) + pen_iJ
+// The pattern is the structural union; nothing is dropped by value.  The host rows below and sa_prolongator_kernel
+// compute the same bits.
+struct SaPenalty {
+  const HostCsr *Ct = nullptr, *C = nullptr;   // Ct: n x m, C = Ct^T
+  const double *w = nullptr;                   // W^-1 diagonal (m)
+  double gamma = 0.0;
+  bool on() const { return Ct != nullptr; }
+};
+
+static void sa_diag(const HostCsr &A, const SaPenalty &pen, std::vector<double> &d) {
+  d.assign(A.nrows, 0.0);
+  for (int64_t i = 0; i < A.nrows; ++i)
+    for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k)
+      if (A.col[k] == i) d[i] = A.val[k];
+  if (!pen.on()) return;
+  const HostCsr &Ct = *pen.Ct;
+  for (int64_t i = 0; i < A.nrows; ++i) {
+    double s = 0.0;
+    for (int64_t k = Ct.rp[i]; k < Ct.rp[i + 1]; ++k) s = std::fma(pen.w[Ct.col[k]] * Ct.val[k], Ct.val[k], s);
+    d[i] = std::fma(pen.gamma, s, d[i]);
+  }
+}
+
+// y = M x row by row (each row one sequential fma chain), row ranges on up to 16 threads
+static void sa_spmv_host(const HostCsr &M, const double *x, double *y) {
+  const int64_t n = M.nrows;
+  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())),
+                                                           (n + 16383) / 16384));
+  auto work = [&](int64_t i0, int64_t i1) {
+    for (int64_t i = i0; i < i1; ++i) {
+      double s = 0.0;
+      for (int64_t k = M.rp[i]; k < M.rp[i + 1]; ++k) s = std::fma(M.val[k], x[M.col[k]], s);
+      y[i] = s;
+    }
+  };
+  std::vector<std::thread> th;
+  for (int t = 1; t < T; ++t) th.emplace_back(work, n * t / T, n * (t + 1) / T);
+  work(0, n / T);
+  for (auto &x_ : th) x_.join();
+}
+
+// lambda_max(D^-1 Aug) by power iteration from the integer-hash start vector of hash_vector_kernel, `its` steps, no
+// safety factor; every reduction is one sequential sum (deterministic)
+static double sa_lambda(const HostCsr &A, const SaPenalty &pen, const std::vector<double> &d, int its) {
+  const int64_t n = A.nrows;
+  std::vector<double> v(n), y(n), t(pen.on() ? pen.C->nrows : 0), u(pen.on() ? n : 0);
+  for (int64_t i = 0; i < n; ++i) v[i] = 1.0 + (double)(((uint64_t)i * 2654435761ull) & 1023ull) * (1.0 / 1024.0);
+  double lam = 0.0;
+  for (int it = 0; it < its; ++it) {
+    double nv = 0.0;
+    for (int64_t i = 0; i < n; ++i) nv = std::fma(v[i], v[i], nv);
+    const double sc = 1.0 / std::sqrt(nv);
+    for (int64_t i = 0; i < n; ++i) v[i] = v[i] * sc;
+    sa_spmv_host(A, v.data(), y.data());
+    if (pen.on()) {
+      sa_spmv_host(*pen.C, v.data(), t.data());
+      for (size_t k = 0; k < t.size(); ++k) t[k] = pen.w[k] * t[k];
+      sa_spmv_host(*pen.Ct, t.data(), u.data());
+      for (int64_t i = 0; i < n; ++i) y[i] = std::fma(pen.gamma, u[i], y[i]);
+    }
+    double ny = 0.0;
+    for (int64_t i = 0; i < n; ++i) {
+      y[i] = y[i] / d[i];
+      ny = std::fma(y[i], y[i], ny);
+    }
+    lam = std::sqrt(ny);
+    std::swap(v, y);
+  }
+  return lam;
+}
+
+// the tentative prolongator as a CSR matrix (only for the small product C P_tent)
+static void sa_tentative(const std::vector<int32_t> &agg, int64_t nc, HostCsr &Pt) {
+  const int64_t n = (int64_t)agg.size();
+  Pt.nrows = n;
+  Pt.ncols = nc;
+  Pt.rp.assign(n + 1, 0);
+  Pt.col.clear();
+  Pt.val.clear();
+  for (int64_t i = 0; i < n; ++i) {
+    if (agg[i] >= 0) {
+      Pt.col.push_back(agg[i]);
+      Pt.val.push_back(1.0);
+    }
+    Pt.rp[i + 1] = (int64_t)Pt.col.size();
+  }
+}
+
+// Tw = diag(gamma w) (C P_tent) in place
+static void sa_scale_rows(HostCsr &T, const double *w, double gamma) {
+  for (int64_t k = 0; k < T.nrows; ++k) {
+    const double s = gamma * w[k];
+    for (int64_t e = T.rp[k]; e < T.rp[k + 1]; ++e) T.val[e] = s * T.val[e];
+  }
+}
+
+// the rows of P on the host (overflow fallback of sa_prolongator_kernel and alfd_host_smoothed_prolongator);
+// Q = pen (n x nc, sorted rows) or nullptr
+static void sa_rows_host(const HostCsr &A, const std::vector<int32_t> &agg, int64_t nc, const std::vector<double> &f,
+                         const HostCsr *Q, HostCsr &P) {
+  const int64_t n = A.nrows;
+  const int T = (int)std::max<int64_t>(1, std::min<int64_t>(std::min(16u, std::max(1u, std::thread::hardware_concurrency())),
+                                                           (n + 4095) / 4096));
+  std::vector<std::vector<int32_t>> t_cnt(T), t_col(T);
+  std::vector<std::vector<double>> t_val(T);
+  std::vector<std::thread> th;
+  for (int t = 0; t < T; ++t)
+    th.emplace_back([&, t]() {
+      const int64_t i0 = n * t / T, i1 = n * (t + 1) / T;
+      std::vector<int64_t> stamp(nc, -1);
+      std::vector<double> acc(nc, 0.0);
+      std::vector<int32_t> touched;
+      auto add = [&](int64_t i, int32_t J, double v) {
+        if (stamp[J] != i) {
+          stamp[J] = i;
+          acc[J] = 0.0;
+          touched.push_back(J);
+        }
+        acc[J] = acc[J] + v;
+      };
+      for (int64_t i = i0; i < i1; ++i) {
+        touched.clear();
+        const int32_t gi = agg[i];
+        if (gi >= 0) {
+          for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
+            const int32_t J = agg[A.col[k]];
+            if (J >= 0) add(i, J, A.val[k]);
+          }
+          if (Q)
+            for (int64_t q = Q->rp[i]; q < Q->rp[i + 1]; ++q) add(i, Q->col[q], Q->val[q]);
+          if (stamp[gi] != i) add(i, gi, 0.0);
+        }
+        std::sort(touched.begin(), touched.end());
+        t_cnt[t].push_back((int32_t)touched.size());
+        for (int32_t J : touched) {
+          t_col[t].push_back(J);
+          t_val[t].push_back(std::fma(f[i], acc[J], J == gi ? 1.0 : 0.0));
+        }
+      }
+    });
+  for (auto &x : th) x.join();
+  P.nrows = n;
+  P.ncols = nc;
+  P.rp.assign(1, 0);
+  P.col.clear();
+  P.val.clear();
+  for (int t = 0; t < T; ++t) {
+    for (int32_t c : t_cnt[t]) P.rp.push_back(P.rp.back() + c);
+    P.col.insert(P.col.end(), t_col[t].begin(), t_col[t].end());
+    P.val.insert(P.val.end(), t_val[t].begin(), t_val[t].end());
+  }
+}
+
+// f_i = -omega / d_i (rows without an aggregate: 0, never read)
+static void sa_factors(const std::vector<int32_t> &agg, const std::vector<double> &d, double omega, std::vector<double> &f) {
+  f.assign(agg.size(), 0.0);
+  for (size_t i = 0; i < agg.size(); ++i)
+    if (agg[i] >= 0) f[i] = -omega / d[i];
+}
+
+// the penalty rows gamma Ct diag(w) C P_tent (an empty matrix without penalty)
+static int sa_penalty_rows(alfd_ctx *ctx, const SaPenalty &pen, const std::vector<int32_t> &agg, int64_t nc, HostCsr &Q) {
+  Q = HostCsr();
+  if (!pen.on()) return ALFD_OK;
+  HostCsr Pt, Tm;
+  sa_tentative(agg, nc, Pt);
+  if (ctx) RC(product(ctx, *pen.C, Pt, Tm));
+  else spgemm_host(*pen.C, Pt, Tm);
+  sa_scale_rows(Tm, pen.w, pen.gamma);
+  if (ctx) RC(product(ctx, *pen.Ct, Tm, Q));
+  else spgemm_host(*pen.Ct, Tm, Q);
+  return ALFD_OK;
+}
+
+// P on the device (sa_prolongator_kernel); *fits = false when a row has more distinct coarse ids than the kernel holds
+static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector<int32_t> &agg, int64_t nc,
+                              const std::vector<double> &f, const HostCsr &Q, HostCsr &P, bool *fits) {
+  *fits = false;
+  const int64_t n = A.nrows;
+  DevRawCsr dA, dQ, dP;
+  RC(upload_raw(ctx, A, dA));
+  const bool pen = !Q.rp.empty();
+  if (pen) RC(upload_raw(ctx, Q, dQ));
+  int32_t *d_agg = nullptr, *counts = nullptr, *ovf = nullptr;
+  double *d_f = nullptr;
+  auto release = [&]() {
+    dA.release();
+    dQ.release();
+    dP.release();
+    for (void *p : {(void *)d_agg, (void *)counts, (void *)ovf, (void *)d_f})
+      if (p) hipFree(p);
+  };
+  auto fail = [&](hipError_t e) {
+    release();
+    ctx->err = std::string("HIP error in the smoothed-aggregation prolongator: ") + hipGetErrorString(e);
+    return ALFD_E_HIP;
+  };
+  hipError_t e;
+  if ((e = hipMalloc((void **)&d_agg, std::max<int64_t>(n, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&d_f, std::max<int64_t>(n, 1) * sizeof(double))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&counts, std::max<int64_t>(n, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&ovf, sizeof(int32_t))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&dP.rp, (n + 1) * sizeof(int64_t))) != hipSuccess) return fail(e);
+  if (n && (e = hipMemcpyAsync(d_agg, agg.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if (n && (e = hipMemcpyAsync(d_f, f.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if ((e = hipMemsetAsync(ovf, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return fail(e);
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n, 256 * 64));
+  const int64_t *qrp = pen ? dQ.rp : nullptr;
+  hipLaunchKernelGGL(sa_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val, d_agg, d_f,
+                     qrp, dQ.col, dQ.val, 0, counts, (const int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, ovf);
+  if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+  std::vector<int32_t> hc(n);
+  int32_t hovf = 0;
+  if (n && (e = hipMemcpyAsync(hc.data(), counts, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if ((e = hipMemcpyAsync(&hovf, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess) return fail(e);
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e);
+  if (hovf) {
+    release();
+    return ALFD_OK;
+  }
+  P.nrows = n;
+  P.ncols = nc;
+  P.rp.assign(n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) P.rp[i + 1] = P.rp[i] + hc[i];
+  const int64_t nnz = P.rp[n];
+  dP.nrows = n;
+  dP.ncols = nc;
+  dP.nnz = nnz;
+  if ((e = hipMemcpyAsync(dP.rp, P.rp.data(), (n + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if ((e = hipMalloc((void **)&dP.col, std::max<int64_t>(nnz, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&dP.val, std::max<int64_t>(nnz, 1) * sizeof(double))) != hipSuccess) return fail(e);
+  hipLaunchKernelGGL(sa_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val, d_agg, d_f,
+                     qrp, dQ.col, dQ.val, 1, counts, (const int64_t *)dP.rp, dP.col, dP.val, ovf);
+  if ((e = hipGetLastError()) != hipSuccess) return fail(e);
+  P.col.resize(nnz);
+  P.val.resize(nnz);
+  if (nnz && (e = hipMemcpyAsync(P.col.data(), dP.col, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if (nnz && (e = hipMemcpyAsync(P.val.data(), dP.val, nnz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream)) != hipSuccess)
+    return fail(e);
+  if ((e = hipStreamSynchronize(ctx->stream)) != hipSuccess) return fail(e);
+  release();
+  *fits = true;
+  return ALFD_OK;
+}
+
 static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, const HostCsr &Ct, const std::vector<double> &w);
 static int patch_setup_rep(alfd_ctx *ctx);
 
@@ -5663,6 +5921,150 @@ int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacit
   if (agg) {
     if (capacity < (int64_t)a.size()) return ALFD_E_INVALID;
     std::copy(a.begin(), a.end(), agg);
+  }
+  return ALFD_OK;
+}
+
+int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
+                                    double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
+                                    double *omega_out) {
+  CHECK_CTX();
+  if (ctx->nranks > 1) return ctx->err = "alfd_build_smoothed_aggregation is single-rank", ALFD_E_UNSUPPORTED;
+  if (!ctx->mat[ALFD_A].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
+  if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
+      !(damping > 0.0) || !std::isfinite(damping))
+    return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
+  if (ctx->mat[ALFD_A].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
+  if (ctx->mat[ALFD_A].nrows != ctx->mat[ALFD_A].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
+  if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
+  const int its = ctx->configured ? ctx->cfg.cheb_power_its : 20;
+  if (its < 1) return ctx->err = "cheb_power_its must be >= 1", ALFD_E_INVALID;
+  // the penalty term: an AL variant with a diagonal W^-1, a non-zero gamma, A not already augmented, Ct and W^-1 present
+  const alfd_config &c = ctx->cfg;
+  const bool use_pen = ctx->configured && c.variant != ALFD_RATIONAL && c.w_inverse == ALFD_W_DIAGONAL &&
+                       !c.aug_assembled && c.gamma != 0.0 && ctx->mat[ALFD_CT].present && ctx->diag[ALFD_INVW];
+  HostCsr A, An, C, Ct, Cn, Q, P, R, AP;
+  std::vector<double> w;
+  RC(download_csr(ctx, ctx->mat[ALFD_A], A));
+  if (use_pen) {
+    RC(download_csr(ctx, ctx->mat[ALFD_CT], Ct));
+    if (Ct.nrows != A.nrows || ctx->diag_n[ALFD_INVW] != Ct.ncols)
+      return ctx->err = "alfd_build_smoothed_aggregation: Ct / W^-1 do not match A", ALFD_E_INVALID;
+    w.resize(Ct.ncols);
+    if (!w.empty())
+      HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    transpose_host(Ct, C);
+  }
+  for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+  ctx->is_setup = false;
+  int nlev = 0;
+  std::vector<double> d, f;
+  while (nlev < max_levels) {
+    std::vector<int32_t> agg;
+    int64_t nc = 0;
+    aggregate_level(A, block_size, threshold, max_aggregate_nodes, agg, nc);
+    if (nc < 1 || nc >= A.nrows) break;     // nothing left to coarsen
+    SaPenalty pen;
+    if (use_pen) pen.Ct = &Ct, pen.C = &C, pen.w = w.data(), pen.gamma = c.gamma;
+    sa_diag(A, pen, d);
+    const double lam = sa_lambda(A, pen, d, its);
+    if (!(lam > 0.0) || !std::isfinite(lam)) {
+      for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_P[l] = HostCsr();
+      return ctx->err = "alfd_build_smoothed_aggregation: lambda_max(D^-1 Aug) of level " + std::to_string(nlev) +
+                        " is not positive and finite (zero diagonal?)", ALFD_E_INVALID;
+    }
+    const double omega = damping / lam;
+    sa_factors(agg, d, omega, f);
+    RC(sa_penalty_rows(ctx, pen, agg, nc, Q));
+    bool fits = false;
+    RC(sa_prolongator_dev(ctx, A, agg, nc, f, Q, P, &fits));
+    if (!fits) sa_rows_host(A, agg, nc, f, use_pen ? &Q : nullptr, P);
+    Q = HostCsr();
+    if (omega_out) omega_out[nlev] = omega;
+    ctx->ml_agg[nlev] = agg;
+    ctx->ml_P[nlev] = P;
+    ctx->ml_ncoarse[nlev] = nc;
+    ++nlev;
+    if (nc <= min_coarse || nlev >= max_levels) break;
+    // next level: A_{l+1} = P^T (A P), C_{l+1} = C P (the Galerkin products of alfd_setup, same order)
+    RC(product(ctx, A, P, AP));
+    transpose_host(P, R);
+    RC(product(ctx, R, AP, An));
+    AP = HostCsr();
+    std::swap(A, An);
+    if (use_pen) {
+      RC(product(ctx, C, P, Cn));
+      std::swap(C, Cn);
+      transpose_host(C, Ct);
+    }
+  }
+  if (nlev == 0) return ctx->err = "algebraic aggregation found nothing to coarsen", ALFD_E_INVALID;
+  if (levels_out) *levels_out = nlev;
+  return ALFD_OK;
+}
+
+int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
+                         int64_t *n_fine, int64_t *n_coarse, int64_t *nnz) {
+  if (!ctx || level < 0 || level >= ALFD_MAX_LEVELS || ctx->ml_P[level].rp.empty()) return ALFD_E_INVALID;
+  const HostCsr &P = ctx->ml_P[level];
+  if (n_fine) *n_fine = P.nrows;
+  if (n_coarse) *n_coarse = P.ncols;
+  if (nnz) *nnz = P.nnz();
+  if (row_ptr) std::copy(P.rp.begin(), P.rp.end(), row_ptr);
+  if (col || val) {
+    if (capacity < P.nnz()) return ALFD_E_INVALID;
+    if (col) std::copy(P.col.begin(), P.col.end(), col);
+    if (val) std::copy(P.val.begin(), P.val.end(), val);
+  }
+  return ALFD_OK;
+}
+
+int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                                   int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
+                                   const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
+                                   int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz) {
+  if (nrows < 1 || !row_ptr || !col || !val || !agg || n_coarse < 1 || n_coarse > INT32_MAX || !nnz ||
+      !std::isfinite(omega) || !std::isfinite(gamma) || row_ptr[0] != 0)
+    return ALFD_E_INVALID;
+  for (int64_t i = 0; i < nrows; ++i)
+    if (row_ptr[i + 1] < row_ptr[i] || agg[i] < -1 || agg[i] >= n_coarse) return ALFD_E_INVALID;
+  for (int64_t k = 0; k < row_ptr[nrows]; ++k)
+    if (col[k] < 0 || col[k] >= nrows) return ALFD_E_INVALID;
+  HostCsr A, Ct, C, Q, P;
+  A.nrows = A.ncols = nrows;
+  A.rp.assign(row_ptr, row_ptr + nrows + 1);
+  A.col.assign(col, col + A.rp[nrows]);
+  A.val.assign(val, val + A.rp[nrows]);
+  SaPenalty pen;
+  if (ct_row_ptr) {
+    if (n_mult < 0 || !ct_col || !ct_val || !w_inv || ct_row_ptr[0] != 0) return ALFD_E_INVALID;
+    for (int64_t i = 0; i < nrows; ++i)
+      if (ct_row_ptr[i + 1] < ct_row_ptr[i]) return ALFD_E_INVALID;
+    for (int64_t k = 0; k < ct_row_ptr[nrows]; ++k)
+      if (ct_col[k] < 0 || ct_col[k] >= n_mult) return ALFD_E_INVALID;
+    Ct.nrows = nrows;
+    Ct.ncols = n_mult;
+    Ct.rp.assign(ct_row_ptr, ct_row_ptr + nrows + 1);
+    Ct.col.assign(ct_col, ct_col + Ct.rp[nrows]);
+    Ct.val.assign(ct_val, ct_val + Ct.rp[nrows]);
+    transpose_host(Ct, C);
+    pen.Ct = &Ct, pen.C = &C, pen.w = w_inv, pen.gamma = gamma;
+  }
+  std::vector<int32_t> a(agg, agg + nrows);
+  std::vector<double> d, f;
+  sa_diag(A, pen, d);
+  for (int64_t i = 0; i < nrows; ++i)
+    if (a[i] >= 0 && !(d[i] != 0.0)) return ALFD_E_INVALID;
+  sa_factors(a, d, omega, f);
+  RC(sa_penalty_rows(nullptr, pen, a, n_coarse, Q));
+  sa_rows_host(A, a, n_coarse, f, pen.on() ? &Q : nullptr, P);
+  *nnz = P.nnz();
+  if (p_row_ptr) std::copy(P.rp.begin(), P.rp.end(), p_row_ptr);
+  if (p_col || p_val) {
+    if (capacity < P.nnz()) return ALFD_E_INVALID;
+    if (p_col) std::copy(P.col.begin(), P.col.end(), p_col);
+    if (p_val) std::copy(P.val.begin(), P.val.end(), p_val);
   }
   return ALFD_OK;
 }

@@ -1569,6 +1569,131 @@ __global__ __launch_bounds__(64) void spgemm_rows_kernel(int64_t nrows, const in
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// Smoothed-aggregation prolongator P = P_tent - omega D^-1 (A P_tent + pen), one 64-lane workgroup per fine row i
+// (alfd_build_smoothed_aggregation).  P_tent is never formed: (P_tent)_{j, agg[j]} = 1, so (A P_tent)_{iJ} is the sum
+// of the entries of row i of A whose column j has agg[j] == J.  pen = gamma Ct diag(w) C P_tent comes in as a CSR matrix
+// with sorted rows (formed beforehand by the generic product; C has few rows).  Canonical order of every entry:
+//   s = 0.0;  s = s + a_ik  for the entries k of row i of A in CSR order with agg[col_k] == J;
+//   s = s + pen_iJ;  P_iJ = fma(f_i, s, J == agg[i] ? 1 : 0)  with f_i = -omega / d_i (from the host).
+// Pattern: the structural union {agg[col_k] >= 0} U pattern(pen row i) U {agg[i]}, columns ascending; rows with
+// agg[i] < 0 stay empty.  Two passes as spgemm_rows_kernel: pass 0 counts the distinct coarse ids of every row (LDS
+// hash set), pass 1 compacts and bitonic-sorts them, then lane t owns output column t and walks the row of A, staged
+// in LDS as (agg[col], val) pairs, in CSR order.  At most kSaMaxOut distinct ids per row (overflow[0] is set
+// otherwise: the host builds the level with the same arithmetic).  LDS: 16 KiB per workgroup.
+constexpr int kSaTable = 2048;
+constexpr int kSaMaxOut = 512;
+constexpr int kSaStage = 512;
+__global__ __launch_bounds__(64) void sa_prolongator_kernel(
+    int64_t nrows, const int64_t *__restrict__ arp, const int32_t *__restrict__ acol, const double *__restrict__ aval,
+    const int32_t *__restrict__ agg, const double *__restrict__ f, const int64_t *__restrict__ qrp,
+    const int32_t *__restrict__ qcol, const double *__restrict__ qval, int pass, int32_t *__restrict__ counts,
+    const int64_t *__restrict__ prp, int32_t *__restrict__ pcol, double *__restrict__ pval,
+    int32_t *__restrict__ overflow) {
+  __shared__ int32_t table[kSaTable];
+  __shared__ int32_t keys[kSaMaxOut];
+  __shared__ int32_t sJ[kSaStage];
+  __shared__ double sv[kSaStage];
+  __shared__ int32_t cnt;
+  const int lane = threadIdx.x;
+  auto insert = [&](int32_t J) {
+    uint32_t h = ((uint32_t)J * 2654435761u) >> 21;   // 11 bits
+    for (;;) {
+      if (*(volatile int32_t *)&cnt > kSaMaxOut) break;   // overflowing row: stop inserting (reported below)
+      const int32_t old = atomicCAS(&table[h], -1, J);
+      if (old == -1) {
+        atomicAdd(&cnt, 1);
+        break;
+      }
+      if (old == J) break;
+      h = (h + 1) & (kSaTable - 1);
+    }
+  };
+  for (int64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    const int32_t gi = agg[i];
+    if (gi < 0) {
+      if (pass == 0 && lane == 0) counts[i] = 0;
+      continue;
+    }
+    const int64_t k0 = arp[i], k1 = arp[i + 1];
+    const int64_t q0 = qrp ? qrp[i] : 0, q1 = qrp ? qrp[i + 1] : 0;
+    for (int s = lane; s < kSaTable; s += 64) table[s] = -1;
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    if (lane == 0) insert(gi);
+    for (int64_t k = k0 + lane; k < k1; k += 64) {
+      const int32_t J = agg[acol[k]];
+      if (J >= 0) insert(J);
+    }
+    for (int64_t q = q0 + lane; q < q1; q += 64) insert(qcol[q]);
+    __syncthreads();
+    const int n = cnt;
+    if (n > kSaMaxOut) {
+      if (lane == 0) overflow[0] = 1;
+      if (pass == 0 && lane == 0) counts[i] = 0;
+      __syncthreads();
+      continue;
+    }
+    if (pass == 0) {
+      if (lane == 0) counts[i] = n;
+      __syncthreads();
+      continue;
+    }
+    // compact, pad to a power of two with INT_MAX, bitonic sort (n2 <= kSaMaxOut)
+    int n2 = 64;
+    while (n2 < n) n2 <<= 1;
+    __syncthreads();
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    for (int s = lane; s < kSaTable; s += 64) {
+      const int32_t J = table[s];
+      if (J != -1) keys[atomicAdd(&cnt, 1)] = J;
+    }
+    __syncthreads();
+    for (int s = n + lane; s < n2; s += 64) keys[s] = 0x7fffffff;
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = lane; t < n2 / 2; t += 64) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool up = (lo & size) == 0;
+          const int32_t a = keys[lo], b = keys[hi];
+          if ((a > b) == up) {
+            keys[lo] = b;
+            keys[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    const int64_t c0 = prp[i];
+    const double fi = f[i];
+    for (int t0 = 0; t0 < n; t0 += 64) {
+      const int t = t0 + lane;
+      const int32_t J = t < n ? keys[t] : -2;
+      double s = 0.0;
+      for (int64_t kb = k0; kb < k1; kb += kSaStage) {
+        const int m = (int)(k1 - kb < kSaStage ? k1 - kb : kSaStage);
+        __syncthreads();
+        for (int e = lane; e < m; e += 64) {
+          sJ[e] = agg[acol[kb + e]];
+          sv[e] = aval[kb + e];
+        }
+        __syncthreads();
+        for (int e = 0; e < m; ++e)
+          if (sJ[e] == J) s = s + sv[e];
+      }
+      for (int64_t q = q0; q < q1; ++q)
+        if (qcol[q] == J) s = s + qval[q];
+      if (t < n) {
+        pcol[c0 + t] = J;
+        pval[c0 + t] = fma(fi, s, J == gi ? 1.0 : 0.0);
+      }
+    }
+    __syncthreads();
+  }
+}
+
 // flag[i] = 1 if row i of the CSR matrix has a column j with mark[j] >= 0 (rows of A that reach the interface patch)
 __global__ void rows_touching_kernel(int64_t nrows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
                                      const int32_t *__restrict__ mark, uint8_t *__restrict__ flag) {

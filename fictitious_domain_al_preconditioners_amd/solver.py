@@ -34,6 +34,7 @@ ABI_SYMBOLS = [
     "alfd_get_device_memory", "alfd_set_row_blocks", "alfd_host_stream_plan",
     "alfd_host_row_blocks_from_points", "alfd_host_stream_plan_short", "alfd_set_prolongator", "alfd_set_controls", "alfd_get_timing_streamed", "alfd_get_setup_seconds",
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
+    "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
 ]
 
 
@@ -106,6 +107,11 @@ def load_library():
         "alfd_build_aggregates": (C.c_int, [vp, i32, dbl, i32, i64, i32, C.POINTER(i32)]),
         "alfd_get_aggregates": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_host_aggregate_level": (C.c_int, [i64, vp, vp, vp, i32, dbl, i32, vp, C.POINTER(i64)]),
+        "alfd_build_smoothed_aggregation": (C.c_int, [vp, i32, dbl, i32, dbl, i64, i32, C.POINTER(i32), vp]),
+        "alfd_get_prolongator": (C.c_int, [vp, C.c_int, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64),
+                                           C.POINTER(i64)]),
+        "alfd_host_smoothed_prolongator": (C.c_int, [i64, vp, vp, vp, i64, vp, vp, vp, vp, dbl, vp, i64, dbl,
+                                                     vp, vp, vp, i64, C.POINTER(i64)]),
         "alfd_comm_init_host": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
         "alfd_get_device_memory": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_set_row_blocks": (C.c_int, [vp, C.c_int, i64, vp, vp]),
@@ -224,6 +230,37 @@ class Context:
             self._ck(self._lib.alfd_get_aggregates(self._h, level, agg.ctypes.data, agg.size, C.byref(nf), C.byref(nc)))
             out.append((agg, int(nc.value)))
         return out
+
+    def build_smoothed_aggregation(self, block_size=1, threshold=0.02, max_aggregate_nodes=8, damping=4.0 / 3.0,
+                                   min_coarse=600, max_levels=7, return_omega=False):
+        """Smoothed aggregation from the uploaded operators (alfd_build_smoothed_aggregation): every level's
+        prolongator P = P_tent - omega D^-1 Aug P_tent, built on the device.  Upload A (and C / Ct / W^-1 and
+        configure an AL variant for the penalty term) first.  Returns [(Csr P, n_coarse), ...] -- the list
+        upload_problem and the oracle take; with return_omega also the damping omega of every level."""
+        nlev = C.c_int32(0)
+        omega = np.zeros(max(max_levels, 8), np.float64)   # ALFD_MAX_LEVELS - 1 entries when max_levels is out of range
+        self._ck(self._lib.alfd_build_smoothed_aggregation(self._h, block_size, threshold, max_aggregate_nodes,
+                                                           damping, min_coarse, max_levels, C.byref(nlev),
+                                                           omega.ctypes.data))
+        out = []
+        for level in range(nlev.value):
+            P = self.prolongator(level)
+            out.append((P, int(P.ncols)))
+        return (out, omega[:nlev.value].copy()) if return_omega else out
+
+    def prolongator(self, level):
+        """The CSR prolongator of a level as a problems.Csr (alfd_get_prolongator): built by
+        build_smoothed_aggregation or set by set_prolongator."""
+        from .problems import Csr
+        nf, nc, nnz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+        self._ck(self._lib.alfd_get_prolongator(self._h, level, None, None, None, 0, C.byref(nf), C.byref(nc),
+                                                C.byref(nnz)))
+        rp = np.empty(nf.value + 1, np.int64)
+        col = np.empty(nnz.value, np.int32)
+        val = np.empty(nnz.value, np.float64)
+        self._ck(self._lib.alfd_get_prolongator(self._h, level, rp.ctypes.data, col.ctypes.data, val.ctypes.data,
+                                                col.size, C.byref(nf), C.byref(nc), C.byref(nnz)))
+        return Csr(int(nf.value), int(nc.value), rp, col, val)
 
     def set_aggregate_partition(self, level, coarse_offsets):
         o = np.ascontiguousarray(coarse_offsets, np.int64)
@@ -429,6 +466,46 @@ def host_aggregate_level(m, block_size=1, threshold=0.02, max_aggregate_nodes=8)
     if rc != _abi.OK:
         raise AlfdError(rc, "alfd_host_aggregate_level failed")
     return agg, int(nc.value)
+
+
+def host_smoothed_prolongator(A, agg, n_coarse, omega, Ct=None, w_inv=None, gamma=0.0):
+    """Host-only: ONE level's smoothed-aggregation prolongator P = P_tent - omega D^-1 (A + gamma Ct diag(w_inv) Ct^T)
+    P_tent with the library's arithmetic (alfd_host_smoothed_prolongator); A, Ct problems.Csr, agg from
+    host_aggregate_level / Context.build_smoothed_aggregation.  Ct None: A alone.  Returns a problems.Csr."""
+    from .problems import Csr
+    lib = load_library()
+    rp = np.ascontiguousarray(A.row_ptr, np.int64)
+    col = np.ascontiguousarray(A.col, np.int32)
+    val = np.ascontiguousarray(A.val, np.float64)
+    agg = np.ascontiguousarray(agg, np.int32)
+    if agg.size != A.nrows:
+        raise ValueError("agg must have one entry per row of A")
+    if Ct is not None:
+        crp = np.ascontiguousarray(Ct.row_ptr, np.int64)
+        ccol = np.ascontiguousarray(Ct.col, np.int32)
+        cval = np.ascontiguousarray(Ct.val, np.float64)
+        w = np.ascontiguousarray(w_inv, np.float64)
+        if w.size != Ct.ncols:
+            raise ValueError("w_inv must have one entry per column of Ct")
+        pen = (int(Ct.ncols), crp.ctypes.data, ccol.ctypes.data, cval.ctypes.data, w.ctypes.data, float(gamma))
+    else:
+        pen = (0, None, None, None, None, 0.0)
+    prp = np.empty(A.nrows + 1, np.int64)
+    nnz = C.c_int64(0)
+
+    def call(pc, pv, cap):
+        return lib.alfd_host_smoothed_prolongator(A.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, *pen,
+                                                  agg.ctypes.data, int(n_coarse), float(omega), prp.ctypes.data, pc,
+                                                  pv, cap, C.byref(nnz))
+    rc = call(None, None, 0)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
+    pcol = np.empty(nnz.value, np.int32)
+    pval = np.empty(nnz.value, np.float64)
+    rc = call(pcol.ctypes.data, pval.ctypes.data, pcol.size)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
+    return Csr(int(A.nrows), int(n_coarse), prp, pcol, pval)
 
 
 def host_window_plan(m, lanes=64, value_index=True):

@@ -337,6 +337,39 @@ int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacit
 int alfd_host_aggregate_level(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
                               int32_t block_size, double threshold, int32_t max_aggregate_nodes, int32_t *agg,
                               int64_t *n_coarse);
+/* Smoothed aggregation (the algorithm of ML in the reference, utilities.h:304-317) from the uploaded operators alone.
+ * Per level l, from A_0 = A (slot A) and C_0 = Ct^T (slot CT):
+ *   agg_l   = the aggregation of alfd_build_aggregates on A_l (block_size, threshold, max_aggregate_nodes);
+ *   Aug_l   = A_l + gamma C_l^T W^-1 C_l when alfd_configure set an AL variant with w_inverse == ALFD_W_DIAGONAL,
+ *             gamma != 0 and aug_assembled == 0 (slot CT and diag slot ALFD_INVW uploaded), else A_l alone;
+ *   omega_l = damping / lambda, lambda = lambda_max(D^-1 Aug_l) from cheb_power_its steps of power iteration
+ *             (the start vector of alfd_setup, no safety factor), D = diag(Aug_l); ML's default damping is 4/3;
+ *   P_l     = P_tent - omega_l D^-1 Aug_l P_tent, P_tent the constant modes of agg_l (one per component), its pattern
+ *             the structural union (nothing dropped by value -- ML drops small entries), built on the device;
+ *   A_{l+1} = P_l^T A_l P_l, C_{l+1} = C_l P_l.
+ * Coarsening stops at <= min_coarse unknowns or max_levels levels.  The levels are stored as alfd_set_prolongator
+ * would store them (alfd_setup forms the Galerkin products again), the aggregates as alfd_set_aggregates
+ * (alfd_get_aggregates returns them); earlier aggregates / prolongators are cleared.  omega_out (may be NULL) receives
+ * omega_l for every built level (room for max_levels entries, ALFD_MAX_LEVELS - 1 when max_levels is out of range).
+ * Deterministic, bit for bit.  Single rank: ALFD_E_UNSUPPORTED on a partitioned context, ALFD_E_NOT_SETUP without
+ * slot A, ALFD_E_INVALID on bad arguments (damping <= 0 or not finite, ...).  Canonical order: DESIGN.md section 4. */
+int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
+                                    double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
+                                    double *omega_out);
+/* The CSR prolongator of a level (built by alfd_build_smoothed_aggregation or set by alfd_set_prolongator):
+ * row_ptr[n_fine + 1], col / val [capacity >= nnz].  NULL arrays query the sizes; ALFD_E_INVALID for a level
+ * without a CSR prolongator. */
+int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
+                         int64_t *n_fine, int64_t *n_coarse, int64_t *nnz);
+/* Host-only (no device, no context): ONE level's smoothed prolongator with the arithmetic of
+ * alfd_build_smoothed_aggregation, from the square CSR A (nrows), optionally Ct (nrows x n_mult, ct_row_ptr == NULL:
+ * no penalty term) with the W^-1 diagonal w_inv[n_mult] and gamma, the aggregates agg[nrows] (-1: empty row),
+ * n_coarse and omega.  Two calls: p_col == p_val == NULL returns *nnz (and p_row_ptr[nrows + 1] if given), then
+ * arrays with capacity >= nnz. */
+int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                                   int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
+                                   const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
+                                   int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz);
 int alfd_configure(alfd_ctx_t ctx, const alfd_config *cfg);
 /* New stop rules for the following solves WITHOUT a new alfd_setup (alfd_configure invalidates the setup): the
  * reference's SolverControl objects are plain members that a caller may change between two solve() calls

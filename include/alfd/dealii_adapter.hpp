@@ -196,6 +196,19 @@ class System {
     check(alfd_set_aggregates(ctx_, level, (int64_t)agg.size(), agg.data(), weights.empty() ? nullptr : weights.data(),
                               n_coarse));
   }
+  // Smoothed-aggregation hierarchy built by the library from the uploaded operators (ML's algorithm,
+  // utilities.h:304-317; alfd_build_smoothed_aggregation): after set_matrix / configure, before setup.
+  // Returns the number of levels; omega (optional) receives the damping of every level.
+  int build_smoothed_aggregation(int32_t block_size = 1, double threshold = 0.02, int32_t max_aggregate_nodes = 8,
+                                 double damping = 4.0 / 3.0, int64_t min_coarse = 600, int32_t max_levels = 7,
+                                 std::vector<double> *omega = nullptr) {
+    int32_t levels = 0;
+    std::vector<double> w(ALFD_MAX_LEVELS, 0.0);
+    check(alfd_build_smoothed_aggregation(ctx_, block_size, threshold, max_aggregate_nodes, damping, min_coarse,
+                                          max_levels, &levels, w.data()));
+    if (omega) omega->assign(w.begin(), w.begin() + levels);
+    return levels;
+  }
   // `Use diagonal inverse = false` / `Diagonal mass immersed = false` (immersed_laplace.cc:859-877,
   // stokes...:979-985, elliptic_interface.cc:713-737): the exact W^-1 = (M^-1)^2 (mode
   // ALFD_W_MASS_INV_SQUARED) or M^-1 (ALFD_W_MASS_INV) from the immersed mass matrix; applied to the
