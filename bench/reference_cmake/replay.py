@@ -6,6 +6,9 @@ pinned (needs a deal.II install, which this repository's pi
     python bench/reference_cmake/replay.py run/stokes_immersed_boundary.alfd [--reference-log run/stokes.log]
                                            [--inner-prec multilevel|sa-multilevel|chebyshev] [--support-points points.npy]
 
+A dump with grad_div_in_A = 0 (`Grad-div stabilization = false`) replays with the identity inner preconditioner, the
+reference's, or with --inner-prec chebyshev; never multilevel.
+
 The inner preconditioner differs from the reference's by construction (Trilinos ML there; here the algebraic aggregation
 of alfd_build_aggregates on the dumped A, or geometric transfers when the caller supplies them; sa-multilevel builds
 ML's algorithm, smoothed aggregation, from the dumped operators with alfd_build_smoothed_aggregation), so OUTER counts
@@ -60,7 +63,13 @@ def main():
         ctx.set_matrix(slot, m)
     for slot, d in diags.items():
         ctx.set_diag(slot, d)
-    if args.inner_prec in ("multilevel", "sa-multilevel") and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
+    gd_off = cfg.variant in (_abi.AL_STOKES, _abi.AL_STOKES_DIAG) and not cfg.grad_div_in_A
+    if gd_off and args.inner_prec in ("multilevel", "sa-multilevel"):
+        # Aug = A + gamma Ct invW C + gamma_gd Bt Mp^-1 B has no multilevel preconditioner (ExcNotImplemented in the
+        # reference): such dumps replay with the identity inner preconditioner of the reference, or --inner-prec chebyshev
+        print("grad_div_in_A = 0: no multilevel inner preconditioner; replaying with the identity inner preconditioner")
+        cfg.inner_prec = _abi.PREC_IDENTITY
+    elif args.inner_prec in ("multilevel", "sa-multilevel") and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
         cfg.inner_prec = _abi.PREC_MULTILEVEL
         cfg.ml_smooth_degree, cfg.ml_smooth_ratio, cfg.ml_coarse_degree = 4, 256.0, 10
         ctx.configure(cfg)

@@ -241,6 +241,12 @@ struct alfd_ctx {
   double *n_r = nullptr, *n_z = nullptr, *n_p = nullptr, *n_Ap = nullptr;
   double *n_sc = nullptr, *n_sc_host = nullptr, *n_partial = nullptr, *n_gather = nullptr;
   int64_t mass_its = 0;
+  // grad_div_in_A = 0 (Stokes): Aug = A + gamma Ct invW C + gamma_gd Bt Mp^-1 B.  The nested Mp solve shares the
+  // n_* set with the mass solve above (n_owner: which of the two holds it, 0 = free); gd_bx / gd_q hold B x and q
+  int n_owner = 0;
+  double *gd_bx = nullptr, *gd_q = nullptr;
+  int nmp_group = 16;               // iterations the host enqueues per state read ("nested_mp_group")
+  int nmp_host_stepped = 0;         // "nested_mp_host_stepped" = 1: host-stepped pcg() on one rank too
   // RationalPreconditioner state (batched CG over the 21 immersed systems)
   HostCsr h_M, h_K;                                    // host copies of the (tiny) immersed matrices
   // multilevel inner preconditioner
@@ -966,9 +972,16 @@ static inline int64_t op_npad(const alfd_ctx *ctx, int op) {
 }
 
 static int winv_scale(alfd_ctx *ctx, double alpha, const double *src, double *dst);
+static int nested_mp_solve(alfd_ctx *ctx, const double *b, double *x);
+
+// grad_div_in_A = 0 on a Stokes variant: Aug carries the term gamma_gd Bt Mp^-1 B (stokes...:991-995)
+static inline bool gd_nested(const alfd_ctx *ctx) {
+  return !ctx->cfg.grad_div_in_A && (ctx->cfg.variant == ALFD_AL_STOKES || ctx->cfg.variant == ALFD_AL_STOKES_DIAG);
+}
 
 // exact_w: apply the configured W^-1 (the operator the inner CG and the outer system see);
-// false: the diagonal weight (everything inside the inner preconditioner).
+// false: the diagonal weight (everything inside the inner preconditioner).  The same split holds for
+// the grad-div-off term: exact_w solves q = Mp^-1 (B x), otherwise q = l .* (B x), l = ALFD_MP_LUMPED_INV.
 static int op_apply(alfd_ctx *ctx, int op, const double *x, double *y, bool exact_w = false) {
   const double *w = ctx->diag[ALFD_INVW];
   switch (op) {
@@ -981,7 +994,15 @@ static int op_apply(alfd_ctx *ctx, int op, const double *x, double *y, bool exac
       } else {
         RC(spmv(ctx, ALFD_C, x, ctx->t_lam, 2, 0.0, w));
       }
-      return spmv(ctx, ALFD_CT, ctx->t_lam, y, 1, ctx->cfg.gamma);
+      RC(spmv(ctx, ALFD_CT, ctx->t_lam, y, 1, ctx->cfg.gamma));
+      if (!gd_nested(ctx)) return ALFD_OK;
+      if (exact_w) {
+        RC(spmv(ctx, ALFD_B, x, ctx->gd_bx, 0));
+        RC(nested_mp_solve(ctx, ctx->gd_bx, ctx->gd_q));
+      } else {
+        RC(spmv(ctx, ALFD_B, x, ctx->gd_q, 2, 0.0, ctx->diag[ALFD_MP_LUMPED_INV]));
+      }
+      return spmv(ctx, ALFD_BT, ctx->gd_q, y, 1, ctx->cfg.gamma_grad_div);
     case OP_MASS:
       return spmv(ctx, ALFD_M, x, y, 0);
     case OP_MP:
@@ -1116,31 +1137,152 @@ static int inner_solve(alfd_ctx *ctx, int op, const double *b, double *x) {
 
 static inline bool is_elliptic(int v) { return v == ALFD_AL_ELL_IDEAL || v == ALFD_AL_ELL_MODIFIED; }
 
+// The nested solves -- the exact-W^-1 mass solve and the Mp solve of the grad-div-off Aug -- may start in
+// the middle of an inner-CG iteration (inside Aug p) or of the outer system_apply, so they run on their own
+// CG vectors, scalar table and reduction buffers, the n_* set, swapped in for the w_* set pcg() works on.
+// The two share that set because they are never live at the same time: mass_solve runs to completion inside
+// winv_scale, before op_apply / system_apply reach the Bt Mp^-1 B term, and neither solve's operator (M, Mp)
+// applies W^-1 or Aug.  n_owner records the holder; a second claim is an internal error.
+enum { NESTED_FREE = 0, NESTED_MASS = 1, NESTED_MP = 2 };
+static int nested_claim(alfd_ctx *ctx, int who) {
+  if (ctx->n_owner != NESTED_FREE)
+    return ctx->err = "nested solve started while another holds its work vectors", ALFD_E_INVALID;
+  ctx->n_owner = who;
+  return ALFD_OK;
+}
+static void nested_swap_ws(alfd_ctx *ctx) {
+  std::swap(ctx->w_r, ctx->n_r);
+  std::swap(ctx->w_z, ctx->n_z);
+  std::swap(ctx->w_p, ctx->n_p);
+  std::swap(ctx->w_Ap, ctx->n_Ap);
+  std::swap(ctx->sc, ctx->n_sc);
+  std::swap(ctx->sc_host, ctx->n_sc_host);
+  std::swap(ctx->partial, ctx->n_partial);
+  std::swap(ctx->gather, ctx->n_gather);
+}
+
 // x = M^-1 b by Jacobi-preconditioned CG to alfd_config::mass (UMFPACK in the reference,
-// stokes...:966-968).  It may run in the middle of an outer inner-CG iteration (inside
-// Aug p), so it works on its own CG vectors, scalar table and reduction buffers.
+// stokes...:966-968).
 static int mass_solve(alfd_ctx *ctx, const double *b, double *x) {
-  auto swap_ws = [&]() {
-    std::swap(ctx->w_r, ctx->n_r);
-    std::swap(ctx->w_z, ctx->n_z);
-    std::swap(ctx->w_p, ctx->n_p);
-    std::swap(ctx->w_Ap, ctx->n_Ap);
-    std::swap(ctx->sc, ctx->n_sc);
-    std::swap(ctx->sc_host, ctx->n_sc_host);
-    std::swap(ctx->partial, ctx->n_partial);
-    std::swap(ctx->gather, ctx->n_gather);
-  };
   int its = 0;
   State st = FAILURE;
   double res = 0;
-  swap_ws();
+  RC(nested_claim(ctx, NESTED_MASS));
+  nested_swap_ws(ctx);
   const int rc = pcg(ctx, OP_MASS, ALFD_PREC_JACOBI, ctx->cfg.mass, b, x, &its, &st, &res);
-  swap_ws();
+  nested_swap_ws(ctx);
+  ctx->n_owner = NESTED_FREE;
   if (rc != ALFD_OK) return rc;
   ctx->mass_its += its;
   if (st == FAILURE) {
     if (std::isnan(res)) return ctx->err = "mass-matrix CG breakdown (NaN)", ALFD_E_BREAKDOWN;
     return ctx->err = "mass-matrix CG (exact W^-1) did not converge", ALFD_E_NO_CONVERGENCE_INNER;
+  }
+  return ALFD_OK;
+}
+
+// Device-stepped form of pcg(ctx, OP_MP, ALFD_PREC_JACOBI, mp_inner, ..) on one rank: the stop rule runs
+// on the device (nmp_finish_kernel), the host enqueues nmp_group iterations at a time and reads the state
+// once per group through the mapped scalar mirror: 5 launches per iteration plus one mirror launch per group.
+// Same arithmetic as pcg(): same bits, same step.  Works on the n_* set (the caller holds it).
+static int pcg_mp_device(alfd_ctx *ctx, const double *b, double *x, int *its_out, State *st_out, double *res_out) {
+  const alfd_control &ctrl = ctx->cfg.mp_inner;
+  const DevCsr &m = ctx->mat[ALFD_MP];
+  const int64_t npad = op_npad(ctx, OP_MP), nb = npad / kChunk;
+  const double *l = ctx->diag[ALFD_MP_LUMPED_INV];
+  double *r = ctx->n_r, *z = ctx->n_z, *p = ctx->n_p, *Ap = ctx->n_Ap, *sc = ctx->n_sc;
+  double *part_rr = ctx->n_partial, *part_rz = ctx->n_partial + ctx->pstride, *part_pap = ctx->n_partial + 2 * ctx->pstride;
+  const unsigned grid = (unsigned)nb;
+  const int sgrid = grid_for_rows(m.nrows, m.L);
+  auto update = [&](int first) {
+    Timer tm(ctx, ALFD_T_VEC, first ? 40.0 * npad : 72.0 * npad);
+    hipLaunchKernelGGL(nmp_update_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, first, part_pap, nb, b, l, p,
+                       Ap, x, r, z, part_rr, part_rz);
+  };
+  auto finish = [&](int step) {
+    Timer tm(ctx, ALFD_T_DOT, 16.0 * nb);
+    hipLaunchKernelGGL(nmp_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, part_rr, part_rz, nb, sc, step,
+                       ctrl.kind, ctrl.max_steps, ctrl.tol, ctrl.reduce);
+  };
+  if (nb > 0) update(1);
+  finish(0);
+  HIPC(hipGetLastError());
+  int enq = 0;   // iterations enqueued so far
+  for (;;) {
+    const int group = std::max(1, ctx->nmp_group);
+    for (int g = 0; g < group && nb > 0 && enq < std::max(ctrl.max_steps, 0); ++g) {
+      const int it = ++enq;
+      {
+        Timer tm(ctx, ALFD_T_VEC, it == 1 ? 16.0 * npad : 24.0 * npad);
+        hipLaunchKernelGGL(nmp_p_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, it == 1 ? 1 : 0, z, p);
+      }
+      {
+        Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes());
+#define ALFD_NMP_S(LL)                                                                                          \
+  hipLaunchKernelGGL((nmp_spmv_kernel<LL>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows, m.rp, m.col, \
+                     m.val, p, Ap)
+        switch (m.L) {
+          case 4: ALFD_NMP_S(4); break;
+          case 8: ALFD_NMP_S(8); break;
+          case 16: ALFD_NMP_S(16); break;
+          case 32: ALFD_NMP_S(32); break;
+          default: ALFD_NMP_S(64); break;
+        }
+#undef ALFD_NMP_S
+      }
+      {
+        Timer tm(ctx, ALFD_T_DOT, 16.0 * npad);
+        hipLaunchKernelGGL(nmp_dot_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, p, Ap, part_pap);
+      }
+      update(0);
+      finish(it);
+    }
+    HIPC(hipGetLastError());
+    {
+      Timer tm(ctx, ALFD_T_DOT, 8.0 * (S_NRTOL + 1));
+      hipLaunchKernelGGL(mirror_scalars_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, sc, ctx->n_sc_host, (int)(S_NRTOL + 1));
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(ctx->stream));
+    const double *h = ctx->n_sc_host;
+    if (h[S_NSTATE] != 0.0) {
+      *its_out = (int)h[S_NSTEP];
+      *st_out = h[S_NSTATE] == 1.0 ? SUCCESS : FAILURE;
+      *res_out = std::sqrt(h[S_RR]);
+      return ALFD_OK;
+    }
+    if (enq >= ctrl.max_steps) return ctx->err = "nested Mp CG: the device stop rule did not end the solve", ALFD_E_INVALID;
+  }
+}
+
+// q = Mp^-1 b: the same solve as the preconditioner's pressure block (lumped-Jacobi CG to alfd_config::mp_inner,
+// zero start), for the gamma_gd Bt Mp^-1 B term of Aug when grad_div_in_A = 0 (stokes...:933-956, 991-995).
+// Device-stepped on one rank; partitioned contexts (dots through the host or an all-gather) and the tunable
+// "nested_mp_host_stepped" take the host-stepped pcg().  Its iterations count as mp_iterations.
+static int nested_mp_solve(alfd_ctx *ctx, const double *b, double *x) {
+  int its = 0;
+  State st = FAILURE;
+  double res = 0;
+  RC(nested_claim(ctx, NESTED_MP));
+  int rc;
+  if (ctx->nranks == 1 && !ctx->nmp_host_stepped && !ctx->mat[ALFD_MP].sparse) {
+    rc = pcg_mp_device(ctx, b, x, &its, &st, &res);
+  } else {
+    nested_swap_ws(ctx);
+    rc = pcg(ctx, OP_MP, ALFD_PREC_JACOBI, ctx->cfg.mp_inner, b, x, &its, &st, &res);
+    nested_swap_ws(ctx);
+  }
+  ctx->n_owner = NESTED_FREE;
+  if (rc != ALFD_OK) return rc;
+  ctx->mp_its += its;
+  if (ctx->cfg.log_level >= 3 && ctx->rank == 0)
+    std::printf("DEAL:mp_aug:cg::%s step %d value %.17g\n", st == SUCCESS ? "Convergence" : "Failure", its, res);
+  if (st == FAILURE) {
+    if (std::isnan(res)) return ctx->err = "nested Mp CG breakdown (NaN)", ALFD_E_BREAKDOWN;
+    if (ctx->cfg.on_inner_failure == ALFD_INNER_THROW)
+      return ctx->err = "nested Mp CG (Bt Mp^-1 B of Aug) did not converge (SolverControl::NoConvergence)",
+             ALFD_E_NO_CONVERGENCE_INNER;
+    ctx->inner_failures++;
   }
   return ALFD_OK;
 }
@@ -1354,7 +1496,13 @@ static int system_apply(alfd_ctx *ctx, const double *x, double *y) {
       }
       RC(spmv(ctx, ALFD_CT, ctx->t_lam, y0, 1, c.gamma));
     }
-    if (ctx->nblocks == 3) {
+    if (gd_nested(ctx)) {
+      // y0 = fma(gamma_gd, (Bt q)_i, y0), q = Mp^-1 (B x0), before + Bt x1; B x0 is block 1 of y
+      RC(spmv(ctx, ALFD_B, x0, y + off[1], 0));
+      RC(nested_mp_solve(ctx, y + off[1], ctx->gd_q));
+      RC(spmv(ctx, ALFD_BT, ctx->gd_q, y0, 1, c.gamma_grad_div));
+      RC(spmv(ctx, ALFD_BT, x + off[1], y0, 1, 1.0));
+    } else if (ctx->nblocks == 3) {
       RC(spmv(ctx, ALFD_BT, x + off[1], y0, 1, 1.0));
       RC(spmv(ctx, ALFD_B, x0, y + off[1], 0));
     }
@@ -3180,40 +3328,50 @@ static int ws_alloc_zero(alfd_ctx *ctx, double **p, int64_t count) {
 }
 
 // dinv = 1 / (diag(Adiag) + g * sum_k w_k R_ik^2): the diagonal of Adiag + g R diag(w) R^T
-static int diag_plus_m(alfd_ctx *ctx, const DevCsr &A, DevCsr &R, double g, int64_t n, double *dinv);
+// (w = ALFD_INVW).  The general form takes the weight w, starts from ctx->dA instead of diag(A) when A is
+// null, and with invert = false leaves the sum itself in dinv (which may be ctx->dA): chained calls add
+// several such terms in a fixed order.
+static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *w, double g, int64_t n, double *dinv,
+                       bool invert);
+static int diag_plus_m(alfd_ctx *ctx, const DevCsr &A, DevCsr &R, double g, int64_t n, double *dinv) {
+  return diag_plus_m(ctx, &A, R, ctx->diag[ALFD_INVW], g, n, dinv, true);
+}
 static int diag_plus(alfd_ctx *ctx, int slot_diag, int slot_rows, double g, int64_t n, double *dinv) {
   return diag_plus_m(ctx, ctx->mat[slot_diag], ctx->mat[slot_rows], g, n, dinv);
 }
-static int diag_plus_m(alfd_ctx *ctx, const DevCsr &A, DevCsr &R, double g, int64_t n, double *dinv) {
-  if (pad_chunk(n) > ctx->diag_cap) {
+static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *w, double g, int64_t n, double *dinv,
+                       bool invert) {
+  if (A && pad_chunk(n) > ctx->diag_cap) {
     // a replicated multigrid level may be longer than this rank's largest block (many ranks): grow the two scratch vectors
     RC(ws_alloc_zero(ctx, &ctx->dA, pad_chunk(n)));
     RC(ws_alloc_zero(ctx, &ctx->s_aug, pad_chunk(n)));
     ctx->diag_cap = pad_chunk(n);
   }
-  HIPC(hipMemsetAsync(ctx->dA, 0, pad_chunk(n) * sizeof(double), ctx->stream));
+  if (A) HIPC(hipMemsetAsync(ctx->dA, 0, pad_chunk(n) * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(ctx->s_aug, 0, pad_chunk(n) * sizeof(double), ctx->stream));
-  const int grid = grid_for_rows(A.nrows, A.L);
-#define ALFD_DIAG(LL)                                                                                   \
-  hipLaunchKernelGGL((extract_diag_kernel<LL>), dim3(grid), dim3(kBlock), 0, ctx->stream, A.nrows, A.rp, \
-                     A.col, A.val, ctx->dA)
-  switch (A.L) {
-    case 4: ALFD_DIAG(4); break;
-    case 8: ALFD_DIAG(8); break;
-    case 16: ALFD_DIAG(16); break;
-    case 32: ALFD_DIAG(32); break;
-    default: ALFD_DIAG(64); break;
-  }
+  if (A) {
+    const int grid = grid_for_rows(A->nrows, A->L);
+#define ALFD_DIAG(LL)                                                                                      \
+  hipLaunchKernelGGL((extract_diag_kernel<LL>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrows, A->rp, \
+                     A->col, A->val, ctx->dA)
+    switch (A->L) {
+      case 4: ALFD_DIAG(4); break;
+      case 8: ALFD_DIAG(8); break;
+      case 16: ALFD_DIAG(16); break;
+      case 32: ALFD_DIAG(32); break;
+      default: ALFD_DIAG(64); break;
+    }
 #undef ALFD_DIAG
+  }
   // a rank with no rows of R of its own may still own W entries its peers need
   if (ctx->nranks > 1 && (ctx->local || ctx->host_alltoallv || R.n_halo > 0 || R.send_off.back() > 0))
-    RC(halo_exchange(ctx, R, ctx->diag[ALFD_INVW]));
+    RC(halo_exchange(ctx, R, w));
   if (R.n_list > 0)
     hipLaunchKernelGGL(aug_diag_rows_kernel, dim3((unsigned)((R.n_list + 255) / 256)), dim3(256), 0,
                        ctx->stream, R.n_list, R.rp, R.col, R.val, R.sparse ? R.rows : nullptr,
-                       ctx->diag[ALFD_INVW], R.halo, R.n_local_cols, ctx->s_aug);
+                       w, R.halo, R.n_local_cols, ctx->s_aug);
   hipLaunchKernelGGL(aug_diag_finish_kernel, dim3((unsigned)std::max<int64_t>(1, (n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                     g, ctx->dA, ctx->s_aug, dinv);
+                     g, ctx->dA, ctx->s_aug, dinv, invert ? 1 : 0);
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
@@ -5269,8 +5427,13 @@ static int setup(alfd_ctx *ctx) {
   if (c.fgmres_flavour == ALFD_FGMRES_DEALII_95 && c.restart < 2)
     return ctx->err = "the deal.II <= 9.5 FGMRES loop needs restart >= 2", ALFD_E_INVALID;
   const bool ell = is_elliptic(c.variant);
-  if (!c.grad_div_in_A && (c.variant == ALFD_AL_STOKES || c.variant == ALFD_AL_STOKES_DIAG))
-    return ctx->err = "grad_div_in_A = 0 (nested Bt Mp^-1 B in Aug) not implemented", ALFD_E_UNSUPPORTED;
+  const bool gd_off = !c.grad_div_in_A && (c.variant == ALFD_AL_STOKES || c.variant == ALFD_AL_STOKES_DIAG);
+  if (gd_off && c.inner_prec == ALFD_PREC_MULTILEVEL)
+    return ctx->err = "grad_div_in_A = 0: no multilevel inner preconditioner (the reference throws ExcNotImplemented for "
+                      "AMG without grad-div); use identity, Jacobi or Chebyshev",
+           ALFD_E_UNSUPPORTED;
+  if (gd_off && c.aug_assembled)
+    return ctx->err = "grad_div_in_A = 0 needs the factored Aug (aug_assembled = 0)", ALFD_E_UNSUPPORTED;
   if ((c.inner_prec == ALFD_PREC_CHEBYSHEV || c.inner_prec == ALFD_PREC_MULTILEVEL) &&
       (c.cheb_degree < 1 || c.cheb_power_its < 1 || !(c.cheb_eig_ratio > 1.0)))
     return ctx->err = "bad Chebyshev parameters", ALFD_E_INVALID;
@@ -5350,6 +5513,24 @@ static int setup(alfd_ctx *ctx) {
   RC(ws_alloc_zero(ctx, &ctx->st_out, N));
   for (int k = 0; k < 7; ++k) ctx->lam_max[k] = 0;
   if (ctx->n_sc_host) hipHostFree(ctx->n_sc_host), ctx->n_sc_host = nullptr;
+  ctx->n_owner = NESTED_FREE;
+  // the n_* set of the nested solves (mass_solve, nested_mp_solve): as long as the longer of the two blocks
+  const int64_t n_nested = std::max<int64_t>(c.w_inverse != ALFD_W_DIAGONAL ? pad_chunk(ctx->n[last]) : 0,
+                                             gd_off ? pad_chunk(ctx->n[1]) : 0);
+  if (n_nested > 0) {
+    RC(ws_alloc_zero(ctx, &ctx->n_r, n_nested));
+    RC(ws_alloc_zero(ctx, &ctx->n_z, n_nested));
+    RC(ws_alloc_zero(ctx, &ctx->n_p, n_nested));
+    RC(ws_alloc_zero(ctx, &ctx->n_Ap, n_nested));
+    RC(ws_alloc_zero(ctx, &ctx->n_sc, kNumScalars));
+    HIPC(hipHostMalloc((void **)&ctx->n_sc_host, kNumScalars * sizeof(double), hipHostMallocMapped));
+    RC(ws_alloc_zero(ctx, &ctx->n_partial, (int64_t)(kMaxBasis + 2) * ctx->pstride));
+    RC(ws_alloc_zero(ctx, &ctx->n_gather, (int64_t)ctx->nranks * (kMaxBasis + 2)));
+  }
+  if (gd_off) {
+    RC(ws_alloc_zero(ctx, &ctx->gd_bx, pad_chunk(ctx->n[1])));
+    RC(ws_alloc_zero(ctx, &ctx->gd_q, pad_chunk(ctx->n[1])));
+  }
   if (c.w_inverse != ALFD_W_DIAGONAL) {
     // exact W^-1 = (M^-1)^2 or M^-1: nested Jacobi CG on the immersed mass matrix
     if (c.w_inverse != ALFD_W_MASS_INV_SQUARED && c.w_inverse != ALFD_W_MASS_INV)
@@ -5373,14 +5554,6 @@ static int setup(alfd_ctx *ctx) {
     HIPC(hipStreamSynchronize(ctx->stream));
     RC(ws_alloc_zero(ctx, &ctx->m_tmp, nlp));
     RC(ws_alloc_zero(ctx, &ctx->m_tmp2, nlp));
-    RC(ws_alloc_zero(ctx, &ctx->n_r, nlp));
-    RC(ws_alloc_zero(ctx, &ctx->n_z, nlp));
-    RC(ws_alloc_zero(ctx, &ctx->n_p, nlp));
-    RC(ws_alloc_zero(ctx, &ctx->n_Ap, nlp));
-    RC(ws_alloc_zero(ctx, &ctx->n_sc, kNumScalars));
-    HIPC(hipHostMalloc((void **)&ctx->n_sc_host, kNumScalars * sizeof(double), hipHostMallocMapped));
-    RC(ws_alloc_zero(ctx, &ctx->n_partial, (int64_t)(kMaxBasis + 2) * ctx->pstride));
-    RC(ws_alloc_zero(ctx, &ctx->n_gather, (int64_t)ctx->nranks * (kMaxBasis + 2)));
   }
   const bool cheb = c.inner_prec == ALFD_PREC_CHEBYSHEV || c.inner_prec == ALFD_PREC_MULTILEVEL;
   if (rat) {
@@ -5471,7 +5644,15 @@ static int setup(alfd_ctx *ctx) {
   std::unique_ptr<PhaseClock> diag_clock(new PhaseClock(ctx, ALFD_SETUP_DIAG_LAMBDA));
   if (c.aug_assembled && is_elliptic(c.variant))
     return ctx->err = "aug_assembled (operator form) is implemented for the AL2 / Stokes variants", ALFD_E_UNSUPPORTED;
-  RC(diag_plus(ctx, ALFD_A, ALFD_CT, c.aug_assembled ? 0.0 : c.gamma, ctx->n[0], ctx->dinv_aug));
+  if (gd_off) {
+    // d_i = fma(gamma_gd, sum_k l_k b_ki^2, fma(gamma, sum_k w_k c_ki^2, a_ii)), then 1 / d_i: the diagonal of the
+    // surrogate Aug the inner preconditioner sees (op_apply, exact_w = false); DESIGN section 4
+    RC(diag_plus_m(ctx, &ctx->mat[ALFD_A], ctx->mat[ALFD_CT], ctx->diag[ALFD_INVW], c.gamma, ctx->n[0], ctx->dA, false));
+    RC(diag_plus_m(ctx, nullptr, ctx->mat[ALFD_BT], ctx->diag[ALFD_MP_LUMPED_INV], c.gamma_grad_div, ctx->n[0],
+                   ctx->dinv_aug, true));
+  } else {
+    RC(diag_plus(ctx, ALFD_A, ALFD_CT, c.aug_assembled ? 0.0 : c.gamma, ctx->n[0], ctx->dinv_aug));
+  }
   if (ell) {
     // diag(A22_aug) = diag(A2) + gamma2 sum_k w_k M_ik^2
     RC(ws_alloc_zero(ctx, &ctx->dinv_a22, pad_chunk(ctx->n[1])));
@@ -5870,6 +6051,8 @@ int alfd_build_aggregates(alfd_ctx_t ctx, int32_t block_size, double threshold, 
                           int64_t min_coarse, int32_t max_levels, int32_t *levels_out) {
   CHECK_CTX();
   if (ctx->nranks > 1) return ctx->err = "alfd_build_aggregates is single-rank", ALFD_E_UNSUPPORTED;
+  if (ctx->configured && gd_nested(ctx))
+    return ctx->err = "alfd_build_aggregates: grad_div_in_A = 0 has no multilevel inner preconditioner", ALFD_E_UNSUPPORTED;
   if (!ctx->mat[ALFD_A].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
   if (block_size < 1 || !(threshold >= 0.0) || max_aggregate_nodes < 2 || min_coarse < 1) return ALFD_E_INVALID;
   if (ctx->mat[ALFD_A].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
@@ -5930,6 +6113,8 @@ int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double t
                                     double *omega_out) {
   CHECK_CTX();
   if (ctx->nranks > 1) return ctx->err = "alfd_build_smoothed_aggregation is single-rank", ALFD_E_UNSUPPORTED;
+  if (ctx->configured && gd_nested(ctx))
+    return ctx->err = "alfd_build_smoothed_aggregation: grad_div_in_A = 0 has no multilevel inner preconditioner", ALFD_E_UNSUPPORTED;
   if (!ctx->mat[ALFD_A].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
   if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
       !(damping > 0.0) || !std::isfinite(damping))
@@ -6821,6 +7006,15 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "batch_major_xcd") == 0) {
     ctx->vs_xcd = value != 0;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "nested_mp_group") == 0) {   // iterations of the device-stepped nested Mp CG per state read
+    if (value < 1 || value > 1000) return ctx->err = "nested_mp_group: 1..1000", ALFD_E_INVALID;
+    ctx->nmp_group = value;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "nested_mp_host_stepped") == 0) {   // 1: the host-stepped pcg() for the nested Mp CG on one rank
+    ctx->nmp_host_stepped = value != 0;
     return ALFD_OK;
   }
   return ctx->err = std::string("unknown tunable ") + name, ALFD_E_INVALID;

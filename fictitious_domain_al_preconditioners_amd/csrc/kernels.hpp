@@ -1431,10 +1431,14 @@ __global__ void aug_diag_rows_kernel(int64_t n_sr, const int64_t *__restrict__ r
     s_out[rows ? rows[r] : r] = s;
   }
 }
-__global__ void aug_diag_finish_kernel(int64_t n, double gamma, const double *__restrict__ dA,
-                                       const double *__restrict__ s, double *__restrict__ dinv) {
+// invert = 0: dinv[i] = fma(gamma, s_i, dA[i]) itself (dinv may be dA), for a further term
+__global__ void aug_diag_finish_kernel(int64_t n, double gamma, const double *dA, const double *__restrict__ s,
+                                       double *dinv, int invert) {
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
-  if (i < n) dinv[i] = 1.0 / fma(gamma, s[i], dA[i]);
+  if (i < n) {
+    const double d = fma(gamma, s[i], dA[i]);
+    dinv[i] = invert ? 1.0 / d : d;
+  }
 }
 // power-iteration start vector: v_i = 1 + ((g*2654435761) & 1023)/1024, g = global index
 __global__ void hash_vector_kernel(int64_t n, int64_t goff, double *__restrict__ v) {
@@ -1718,6 +1722,175 @@ __global__ void gather_rows_kernel(int64_t nlist, const int32_t *__restrict__ ro
     ocol[o0 + k] = col[k0 + k];
     oval[o0 + k] = val[k0 + k];
   }
+}
+
+// ---- device-stepped lumped-Jacobi PCG on Mp (the Bt Mp^-1 B term of Aug when grad_div_in_A = 0)
+// The stop rule (Control::check) runs on the device, so the host enqueues a group of iterations and reads
+// the state once per group.  Five launches per iteration, in pcg()'s canonical order:
+//   P  p = z (first) or fma(beta, p, z)
+//   S  Ap = Mp p: spmv_kernel's canonical L-lane rows, grid-stride over all resident workgroups
+//   D  the p.Ap chunk partials (dot_partial_kernel)
+//   U  alpha = rz / pAp from those partials (every workgroup takes the same second stage), then
+//      x = fma(alpha, p, x), r = fma(-alpha, Ap, r), z = l .* r, and the r.r and r.z chunk partials
+//   F  rr, rz = second stages; res = sqrt(rr); Control::check(step, res); beta = rz / rz_old
+// Every kernel of an iteration returns at once when the state word sc[S_NSTATE] is no longer
+// ITERATE (0), so nothing runs past convergence but the launch itself.  All partials use the dot's
+// thread<->element map and all second stages dot_final_kernel's order: the bits are those of pcg().
+enum { S_NSTATE = S_H, S_NSTEP = S_H + 1, S_NRES = S_H + 2, S_NRTOL = S_H + 3 };
+
+__device__ __forceinline__ bool nmp_stopped(const double *sc) { return sc[S_NSTATE] != 0.0; }
+
+// second stage of dot_final_kernel (thread-strided sequential adds, then the 256-thread tree); every
+// thread returns the sum
+__device__ __forceinline__ double nmp_second_stage(const double *__restrict__ part, int64_t nb, double *lds4) {
+  double acc = 0.0;
+  for (int64_t i = threadIdx.x; i < nb; i += kBlock) acc = acc + part[i];
+  return block_reduce_256(acc, lds4);
+}
+
+// U, first = 1: r = b, x = 0, Ap = 0 (pcg()'s start; Ap's padding must stay 0); first = 0: alpha from the
+// p.Ap partials (FIN_ALPHA of dot_final_kernel), the x / r update.  Then z = l .* r and the chunk partials of
+// r.r (part_rr) and r.z (part_rz).
+__global__ __launch_bounds__(kBlock) void nmp_update_kernel(const double *__restrict__ sc, int first,
+                                                            const double *__restrict__ part_pap, int64_t nb,
+                                                            const double *__restrict__ b,
+                                                            const double *__restrict__ l,
+                                                            const double *__restrict__ p, double *__restrict__ Ap,
+                                                            double *__restrict__ x, double *__restrict__ r,
+                                                            double *__restrict__ z, double *__restrict__ part_rr,
+                                                            double *__restrict__ part_rz) {
+  __shared__ double lds_a[4], lds_rr[4], lds_rz[4];
+  if (!first && nmp_stopped(sc)) return;
+  double a = 0.0, na = 0.0;
+  if (!first) {
+    const double pap = nmp_second_stage(part_pap, nb, lds_a);
+    a = sc[S_RZ] / pap;
+    na = -a;
+  }
+  double arr = 0.0, arz = 0.0;
+  ALFD_FOR_PAIRS(i) {
+    double2 rv, xv;
+    if (first) {
+      rv = ld2(b, i);
+      xv = make_double2(0.0, 0.0);
+      st2(Ap, i, make_double2(0.0, 0.0));
+    } else {
+      const double2 pv = ld2(p, i), av = ld2(Ap, i);
+      xv = ld2(x, i);
+      rv = ld2(r, i);
+      xv.x = fma(a, pv.x, xv.x);
+      xv.y = fma(a, pv.y, xv.y);
+      rv.x = fma(na, av.x, rv.x);
+      rv.y = fma(na, av.y, rv.y);
+    }
+    st2(x, i, xv);
+    st2(r, i, rv);
+    const double2 lv = ld2(l, i);
+    double2 zv;
+    zv.x = lv.x * rv.x;
+    zv.y = lv.y * rv.y;
+    st2(z, i, zv);
+    arr = fma(rv.x, rv.x, arr);
+    arr = fma(rv.y, rv.y, arr);
+    arz = fma(rv.x, zv.x, arz);
+    arz = fma(rv.y, zv.y, arz);
+  }
+  const double srr = block_reduce_256(arr, lds_rr);
+  const double srz = block_reduce_256(arz, lds_rz);
+  if (threadIdx.x == 0) {
+    part_rr[blockIdx.x] = srr;
+    part_rz[blockIdx.x] = srz;
+  }
+}
+
+// F: one workgroup.  Control::check of alfd.hip, step by step (step 0 fixes the reference value of
+// the reduction kind); the state word is written last, by an ordinary store of thread 0.
+__global__ __launch_bounds__(kBlock) void nmp_finish_kernel(const double *__restrict__ part_rr,
+                                                            const double *__restrict__ part_rz, int64_t nb,
+                                                            double *__restrict__ sc, int step, int kind,
+                                                            int max_steps, double tol, double reduce) {
+  __shared__ double lds_rr[4], lds_rz[4];
+  if (step > 0 && nmp_stopped(sc)) return;
+  const double rr = nmp_second_stage(part_rr, nb, lds_rr);
+  const double rz = nmp_second_stage(part_rz, nb, lds_rz);
+  if (threadIdx.x == 0) {
+    const double v = sqrt(rr);
+    if (step == 0) sc[S_NRTOL] = v * reduce;
+    const double reduced_tol = step == 0 ? v * reduce : sc[S_NRTOL];
+    int state = 0;   // ITERATE
+    if (kind == ALFD_CTRL_REDUCTION && v < reduced_tol) state = 1;
+    else if (kind == ALFD_CTRL_FIXED_ITERS && step >= max_steps) state = 1;
+    else if (v <= tol) state = 1;
+    else if (step >= max_steps || isnan(v)) state = 2;
+    sc[S_RR] = rr;
+    sc[S_NRES] = v;
+    sc[S_NSTEP] = (double)step;
+    if (state == 0) {   // FIN_RZ of the next iteration
+      const double old = sc[S_RZ];
+      sc[S_RZ_OLD] = old;
+      sc[S_RZ] = rz;
+      sc[S_BETA] = rz / old;
+    }
+    sc[S_NSTATE] = (double)state;
+  }
+}
+
+// P: p = z on the first iteration, else p = fma(beta, p, z)
+__global__ __launch_bounds__(kBlock) void nmp_p_kernel(const double *__restrict__ sc, int first,
+                                                       const double *__restrict__ z, double *__restrict__ p) {
+  if (nmp_stopped(sc)) return;
+  const double beta = first ? 0.0 : sc[S_BETA];
+  ALFD_FOR_PAIRS(i) {
+    const double2 zv = ld2(z, i);
+    if (first) {
+      st2(p, i, zv);
+    } else {
+      double2 pv = ld2(p, i);
+      pv.x = fma(beta, pv.x, zv.x);
+      pv.y = fma(beta, pv.y, zv.y);
+      st2(p, i, pv);
+    }
+  }
+}
+
+// S: Ap = Mp p, spmv_kernel<L, 0, false> behind the state word (single rank: every column is local).
+// Rows only; the padding of Ap stays as U (first) left it.
+template <int L>
+__global__ __launch_bounds__(kBlock) void nmp_spmv_kernel(const double *__restrict__ sc, int64_t nrows,
+                                                          const int64_t *__restrict__ rp,
+                                                          const int32_t *__restrict__ col,
+                                                          const double *__restrict__ val,
+                                                          const double *__restrict__ p, double *__restrict__ Ap) {
+  if (nmp_stopped(sc)) return;
+  constexpr int RPB = kBlock / L;
+  const int lane = threadIdx.x % L;
+  const int sub = threadIdx.x / L;
+  const int64_t ngroups = (nrows + RPB - 1) / RPB;
+  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+    const int64_t row = g * RPB + sub;
+    if (row < nrows) {   // uniform within the L-lane group
+      const int64_t k0 = rp[row], k1 = rp[row + 1];
+      double acc = 0.0;
+      for (int64_t k = k0 + lane; k < k1; k += L) acc = fma(val[k], p[col[k]], acc);
+      acc = group_reduce<L>(acc);
+      if (lane == 0) Ap[row] = acc;
+    }
+  }
+}
+
+// D: the canonical chunk partials of p.Ap (dot_partial_kernel behind the state word)
+__global__ __launch_bounds__(kBlock) void nmp_dot_kernel(const double *__restrict__ sc, const double *__restrict__ p,
+                                                         const double *__restrict__ Ap, double *__restrict__ part_pap) {
+  __shared__ double lds4[4];
+  if (nmp_stopped(sc)) return;
+  double acc = 0.0;
+  ALFD_FOR_PAIRS(i) {
+    const double2 a = ld2(p, i), b = ld2(Ap, i);
+    acc = fma(a.x, b.x, acc);
+    acc = fma(a.y, b.y, acc);
+  }
+  const double s = block_reduce_256(acc, lds4);
+  if (threadIdx.x == 0) part_pap[blockIdx.x] = s;
 }
 
 }  // namespace alfd

@@ -245,6 +245,7 @@ struct Params {
   double lame_lambda = 2.0, lame_mu = 1.0, lame2_lambda = 18.0, lame2_mu = 9.0;
   double box_lo[3] = {-0.65, -0.3, -0.4}, box_hi[3] = {0.65, 0.3, 0.4};
   int box_cells[3] = {2, 2, 2};
+  int sym_grad = 0;   // 2 eps(u):eps(v) velocity block (alfd_synth_params::sym_grad)
   // row ranges of this process (multi-GPU row partition); -1 = everything.
   // u/p ranges are in NODES (z-slabs of the lexicographic numbering), l in dofs.
   int64_t u_node0 = -1, u_node1 = -1, p_node0 = -1, p_node1 = -1, l0 = -1, l1 = -1;
@@ -493,6 +494,15 @@ void build_A(const Params &P, const Grid &g, Csr &A, int64_t node0, int64_t node
             for (int a = 0; a < nc; ++a)
               for (int b = 0; b < nc; ++b) {
                 double v = (a == b) ? P.beta * lap : 0.0;
+                if (P.sym_grad) {
+                  // 2 eps:eps = grad:grad + T, T_(i,a),(j,b) = int d_b phi_i d_a phi_j: the grad-div entry with a, b swapped
+                  double t = 1.0;
+                  for (int c = 0; c < dim; ++c) {
+                    if (a == b) t *= (c == a) ? k[c] : m[c];
+                    else t *= (c == b) ? gij[c] : (c == a) ? gji[c] : m[c];
+                  }
+                  v += P.beta * t;
+                }
                 if (ggd != 0.0) {
                   double t;
                   if (a == b) {
@@ -1154,6 +1164,8 @@ bool generate(Problem &pb) {
   }
   if (P.elasticity && (P.ncomp != P.dim || P.dim != 3 || P.stokes || P.degree != 1))
     return pb.err = "elasticity needs dim 3, degree 1, ncomp 3, stokes off", false;
+  if (P.sym_grad && (!P.stokes || P.assembly != 0))
+    return pb.err = "sym_grad (2 eps:eps) needs stokes and the Kronecker assembly", false;
 
   Grid g;
   g.dim = P.dim;
@@ -1253,6 +1265,7 @@ void *alfd_synth_generate(const alfd_synth_params *sp, char *err, int errlen) {
   P.want_surface_mass = sp->want_surface_mass;
   P.assembly = sp->assembly;
   P.elasticity = sp->elasticity;
+  P.sym_grad = sp->sym_grad;
   P.lame_lambda = sp->lame_lambda;
   P.lame_mu = sp->lame_mu;
   P.lame2_lambda = sp->lame2_lambda;

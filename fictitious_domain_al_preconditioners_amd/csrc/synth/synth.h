@@ -33,7 +33,11 @@ typedef struct alfd_synth_params {
   int32_t elasticity, pad2_;
   double lame_lambda, lame_mu, lame2_lambda, lame2_mu;
   double box_lo[3], box_hi[3];
-  int32_t box_cells[3], pad3_;
+  int32_t box_cells[3];
+  /* 1: the Stokes velocity block is the reference's 2 eps(u):eps(v) form (stokes...:712-730) instead of
+   * grad u : grad v; Kronecker assembly only.  2 eps:eps = grad:grad + T, block (b,a) of T = block (a,b) of the
+   * gamma_gd = 1 grad-div matrix.  The grad-div term, if on, is added after T. */
+  int32_t sym_grad;
 } alfd_synth_params;
 
 /* NULL on failure (message in err). */

@@ -104,7 +104,13 @@ def config_from_prm(tree: dict) -> tuple[_abi.Config, dict]:
             # stokes...:979-985: invW = M^-1 M^-1 (UMFPACK there, CG on slot M here)
             cfg.w_inverse = _abi.W_MASS_INV_SQUARED
         if not cfg.grad_div_in_A:
-            info["unsupported"].append("Grad-div stabilization = false (nested Bt Mp^-1 B in Aug)")
+            # stokes...:991-995: Aug = A + gamma Ct invW C + gamma_gd Bt Mp_inv B, inner CG with PreconditionIdentity;
+            # AMG for the augmented block without grad-div is ExcNotImplemented there (:1027-1050)
+            if info["amg_for_augmented_block"]:
+                info["unsupported"].append("Grad-div stabilization = false with AMG for augmented block = true "
+                                           "(ExcNotImplemented in the reference)")
+            else:
+                cfg.inner_prec = _abi.PREC_IDENTITY
         if spd:
             # stokes...:1055-1064: the block-diagonal SPD preconditioner is used with SolverMinRes
             cfg.outer_solver = _abi.OUTER_MINRES

@@ -39,7 +39,7 @@ class _Params(C.Structure):
         ("lame_lambda", C.c_double), ("lame_mu", C.c_double),
         ("lame2_lambda", C.c_double), ("lame2_mu", C.c_double),
         ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
-        ("box_cells", C.c_int32 * 3), ("pad3_", C.c_int32),
+        ("box_cells", C.c_int32 * 3), ("sym_grad", C.c_int32),
     ]
 
 
@@ -202,12 +202,15 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
              gamma_grad_div=0.0, beta=1.0, center=(0.5, 0.5, 0.5), radius=0.2, immersed_refine=3,
              coupling_nq=3, body_force=(0.0, 0.0, 0.0), embedded_value=(1.0, 0.0, 0.0),
              row_ranges=None, immersed_box=None, beta2=0.0, surface_mass=False,
-             elasticity=None, immersed_box3d=None, immersed_segments=0, assembly="kronecker") -> SyntheticProblem:
+             elasticity=None, immersed_box3d=None, immersed_segments=0, assembly="kronecker",
+             sym_grad=False) -> SyntheticProblem:
     """immersed_box = (lo, hi, cells): the immersed domain is the 2-D box [lo,hi]^2
     with cells^2 Q1 cells (volume coupling, elliptic_interface); beta2 scales "A2".
     elasticity = (lambda, mu, lambda_jump, mu_jump): vector-Q1 linear elasticity on the background
     (utilities.h:377-427), A2 = the same form with the jump parameters on the immersed box;
     immersed_box3d = (lo[3], hi[3], cells[3]): 3-D box meshed with trilinear cells (volume coupling).
+    sym_grad = True: the Stokes velocity block is the reference's 2 eps(u):eps(v) form (stokes...:712-730,
+    used with `Grad-div stabilization = false`) instead of grad u : grad v; Kronecker assembly only.
     row_ranges = (u_node0, u_node1, p_node0, p_node1, l0, l1): generate only this
     rank's rows (node ranges for the background spaces, dof range for the
     multiplier); column indices stay global.  None = the whole problem."""
@@ -226,6 +229,7 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
     p.u_node0, p.u_node1, p.p_node0, p.p_node1, p.l0, p.l1 = rr
     p.want_surface_mass = int(surface_mass)
     p.assembly = {"kronecker": 0, "cellwise": 1}[assembly]
+    p.sym_grad = int(sym_grad)
     if immersed_box is not None:
         p.immersed_kind, p.imm_lo, p.imm_hi, p.imm_cells = 1, float(immersed_box[0]), float(immersed_box[1]), int(immersed_box[2])
         p.beta2 = beta2
@@ -246,7 +250,8 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
         raise ValueError("synthetic generator: " + err.value.decode())
     params = dict(dim=dim, degree=degree, ncomp=ncomp, n_cells=n_cells, lo=lo, hi=hi, stokes=stokes,
                   grad_div=grad_div, gamma_grad_div=gamma_grad_div, beta=beta, center=tuple(center),
-                  radius=radius, immersed_refine=immersed_refine, coupling_nq=coupling_nq, assembly=assembly)
+                  radius=radius, immersed_refine=immersed_refine, coupling_nq=coupling_nq, assembly=assembly,
+                  sym_grad=bool(sym_grad))
     owner = _NativeHandle(h)
     pb = SyntheticProblem(params=params, _handle=owner,
                           row_ranges=rr if row_ranges is not None else None)

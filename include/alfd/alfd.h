@@ -161,7 +161,13 @@ typedef struct alfd_config {
   int32_t variant;            /* enum alfd_variant */
   int32_t restart;            /* FGMRES max_basis_size: 30 default, 50 elliptic...:863 */
   int32_t orthogonalization;  /* enum alfd_orthogonalization */
-  int32_t grad_div_in_A;      /* 1: A already holds gamma_gd (div,div) (stokes...:991-993) */
+  int32_t grad_div_in_A;      /* 1: A already holds gamma_gd (div,div) (stokes...:991-993).  0 (`Grad-div
+                               * stabilization = false`, ALFD_AL_STOKES / _DIAG): A is the 2 eps:eps form and
+                               * Aug = A + gamma Ct invW C + gamma_gd Bt Mp^-1 B (stokes...:991-995); every exact
+                               * application of Aug (outer system, inner CG) runs a nested lumped-Jacobi CG on Mp to
+                               * mp_inner, the inner preconditioner sees Mp^-1 replaced by ALFD_MP_LUMPED_INV.  Inner
+                               * preconditioner identity (the reference's), Jacobi or Chebyshev; multilevel is refused
+                               * (ALFD_E_UNSUPPORTED), as the reference throws there. */
   double gamma;               /* AL parameter (gamma_1 for elliptic) */
   double gamma_grad_div;      /* stokes...:987 */
   double gamma2;              /* gamma_2, elliptic...:751-752 */
@@ -213,7 +219,8 @@ typedef struct alfd_result {
   double initial_residual;
   double last_residual;       /* SolverControl::last_value() */
   int64_t inner_iterations;   /* total CG iterations on the augmented block(s) */
-  int64_t mp_iterations;      /* total CG iterations on Mp */
+  int64_t mp_iterations;      /* total CG iterations on Mp: the preconditioner's pressure block and, with
+                               * grad_div_in_A = 0, the nested solves inside Aug */
   int32_t inner_failures;     /* inner solves that hit max_steps (ACCEPT policy) */
   int32_t precond_applications;
   double solve_seconds;       /* wall time inside alfd_solve, device-synchronised */
@@ -530,6 +537,10 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  matrix with repeating values but no translate structure gets; at the next alfd_set_matrix);
  *                  "batch_major_wide" (0/1, default 1): blocks with more than 512 distinct values are re-planned with
  *                  10-bit codes / 11-bit window columns instead of being halved (cell-wise assembled matrices).
+ *   "nested_mp_host_stepped" (0/1, default 0): grad_div_in_A = 0, one rank: the nested CG on Mp inside Aug is
+ *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
+ *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
+ *                  "nested_mp_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
  * Returns ALFD_E_INVALID for an unknown name. */
 int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value);
 /* Kernel-class timing of the last solve, accumulated with HIP events when
