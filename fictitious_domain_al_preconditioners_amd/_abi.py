@@ -19,6 +19,8 @@ AL2, AL_STOKES, AL_STOKES_DIAG, AL_ELL_IDEAL, AL_ELL_MODIFIED, RATIONAL = range(
 CTRL_ABS, CTRL_REDUCTION, CTRL_FIXED_ITERS = range(3)
 # enum alfd_inner_prec
 PREC_IDENTITY, PREC_JACOBI, PREC_CHEBYSHEV, PREC_MULTILEVEL = range(4)
+# enum alfd_inner_op (alfd_inner_prec_apply)
+INNER_OP_AUG, INNER_OP_A22, INNER_OP_AUG2 = range(3)
 # enum alfd_orthogonalization
 ORTH_MGS, ORTH_CGS, ORTH_CGS2 = range(3)
 # enum alfd_outer_solver

@@ -5136,6 +5136,9 @@ static int ml_setup(alfd_ctx *ctx) {
   const alfd_config &c = ctx->cfg;
   if (c.ml_smooth_degree < 1 || c.ml_coarse_degree < 1 || !(c.ml_smooth_ratio > 1.0) || !(c.ml_coarse_ratio > 1.0))
     return ctx->err = "bad multilevel parameters", ALFD_E_INVALID;
+  // before the dispatch to the replicated setup: a ratio <= 1 (or NaN) makes delta <= 0 and the patch polynomial NaN
+  if (c.ml_patch_degree < 0) return ctx->err = "negative ml_patch_degree", ALFD_E_INVALID;
+  if (c.ml_patch_degree > 0 && !(c.ml_patch_ratio > 1.0)) return ctx->err = "bad ml_patch_ratio", ALFD_E_INVALID;
   int nlev = 0;
   bool any_P = false;
   while (nlev < ALFD_MAX_LEVELS && (!ctx->ml_agg[nlev].empty() || !ctx->ml_P[nlev].rp.empty())) {
@@ -5147,7 +5150,6 @@ static int ml_setup(alfd_ctx *ctx) {
   if (ctx->nranks > 1 && any_P) return ml_setup_rep_prolongators(ctx, nlev);
   if (ctx->nranks > 1 && (c.ml_patch_degree > 0 || c.ml_coarse_direct > 0))
     return ctx->err = "partitioned context: the interface patch and the direct coarsest solve need CSR prolongators", ALFD_E_UNSUPPORTED;
-  if (c.ml_patch_degree > 0 && !(c.ml_patch_ratio > 1.0)) return ctx->err = "bad ml_patch_ratio", ALFD_E_INVALID;
   const int rk = ctx->rank, last = ctx->nblocks - 1;
   // rank offsets of every level's unknowns: level 0 = block 0, level l+1 = ml_coff[l]
   std::vector<std::vector<int64_t>> off(nlev + 1);
@@ -6406,6 +6408,55 @@ int alfd_spmv(alfd_ctx_t ctx, int slot, const double *x, double *y, int mode, do
   hipFree(dx);
   hipFree(dy);
   return rc;
+}
+
+int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!r || !z) return ALFD_E_INVALID;
+  const int v = ctx->cfg.variant;
+  int kind = -1;
+  if (op == ALFD_INNER_OP_AUG &&
+      (v == ALFD_AL2 || v == ALFD_AL_STOKES || v == ALFD_AL_STOKES_DIAG || v == ALFD_AL_ELL_MODIFIED))
+    kind = OP_AUG;
+  else if (op == ALFD_INNER_OP_A22 && v == ALFD_AL_ELL_MODIFIED)
+    kind = OP_A22;
+  else if (op == ALFD_INNER_OP_AUG2 && v == ALFD_AL_ELL_IDEAL)
+    kind = OP_AUG2;
+  if (kind < 0)
+    return ctx->err = "alfd_inner_prec_apply: the configured variant has no such inner operator", ALFD_E_INVALID;
+  // the blocks the operator spans, at their places in the staging vectors of the depth-1 calls
+  const int b0 = kind == OP_A22 ? 1 : 0, b1 = kind == OP_AUG2 ? 1 : b0;
+  const int64_t npad = op_npad(ctx, kind);
+  double *dr = ctx->st_in + ctx->off[b0], *dz = ctx->st_out + ctx->off[b0];
+  HIPC(hipMemsetAsync(ctx->st_in, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  HIPC(hipMemsetAsync(ctx->st_out, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  int64_t at = 0;
+  for (int b = b0; b <= b1; ++b) {
+    HIPC(hipMemcpyAsync(ctx->st_in + ctx->off[b], r + at, ctx->n[b] * sizeof(double), hipMemcpyHostToDevice,
+                        ctx->stream));
+    at += ctx->n[b];
+  }
+  // the dispatch of pcg(): what the inner CG of this operator calls once per iteration
+  const int prec = ctx->cfg.inner_prec;
+  if (prec == ALFD_PREC_IDENTITY) {
+    HIPC(hipMemcpyAsync(dz, dr, npad * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  } else if (prec == ALFD_PREC_JACOBI) {
+    VEC_LAUNCH(jacobi_dot_kernel, npad, 24, op_dinv(ctx, kind), dr, dz, ctx->partial);
+    HIPC(hipGetLastError());
+  } else if (prec == ALFD_PREC_MULTILEVEL && kind == OP_AUG) {
+    RC(ml_apply(ctx, dr, dz));
+  } else {
+    RC(cheb_apply(ctx, kind, dr, dz, npad));
+  }
+  at = 0;
+  for (int b = b0; b <= b1; ++b) {
+    HIPC(hipMemcpyAsync(z + at, ctx->st_out + ctx->off[b], ctx->n[b] * sizeof(double), hipMemcpyDeviceToHost,
+                        ctx->stream));
+    at += ctx->n[b];
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
 }
 
 int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double *result) {

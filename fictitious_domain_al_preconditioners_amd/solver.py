@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "alfd_host_row_blocks_from_points", "alfd_host_stream_plan_short", "alfd_set_prolongator", "alfd_set_controls", "alfd_get_timing_streamed", "alfd_get_setup_seconds",
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
+    "alfd_inner_prec_apply",
 ]
 
 
@@ -86,6 +87,7 @@ def load_library():
         "alfd_get_history": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
         "alfd_spmv": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, dbl]),
         "alfd_dot": (C.c_int, [vp, i64, vp, vp, C.POINTER(dbl)]),
+        "alfd_inner_prec_apply": (C.c_int, [vp, C.c_int, vp, vp]),
         "alfd_matrix_lanes": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
         "alfd_bench_spmv": (C.c_int, [vp, C.c_int, i32, C.POINTER(dbl), C.POINTER(dbl)]),
         "alfd_enable_timing": (C.c_int, [vp, C.c_int]),
@@ -359,6 +361,22 @@ class Context:
         out = C.c_double()
         self._ck(self._lib.alfd_dot(self._h, x.size, x.ctypes.data, y.ctypes.data, C.byref(out)))
         return out.value
+
+    def inner_prec_apply(self, r, op=_abi.INNER_OP_AUG):
+        """z = M^-1 r: one application of the inner CG's preconditioner alone (alfd_inner_prec_apply).  op: the
+        augmented (1,1) block (r as long as block 0), A22 of the modified elliptic variant (block 1), or the
+        2-block operator of the ideal elliptic variant (blocks 0 and 1, one after the other)."""
+        r = np.ascontiguousarray(r, np.float64)
+        bs = self.block_sizes
+        if bs is None:                      # not set up: the library answers ALFD_E_NOT_SETUP
+            n = r.size
+        else:
+            n = {_abi.INNER_OP_AUG: bs[0], _abi.INNER_OP_A22: bs[1]}.get(op, bs[0] + bs[1])
+            if r.size != n:
+                raise ValueError(f"r has {r.size} entries, the inner operator {n}")
+        z = np.zeros(n)
+        self._ck(self._lib.alfd_inner_prec_apply(self._h, int(op), r.ctypes.data, z.ctypes.data))
+        return z
 
     def bench_spmv(self, slot, reps=20):
         ms, nbytes = C.c_double(), C.c_double()
@@ -636,7 +654,7 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
                 if len(entry) > 2 and entry[2] is not None:   # partitioned context: coarse offsets by rank (partition.local_prolongators)
                     ctx.set_aggregate_partition(level, entry[2])
                 continue
-            ctx.set_aggregates(level, agg, nc)
+            ctx.set_aggregates(level, agg, nc, entry[3] if len(entry) > 3 else None)   # 4th entry: prolongation weights
             if len(entry) > 2 and entry[2] is not None:      # (agg_local, n_coarse_global, coarse_offsets)
                 ctx.set_aggregate_partition(level, entry[2])
 

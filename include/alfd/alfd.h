@@ -207,7 +207,9 @@ typedef struct alfd_config {
    * in D^-1 Aug_SS over [lambda_max / ml_patch_ratio, lambda_max].  The penalty gamma Ct W^-1 C is what a
    * multigrid cycle on the background mesh cannot resolve; it lives on S only (a few 10^4 rows at 10^7 DoF).
    * ml_coarse_direct > 0: when the coarsest level has at most that many unknowns its operator is inverted
-   * explicitly (dense Cholesky at setup, one dense product per cycle) instead of the Chebyshev sweep. */
+   * explicitly (dense Cholesky at setup, one dense product per cycle) instead of the Chebyshev sweep; <= 0: off.
+   * alfd_setup answers ALFD_E_INVALID for ml_patch_degree < 0 and, with a patch, for an ml_patch_ratio that is not
+   * > 1 (the interval [lambda_max / ratio, lambda_max] would be empty), on one rank and on a partitioned context. */
   int32_t ml_patch_degree;
   int32_t ml_coarse_direct;
   double ml_patch_ratio;
@@ -421,6 +423,20 @@ int alfd_get_history(alfd_ctx_t ctx, double *out, int32_t capacity, int32_t *cou
  * alfd_spmv is collective: x holds this rank's owned columns of the slot's column block, y its rows. */
 int alfd_spmv(alfd_ctx_t ctx, int slot, const double *x, double *y, int mode, double alpha);
 int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double *result);
+/* z = M^-1 r: ONE application of the preconditioner of the inner CG, with no CG around it -- exactly the operator
+ * the configured variant's inner solve calls once per iteration (alfd_config::inner_prec: identity, Jacobi, the
+ * Chebyshev sweep, the multilevel cycle incl. patch and coarsest inverse), after alfd_setup.  Unlike
+ * alfd_precond_apply with one fixed CG step, which returns alpha(r) M^-1 r, this keeps the scale, so linearity,
+ * symmetry and the operator itself can be compared with an independent reference.  `op` selects the inner operator:
+ *   ALFD_INNER_OP_AUG   the augmented (1,1) block: AL2, AL_STOKES, AL_STOKES_DIAG, AL_ELL_MODIFIED (the only one
+ *                       ALFD_PREC_MULTILEVEL applies to); r, z have the length of block 0
+ *   ALFD_INNER_OP_A22   the second block A22_aug of AL_ELL_MODIFIED; r, z have the length of block 1
+ *   ALFD_INNER_OP_AUG2  the coupled 2-block operator of AL_ELL_IDEAL; r, z hold block 0 followed by block 1
+ * An op the configured variant does not solve with: ALFD_E_INVALID; before alfd_setup: ALFD_E_NOT_SETUP.  Stages
+ * through the buffers of the depth-1 calls (a resident right-hand side stays intact).  On a partitioned context the
+ * call is collective like alfd_spmv: r, z hold this rank's rows. */
+enum alfd_inner_op { ALFD_INNER_OP_AUG = 0, ALFD_INNER_OP_A22 = 1, ALFD_INNER_OP_AUG2 = 2 };
+int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z);
 /* Lanes per row the canonical SpMV order uses for this slot (after setup). */
 int alfd_matrix_lanes(alfd_ctx_t ctx, int slot, int32_t *lanes);
 /* Benchmark hook: run `reps` back-to-back y = A x launches of `slot` on resident

@@ -1812,6 +1812,52 @@ int orc_h_system_apply(void *h, const double *const *src, double *const *dst) {
   return rc;
 }
 
+// z = M^-1 r: one application of the inner CG's preconditioner on a persistent handle (alfd_inner_prec_apply):
+// the dispatch of inner_solve() without the CG.  op: enum alfd_inner_op; r, z as in alfd.h.
+int orc_h_inner_prec_apply(void *h, int op, const double *r, double *z) {
+  orc::Problem &P = *static_cast<orc::Problem *>(h);
+  if (!r || !z) return ALFD_E_INVALID;
+  const int v = P.cfg.variant;
+  int kind = -1;
+  if (op == ALFD_INNER_OP_AUG &&
+      (v == ALFD_AL2 || v == ALFD_AL_STOKES || v == ALFD_AL_STOKES_DIAG || v == ALFD_AL_ELL_MODIFIED))
+    kind = orc::OP_AUG;
+  else if (op == ALFD_INNER_OP_A22 && v == ALFD_AL_ELL_MODIFIED)
+    kind = orc::OP_A22;
+  else if (op == ALFD_INNER_OP_AUG2 && v == ALFD_AL_ELL_IDEAL)
+    kind = orc::OP_AUG2;
+  if (kind < 0) return ALFD_E_INVALID;
+  orc::InnerOp op2{P, kind, {}};
+  const int64_t n = op2.n();
+  std::vector<double> rr(n, 0.0), zz(n, 0.0);
+  if (kind == orc::OP_AUG2) {          // [r_0 ; r_1] -> [block 0 | pad | block 1]
+    std::memcpy(rr.data(), r, P.n[0] * sizeof(double));
+    std::memcpy(rr.data() + P.off[1], r + P.n[0], P.n[1] * sizeof(double));
+  } else {
+    std::memcpy(rr.data(), r, n * sizeof(double));
+  }
+  if (P.cfg.inner_prec == ALFD_PREC_IDENTITY) {
+    orc::IdentityPrec pr;
+    pr(rr.data(), zz.data(), n);
+  } else if (P.cfg.inner_prec == ALFD_PREC_JACOBI) {
+    orc::DiagPrec pr{orc::op_dinv(P, kind)};
+    pr(rr.data(), zz.data(), n);
+  } else if (P.cfg.inner_prec == ALFD_PREC_MULTILEVEL && kind == orc::OP_AUG) {
+    orc::MlPrec pr{P};
+    pr(rr.data(), zz.data(), n);
+  } else {
+    orc::ChebPrec pr{P, op2, orc::op_dinv(P, kind), P.lam_max[kind], P.lam_max[kind] / P.cfg.cheb_eig_ratio, {}, {}, {}};
+    pr(rr.data(), zz.data(), n);
+  }
+  if (kind == orc::OP_AUG2) {
+    std::memcpy(z, zz.data(), P.n[0] * sizeof(double));
+    std::memcpy(z + P.n[0], zz.data() + P.off[1], P.n[1] * sizeof(double));
+  } else {
+    std::memcpy(z, zz.data(), n * sizeof(double));
+  }
+  return ALFD_OK;
+}
+
 int orc_precond_apply(const orc_problem *op, const alfd_config *cfg, const double *const *src,
                       double *const *dst, alfd_result *res) {
   orc::Problem P;

@@ -67,6 +67,8 @@ def lib():
         l.orc_h_solve.argtypes = [C.c_void_p, PP, PP, C.POINTER(_abi.Result), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.orc_h_system_apply.restype = C.c_int
         l.orc_h_system_apply.argtypes = [C.c_void_p, PP, PP]
+        l.orc_h_inner_prec_apply.restype = C.c_int
+        l.orc_h_inner_prec_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         l.orc_set_threads.restype = C.c_int
         l.orc_set_threads.argtypes = [C.c_int]
         l.orc_set_row_order.restype = C.c_int
@@ -150,6 +152,11 @@ class OracleSystem:
                 self._keep += (agg,)
                 p.ml_agg[l] = agg.ctypes.data
                 p.ml_ncoarse[l] = nc
+                if len(entry) > 3 and entry[3] is not None:      # prolongation weights P_{i,agg[i]}
+                    wgt = np.ascontiguousarray(entry[3], np.float64)
+                    assert wgt.size == agg.size
+                    self._keep += (wgt,)
+                    p.ml_weight[l] = wgt.ctypes.data
                 if len(entry) > 2 and entry[2] is not None and nranks_emulated > 1:
                     off = np.ascontiguousarray(entry[2], np.int64)
                     self._keep += (off,)
@@ -199,6 +206,17 @@ class OracleSystem:
         dst = [np.zeros(n) for n in self.block_sizes]
         rc = lib().orc_h_system_apply(h, _blocks(src), _blocks(dst))
         return rc, dst
+
+    def handle_inner_prec_apply(self, h, r, op=_abi.INNER_OP_AUG):
+        """(rc, z = M^-1 r): the inner CG's preconditioner alone (orc_h_inner_prec_apply); r as for
+        Context.inner_prec_apply."""
+        r = np.ascontiguousarray(r, np.float64)
+        bs = self.block_sizes
+        n = {_abi.INNER_OP_AUG: bs[0], _abi.INNER_OP_A22: bs[1]}.get(op, bs[0] + bs[1])
+        assert r.size == n
+        z = np.zeros(n)
+        rc = lib().orc_h_inner_prec_apply(h, int(op), r.ctypes.data, z.ctypes.data)
+        return rc, z
 
     @staticmethod
     def close_handle(h):

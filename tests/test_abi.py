@@ -55,6 +55,14 @@ def test_argument_validation_without_gpu():
     assert lib.alfd_setup(None) == _abi.E_INVALID
     assert lib.alfd_comm_unique_id(None, 0) == _abi.E_INVALID
     assert lib.alfd_last_error(None) == b"null context"
+    # the inner-preconditioner primitive: null context here; ALFD_E_NOT_SETUP before alfd_setup and ALFD_E_INVALID for
+    # an operator the variant does not have need a context, i.e. a GPU (tests/test_gpu_inner_preconditioner.py)
+    import numpy as np
+    z = np.zeros(4)
+    assert lib.alfd_inner_prec_apply(None, _abi.INNER_OP_AUG, z.ctypes.data, z.ctypes.data) == _abi.E_INVALID
+    assert (_abi.INNER_OP_AUG, _abi.INNER_OP_A22, _abi.INNER_OP_AUG2) == (0, 1, 2)
+    hdr = open(os.path.join(ROOT, "include", "alfd", "alfd.h")).read()
+    assert "ALFD_INNER_OP_AUG = 0, ALFD_INNER_OP_A22 = 1, ALFD_INNER_OP_AUG2 = 2" in hdr
 
 
 def test_no_cpu_fallback():

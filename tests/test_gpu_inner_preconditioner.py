@@ -1,0 +1,330 @@
+"""The inner preconditioner M^-1 of the LIBRARY (alfd_inner_prec_apply: z = M^-1 r, no CG around it) against the oracle
+AND against tests/precond_reference.py, the independent restatement from the definitions -- so that a mistake shared by
+library and oracle is still caught here.  Configurations, inputs and measures come from tests/test_inner_preconditioner.py.
+
+  a. vectors against the restatement              b. the whole operator, every column (small sizes)
+  c. symmetry of the dense operator               d. definiteness: eig((M + M^T)/2) > 0, eig(L^T M L) > 0, Aug_0 = L L^T
+  e. the eigenvalue estimates bound the true lambda_max; level 0 equals alfd_result.lambda_max
+  f. library against oracle, bit for bit          g. statelessness and linearity on the device
+  h. mid size (N = 20, the production kernels)    i. two ranks against one"""
+import threading
+import time
+
+import numpy as np
+import pytest
+
+import cases
+import precond_reference as pr
+import test_inner_preconditioner as base
+from fictitious_domain_al_preconditioners_amd import _abi, partition, problems, solver
+
+pytestmark = pytest.mark.gpu
+
+HIST_RTOL = 1e-10          # tolerance north_star states for residuals (tests/test_gpu_parity.py)
+
+
+def _context(cf):
+    cfg = _abi.Config.from_buffer_copy(cf.cfg)      # set_controls below must not reach the shared configuration
+    return solver.context_from_problem(cf.pb, cfg, aggregates=cf.levels)
+
+
+def _lambda_max(ctx, pb):
+    ctx.set_controls(inner=_abi.Control(_abi.CTRL_FIXED_ITERS, 1, 0.0, 0.0))
+    return ctx.precond_apply(cases.rng_blocks(pb, 3))[1].lambda_max
+
+
+def _vectors(cf, ctx, ref, osys, h):
+    """(a) against the restatement and (f) against the oracle.  (f) is bit-equality: DESIGN.md section 4 claims canonical
+    arithmetic for every step of every configuration here (SpMV rows, dots, the Chebyshev updates, both Galerkin orders,
+    the patch extractions, the explicit coarsest inverse)."""
+    for what, r in base.inputs(cf).items():
+        z = ctx.inner_prec_apply(r, cf.op)
+        err = base.rel(z, ref.apply(r))
+        rc, zo = osys.handle_inner_prec_apply(h, r, cf.op)
+        assert rc == 0
+        same = np.array_equal(z, zo)
+        print(f"(a) library {cf.name}, {what}: {err:.2e}; (f) bit-equal to the oracle: {same}"
+              + ("" if same else f" (max rel {base.rel(z, zo):.2e})"))
+        assert err <= pr.TOL, (cf.name, what, err)
+        assert same, (cf.name, what, base.rel(z, zo))
+
+
+@pytest.mark.parametrize("name", base.SMALL + base.CASES)
+def test_vectors_against_restatement_and_oracle(built, name):
+    cf = base.config(name)
+    ref = cf.reference()
+    ctx = _context(cf)
+    osys, h = cf.oracle()
+    try:
+        _vectors(cf, ctx, ref, osys, h)
+        if cf.op != _abi.INNER_OP_A22 and cf.cfg.inner_prec in (_abi.PREC_CHEBYSHEV, _abi.PREC_MULTILEVEL):
+            lam, got = float(ref.levels[0].lam), _lambda_max(ctx, cf.pb)
+            one = _abi.Control(_abi.CTRL_FIXED_ITERS, 1, 0.0, 0.0)
+            ores = osys.handle_precond_apply(h, cases.rng_blocks(cf.pb, 3), inner=one)[2]
+            print(f"(e) {name}: lambda_0 restatement {lam!r}, library {got!r}, oracle {ores.lambda_max!r}")
+            assert abs(got - lam) <= pr.TOL * lam and got == ores.lambda_max
+    finally:
+        osys.close_handle(h)
+        ctx.close()
+
+
+@pytest.mark.parametrize("name", base.SMALL)
+def test_operator_symmetry_definiteness_and_estimates(built, name):
+    """(b), (c), (d) from every column of the library's operator; (e) on every level and the patch."""
+    cf = base.config(name)
+    ref = cf.reference()
+    ctx = _context(cf)
+    try:
+        t0 = time.time()
+        m = base.dense_operator(lambda e: ctx.inner_prec_apply(e, cf.op), ref.n)
+        print(f"{name}: {ref.n} columns in {time.time() - t0:.1f} s")
+    finally:
+        ctx.close()
+    base.check_operator("library", name, m, ref)
+    base.check_estimates(name, ref)
+
+
+@pytest.mark.parametrize("kind", ["aggregates", "smoothed"])
+def test_library_built_hierarchies(built, kind):
+    """alfd_build_aggregates / alfd_build_smoothed_aggregation on the hanging-node operator: what alfd_get_aggregates /
+    alfd_get_prolongator read back feeds the restatement (and the oracle); all of (a) to (f)."""
+    pb = cases.hanging_node_variant(problems.stokes3d_sphere(4, 1))
+    cfg = _abi.default_config(_abi.AL_STOKES)
+    cfg.inner_prec = _abi.PREC_MULTILEVEL
+    cfg.ml_smooth_degree, cfg.ml_smooth_ratio, cfg.ml_coarse_degree = 4, 256.0, 10
+    ctx = solver.Context(0)
+    try:
+        ctx.set_matrix(_abi.A, pb.mats["A"])
+        ctx.set_matrix(_abi.C_, pb.mats["C"])
+        ctx.set_matrix(_abi.CT, pb.mats["Ct"])
+        ctx.set_diag(_abi.INVW, pb.inv_w_diag_squared())
+        ctx.configure(_abi.Config.from_buffer_copy(cfg))
+        kw = dict(block_size=3, threshold=0.02, max_aggregate_nodes=8, min_coarse=50)
+        levels = ctx.build_smoothed_aggregation(damping=4.0 / 3.0, **kw) if kind == "smoothed" else ctx.build_aggregates(**kw)
+        assert len(levels) >= 2, [nc for _, nc in levels]
+        solver.upload_problem(ctx, pb, _abi.Config.from_buffer_copy(cfg), None)      # keeps the hierarchy built above
+        cf = base.Config(f"hanging_node_{kind}", pb, cfg, levels)
+        ref = cf.reference()
+        print(f"{cf.name}: levels {[L.n for L in ref.levels]}")
+        osys, h = cf.oracle()
+        try:
+            _vectors(cf, ctx, ref, osys, h)
+        finally:
+            osys.close_handle(h)
+        m = base.dense_operator(lambda e: ctx.inner_prec_apply(e), ref.n)
+    finally:
+        ctx.close()
+    base.check_operator("library", cf.name, m, ref)
+    base.check_estimates(cf.name, ref)
+
+
+def test_stateless_and_linear(built):
+    """(g): same bits twice; same bits after a solve, a preconditioner application and an SpMV on a shorter slot;
+    M^-1 (a u + b v) = a M^-1 u + b M^-1 v within tol."""
+    cf = base.config("ml_gmg_patch")
+    ref = cf.reference()
+    ctx = _context(cf)
+    try:
+        rng = np.random.default_rng(21)
+        u, v = rng.uniform(-1, 1, ref.n), rng.uniform(-1, 1, ref.n)
+        z1 = ctx.inner_prec_apply(u)
+        assert np.array_equal(ctx.inner_prec_apply(u), z1)
+        rhs = ctx.augment_rhs(cases.rhs_of(cf.pb))
+        x, res = ctx.solve(rhs)
+        assert res.status == 0
+        ctx.precond_apply(cases.rng_blocks(cf.pb, 4))
+        mp = cf.pb.mats["Mp"]
+        ctx.spmv(_abi.MP, rng.uniform(-1, 1, mp.ncols), np.zeros(mp.nrows))
+        assert np.array_equal(ctx.inner_prec_apply(u), z1)
+        a, b = 0.7, -1.3
+        lin = a * z1 + b * ctx.inner_prec_apply(v)
+        err = base.rel(ctx.inner_prec_apply(a * u + b * v), lin)
+        print(f"(g) linearity: {err:.2e}")
+        assert err <= pr.TOL
+    finally:
+        ctx.close()
+
+
+def test_reuploaded_context_equals_a_fresh_one(built):
+    """(g): one context set up for N = 8, applied, then uploaded with N = 6 and applied: the bits of a fresh context
+    (stale padding, stale Chebyshev, patch and level buffers of the longer problem)."""
+    big, _ = cases.case("stokes3d_gmg_patch")
+    cfg = base.config("ml_gmg_patch").cfg
+    small = problems.stokes3d_sphere(6, 1)
+    lv_big = problems.tensor_prolongators(big.params, min_coarse=50)
+    lv_small = problems.tensor_prolongators(small.params, min_coarse=50)
+    r = np.random.default_rng(31).uniform(-1, 1, small.block_sizes[0])
+    ctx = solver.context_from_problem(big, _abi.Config.from_buffer_copy(cfg), aggregates=lv_big)
+    try:
+        ctx.inner_prec_apply(np.random.default_rng(30).uniform(-1, 1, big.block_sizes[0]))
+        x, res = ctx.solve(ctx.augment_rhs(cases.rhs_of(big)))
+        solver.upload_problem(ctx, small, _abi.Config.from_buffer_copy(cfg), lv_small)
+        z = ctx.inner_prec_apply(r)
+    finally:
+        ctx.close()
+    fresh = solver.context_from_problem(small, _abi.Config.from_buffer_copy(cfg), aggregates=lv_small)
+    try:
+        z_fresh = fresh.inner_prec_apply(r)
+    finally:
+        fresh.close()
+    assert np.array_equal(z, z_fresh), base.rel(z, z_fresh)
+    cf = base.Config("ml_gmg_patch at N = 6", small, cfg, lv_small)
+    err = base.rel(z, cf.reference().apply(r))
+    print(f"(a) {cf.name}: {err:.2e}")
+    assert err <= pr.TOL
+
+
+def test_mid_size_symmetry_and_restatement(built):
+    """(h): N = 20 Taylor-Hood on 16x4x1 bricks with the benchmark's multigrid settings -- where the batch-major
+    kernels run.  <M^-1 u, v> = <u, M^-1 v> relative to |M^-1 u| |v| within the tolerance of (c) for these settings (64
+    times the asymmetry of the float64 restatement's dense operator at the small size), <M^-1 u, u> > 0, for three random
+    pairs; two of the vectors against the sparse restatement as in (a).  The restatement's own pair defects are printed
+    but make no tolerance: a single pair can cancel to 1e-18 by chance."""
+    pb = problems.stokes3d_sphere(20, 2)
+    cfg = _abi.bench_multilevel_settings(_abi.default_config(_abi.AL_STOKES), geometric=True)
+    levels = problems.tensor_prolongators(pb.params, min_coarse=_abi.BENCH_MIN_COARSE)
+    cf = base.Config("bench settings at N = 20", pb, cfg, levels)
+    t0 = time.time()
+    ref = cf.reference()
+    print(f"(h) restatement set up in {time.time() - t0:.1f} s, levels {[L.n for L in ref.levels]}, "
+          f"patch {ref.patch.n if ref.patch else 0}")
+    ctx = solver.context_from_problem(pb, _abi.Config.from_buffer_copy(cfg), aggregates=levels,
+                                      row_blocks=problems.brick_row_blocks(pb.params, (16, 4, 1)))
+    try:
+        assert ctx.matrix_info(_abi.A)["batch_major"] == 2
+        rng = np.random.default_rng(41)
+        defects, ref_defects = [], []
+        for pair in range(3):
+            u, v = rng.uniform(-1, 1, ref.n), rng.uniform(-1, 1, ref.n)
+            zu, zv = ctx.inner_prec_apply(u), ctx.inner_prec_apply(v)
+            ru, rv = ref.apply(u), ref.apply(v)
+            defects.append(abs(np.dot(zu, v) - np.dot(u, zv)) / (np.linalg.norm(zu) * np.linalg.norm(v)))
+            ref_defects.append(abs(np.dot(ru, v) - np.dot(u, rv)) / (np.linalg.norm(ru) * np.linalg.norm(v)))
+            assert np.dot(zu, u) > 0 and np.dot(zv, v) > 0
+            if pair == 0:
+                for what, z, zr in (("u", zu, ru), ("v", zv, rv)):
+                    err = base.rel(z, zr)
+                    print(f"(h) library against the restatement, {what}: {err:.2e}")
+                    assert err <= pr.TOL
+        print(f"(h) symmetry defects library {defects}, restatement {ref_defects}, total {time.time() - t0:.1f} s")
+        sym_tol = 64 * base.asymmetry(base.config("ml_gmg_patch_bench").reference().dense())
+        print(f"(h) tolerance of (c) for these settings: {sym_tol:.2e}")
+        assert max(defects) <= sym_tol
+    finally:
+        ctx.close()
+
+
+def _two_ranks(work):
+    group = solver.LocalGroup(2)
+    out, errs = [None, None], []
+
+    def run(rank):
+        try:
+            out[rank] = work(group, rank)
+        except Exception as e:   # noqa: BLE001
+            errs.append((rank, e))
+
+    th = [threading.Thread(target=run, args=(r,)) for r in range(2)]
+    for t in th:
+        t.start()
+    for t in th:
+        t.join(timeout=600)
+    group.close()
+    return out, errs
+
+
+def _rank_context(group, rank, plan, glevels, full, cfg, n, ref):
+    pb = problems.stokes3d_sphere(n, ref, row_ranges=plan.generator_ranges(rank))
+    ctx = solver.Context(0)
+    ctx.comm_init_local(group.handle, rank)
+    ctx.set_partition(plan.offsets)
+    solver.upload_problem(ctx, pb, _abi.Config.from_buffer_copy(cfg),
+                          partition.local_prolongators(glevels, full.params, plan, rank))
+    return ctx
+
+
+def test_two_ranks_match_one(built):
+    """(i): the collective call on two in-process ranks (levels >= 1 and the patch replicated: ml_cycle_rep,
+    patch_setup_rep) gathers to the single-rank result within HIST_RTOL -- not bit-equal, the level-0 reductions of the
+    power iterations are summed in rank order."""
+    n, refine = 8, 1
+    full, cfg = cases.case("stokes3d_gmg_patch")
+    glevels = cases.aggregates_of(full, cfg)
+    plan = partition.slab_partition_stokes3d(n, refine, 2)
+    r = np.random.default_rng(51).uniform(-1, 1, full.block_sizes[0])
+    offs = plan.offsets[0]
+
+    def work(group, rank):
+        ctx = _rank_context(group, rank, plan, glevels, full, cfg, n, refine)
+        try:
+            return ctx.inner_prec_apply(r[int(offs[rank]):int(offs[rank + 1])])
+        finally:
+            ctx.close()
+
+    out, errs = _two_ranks(work)
+    assert not errs, errs
+    ctx = solver.context_from_problem(full, _abi.Config.from_buffer_copy(cfg), aggregates=glevels)
+    try:
+        one = ctx.inner_prec_apply(r)
+    finally:
+        ctx.close()
+    err = base.rel(np.concatenate(out), one)
+    print(f"(i) two ranks against one: {err:.2e}")
+    assert err <= HIST_RTOL
+
+
+@pytest.mark.parametrize("ratio", [1.0, float("nan")])
+def test_partitioned_setup_rejects_bad_patch_ratio(built, ratio):
+    """A patch interval [lambda / ratio, lambda] with ratio <= 1 (or NaN) has delta <= 0: the replicated setup of a
+    partitioned context must refuse it like the single-rank one, not hand CG a NaN polynomial."""
+    n, refine = 8, 1
+    full, cfg = cases.case("stokes3d_gmg_patch")
+    cfg = _abi.Config.from_buffer_copy(cfg)
+    cfg.ml_patch_ratio = ratio
+    glevels = cases.aggregates_of(full, cfg)
+    plan = partition.slab_partition_stokes3d(n, refine, 2)
+
+    def work(group, rank):
+        try:
+            _rank_context(group, rank, plan, glevels, full, cfg, n, refine).close()
+        except solver.AlfdError as e:
+            return e.status
+        return _abi.OK
+
+    out, errs = _two_ranks(work)
+    assert not errs, errs
+    assert out == [_abi.E_INVALID, _abi.E_INVALID]
+    cfg.ml_patch_ratio, cfg.ml_patch_degree = 30.0, -1
+    with pytest.raises(solver.AlfdError) as e:
+        solver.context_from_problem(full, cfg, aggregates=glevels)
+    assert e.value.status == _abi.E_INVALID
+
+
+def test_wrong_state_and_wrong_operator(built):
+    cf = base.config("cheb1_al2")
+    ctx = solver.Context(0)
+    try:
+        z = np.zeros(cf.pb.block_sizes[0])
+        lib, h = ctx._lib, ctx._h
+        assert lib.alfd_inner_prec_apply(h, _abi.INNER_OP_AUG, z.ctypes.data, z.ctypes.data) == _abi.E_NOT_SETUP
+        solver.upload_problem(ctx, cf.pb, _abi.Config.from_buffer_copy(cf.cfg))
+        assert lib.alfd_inner_prec_apply(h, _abi.INNER_OP_AUG, None, z.ctypes.data) == _abi.E_INVALID
+        for op in (_abi.INNER_OP_A22, _abi.INNER_OP_AUG2, 7, -1):
+            assert lib.alfd_inner_prec_apply(h, op, z.ctypes.data, z.ctypes.data) == _abi.E_INVALID
+        # a resident right-hand side stays intact
+        rhs = ctx.augment_rhs(cases.rhs_of(cf.pb))
+        ctx.upload_rhs(rhs)
+        first, h1 = ctx.solve_resident(), ctx.history()
+        ctx.inner_prec_apply(np.ones(z.size))
+        again, h2 = ctx.solve_resident(), ctx.history()
+        assert np.array_equal(h1, h2) and first.outer_iterations == again.outer_iterations
+    finally:
+        ctx.close()
+    el = base.config("ell_ideal_aug2")
+    ctx = _context(el)
+    try:
+        n = el.pb.block_sizes[0]
+        z = np.zeros(n)
+        assert ctx._lib.alfd_inner_prec_apply(ctx._h, _abi.INNER_OP_AUG, z.ctypes.data, z.ctypes.data) == _abi.E_INVALID
+    finally:
+        ctx.close()

@@ -346,7 +346,9 @@ def test_minres_with_diagonal_spd_al_preconditioner():
 def test_multilevel_hierarchy_and_preconditioner_quality():
     """ALFD_PREC_MULTILEVEL: aggregates are a partition of the interior dofs, the V-cycle
     is a symmetric positive definite operator (needed by CG), it beats the single-level
-    Chebyshev sweep in inner iterations, and the outer solve is unaffected."""
+    Chebyshev sweep in inner iterations, and the outer solve is unaffected.
+    (Symmetry and definiteness of the whole operator, every column, for every hierarchy kind:
+    tests/test_inner_preconditioner.py checks (c), (d); here only two positive Rayleigh quotients.)"""
     pb, cfg = cases.case("stokes3d_multilevel")
     aggs = cases.aggregates_of(pb, cfg)
     n0 = pb.block_sizes[0]
