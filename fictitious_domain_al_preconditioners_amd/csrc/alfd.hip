@@ -157,6 +157,7 @@ struct MlLevel {
   double *dinv = nullptr;
   double lmax = 0;
   double *r = nullptr, *z = nullptr, *t = nullptr, *cd = nullptr, *cres = nullptr, *ctmp = nullptr;
+  uint8_t *tail_mask = nullptr;   // npad bytes, 1 = row listed in Ct (aug_tail_kernel); null: this level runs unfused
   // multi-rank: levels from alfd_ctx::ml_rep_level on are REPLICATED on every rank (global operators and
   // vectors, no halo exchanges); gP / gR connect two replicated levels, P / R above stay rank-local
   DevCsr gA, gC, gCt, gP, gR;
@@ -264,6 +265,7 @@ struct alfd_ctx {
     double *dinv = nullptr, *rS = nullptr, *zS = nullptr, *uS = nullptr, *eS = nullptr, *cd = nullptr,
            *cres = nullptr, *ctmp = nullptr, *rr = nullptr;
     double lmax = 0;
+    uint8_t *tail_mask = nullptr;              // rows of Cts (aug_tail_kernel), as MlLevel::tail_mask
     // partitioned context: the patch is REPLICATED (Ass, Cs, Cts whole on every rank); S[] = this rank's rows
     // (m_loc of them, patch ids soff[rank] ..), Cts_loc / Ctg = Ct[S_loc, :] / Ct[owned rows, :] over GLOBAL
     // multiplier ids, As / Ats = this rank's rows of A[S, :] (halo on the fine vector) / A[:, S]
@@ -277,6 +279,7 @@ struct alfd_ctx {
   int ml_rep_level = -1;                      // first replicated level (multi-rank), -1: none
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
+  int ml_fuse = 1;                            // fused smoother steps: aug_tail_kernel ("ml_fuse", ALFD_ML_FUSE)
   int ml_gpu_galerkin = 1;                    // Galerkin products of CSR-prolongator levels on the device (ALFD_ML_GPU_GALERKIN)
   double *g_w = nullptr, *g_tlam = nullptr;   // global W^-1 diagonal and multiplier work vector of the replicated levels
   std::vector<int64_t> ml_coff[ALFD_MAX_LEVELS];       // rank offsets of the coarse dofs of each level
@@ -3578,6 +3581,159 @@ static int upload_level(alfd_ctx *ctx, DevCsr &dst, const HostCsr &h) {
   return ALFD_OK;
 }
 
+// ---- fused smoother steps ("ml_fuse").  One application of a factored operator
+// Aug = A + gamma Ct invW C inside a Chebyshev sweep or a residual is three dependent launches plus the element-wise
+// kernel that consumes it.  Here the last two become one (aug_tail); the arithmetic of every element is the same,
+// so are the bits.
+struct FusedAug {   // the operands of one factored operator and the sweep vectors that go with it
+  DevCsr *A = nullptr, *C = nullptr, *Ct = nullptr;
+  int clsA = ALFD_T_SPMV_OTHER;
+  const uint8_t *mask = nullptr;
+  int64_t npad = 0;
+  const double *dinv = nullptr;
+  double *cd = nullptr, *cres = nullptr, *ctmp = nullptr;
+  double lmax = 0;
+};
+
+// does spmv_launch_local run m on spmv_kernel<L, *, *> (no batch-major, window or stream form)?
+static bool plain_form(const alfd_ctx *ctx, const DevCsr &m) {
+  return m.present && !m.vs.on && !m.win && !(m.L == 64 && !m.sparse && ctx->spmv_stream_R > 0);
+}
+
+// Everything else keeps the separate launches: Ct in another storage form, partitioned contexts (halo exchanges),
+// the nested grad-div term, the exact W^-1, a level without mask.
+static bool fused_ok(const alfd_ctx *ctx, const FusedAug &F) {
+  return ctx->ml_fuse && ctx->nranks == 1 && !ctx->cfg.aug_assembled && !gd_nested(ctx) &&
+         ctx->cfg.w_inverse == ALFD_W_DIAGONAL && F.mask && F.A->present && F.C->present && plain_form(ctx, *F.Ct);
+}
+
+static FusedAug level_fused(alfd_ctx *ctx, int l) {
+  MlLevel &L = ctx->ml[l];
+  FusedAug F;
+  F.A = l == 0 ? &ctx->mat[ALFD_A] : &L.A;
+  F.C = l == 0 ? &ctx->mat[ALFD_C] : &L.C;
+  F.Ct = l == 0 ? &ctx->mat[ALFD_CT] : &L.Ct;
+  F.clsA = l == 0 ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
+  F.mask = L.tail_mask;
+  F.npad = L.npad;
+  F.dinv = L.dinv;
+  F.cd = L.cd, F.cres = L.cres, F.ctmp = L.ctmp;
+  F.lmax = L.lmax;
+  return F;
+}
+
+static FusedAug patch_fused(alfd_ctx *ctx) {
+  alfd_ctx::Patch &Q = ctx->patch;
+  FusedAug F;
+  F.A = &Q.Ass, F.C = &Q.Cs, F.Ct = &Q.Cts;
+  F.mask = Q.tail_mask;
+  F.npad = Q.mpad;
+  F.dinv = Q.dinv;
+  F.cd = Q.cd, F.cres = Q.cres, F.ctmp = Q.ctmp;
+  F.lmax = Q.lmax;
+  return F;
+}
+
+// y = A x and t_lam = invW .* (C x), as level_op / patch_op launch them
+static int fused_AC(alfd_ctx *ctx, const FusedAug &F, const double *x, double *y) {
+  RC(spmv_m(ctx, *F.A, F.clsA, x, y, 0));
+  return spmv_m(ctx, *F.C, ALFD_T_SPMV_OTHER, x, ctx->t_lam, 2, 0.0, ctx->diag[ALFD_INVW]);
+}
+
+// p.y += gamma Ct t_lam, then the element-wise operation of the mode; vec_bytes: per element, of the kernel(s) replaced
+static int aug_tail(alfd_ctx *ctx, const FusedAug &F, int mode, const AugTailArgs &p, double vec_bytes) {
+  const DevCsr &m = *F.Ct;
+  const int nb_rows = m.n_list > 0 ? grid_for_rows(m.n_list, m.L) : 0;
+  const unsigned grid = (unsigned)nb_rows + (unsigned)(F.npad / kChunk);
+  if (grid == 0) return ALFD_OK;
+  Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes() + vec_bytes * (double)F.npad,
+           m.streamed_bytes(false) + vec_bytes * (double)F.npad);
+#define ALFD_TAIL(LL, MM)                                                                                         \
+  hipLaunchKernelGGL((aug_tail_kernel<LL, MM>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp, m.col,  \
+                     m.val, m.sparse ? m.rows : (const int32_t *)nullptr, ctx->t_lam, nb_rows, F.mask, p)
+#define ALFD_TAIL_L(LL)                                      \
+  switch (mode) {                                            \
+    case TAIL_STEP: ALFD_TAIL(LL, TAIL_STEP); break;         \
+    case TAIL_LAST: ALFD_TAIL(LL, TAIL_LAST); break;         \
+    case TAIL_LAST_ADD: ALFD_TAIL(LL, TAIL_LAST_ADD); break; \
+    case TAIL_RES: ALFD_TAIL(LL, TAIL_RES); break;           \
+    case TAIL_RES_INIT: ALFD_TAIL(LL, TAIL_RES_INIT); break; \
+    default: ALFD_TAIL(LL, TAIL_RES_INIT_ADD); break;        \
+  }
+  switch (m.L) {   // as spmv_launch_local
+    case 4: ALFD_TAIL_L(4) break;
+    case 8: ALFD_TAIL_L(8) break;
+    case 16: ALFD_TAIL_L(16) break;
+    case 32: ALFD_TAIL_L(32) break;
+    default: ALFD_TAIL_L(64) break;
+  }
+#undef ALFD_TAIL_L
+#undef ALFD_TAIL
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+
+// The Chebyshev sweep of level_cheb / patch_cheb on the operands of F.  have_init: z already holds the first
+// direction inv_theta * (dinv .* r) (fused_correct wrote it).  zout: the result is added to zout, z is scratch.
+// The first step reads its direction from z and its residual from r, the last stores neither: after a sweep
+// cd / cres are only ever read by the next step of the same sweep.
+static int cheb_fused(alfd_ctx *ctx, const FusedAug &F, int degree, double ratio, const double *r, double *z, double *zout,
+                      bool have_init) {
+  const double lmax = F.lmax, lmin = lmax / ratio;
+  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
+  const double sigma = theta / delta;
+  double rho = 1.0 / sigma;
+  if (!have_init) VEC_LAUNCH(cheb_init_z_kernel, F.npad, 24, 1.0 / theta, F.dinv, r, z);
+  for (int j = 1; j < degree; ++j) {
+    RC(fused_AC(ctx, F, j == 1 ? z : F.cd, F.ctmp));
+    const double rho_new = 1.0 / (2.0 * sigma - rho);
+    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
+    AugTailArgs p;
+    p.gamma = ctx->cfg.gamma, p.c1 = c1, p.c2 = c2;
+    p.dinv = F.dinv, p.y = F.ctmp, p.rin = j == 1 ? r : F.cres, p.din = j == 1 ? z : F.cd;
+    p.res = F.cres, p.d = F.cd, p.z = z, p.zout = zout;
+    const bool last = j == degree - 1;
+    RC(aug_tail(ctx, F, !last ? TAIL_STEP : zout ? TAIL_LAST_ADD : TAIL_LAST, p, last && zout ? 88.0 : 64.0));
+    rho = rho_new;
+  }
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+
+// t = r - Aug x, where t holds A x and t_lam holds invW .* (C x)
+static int fused_residual(alfd_ctx *ctx, const FusedAug &F, const double *r, double *t) {
+  AugTailArgs p;
+  p.gamma = ctx->cfg.gamma, p.y = t, p.rin = r, p.res = t;
+  return aug_tail(ctx, F, TAIL_RES, p, 24.0);
+}
+
+// The residual t = r - Aug x as above and the sweep on it: zc = q(t), or zout += q(t) with zc as scratch
+static int fused_correct(alfd_ctx *ctx, const FusedAug &F, int degree, double ratio, const double *r, double *t, double *zc,
+                         double *zout) {
+  const double lmin = F.lmax / ratio, theta = 0.5 * (F.lmax + lmin);
+  AugTailArgs p;
+  p.gamma = ctx->cfg.gamma, p.c1 = 1.0 / theta;
+  p.dinv = F.dinv, p.y = t, p.rin = r, p.res = t, p.z = zc, p.zout = zout;
+  p.store_res = degree > 1;
+  if (degree <= 1 && zout) return aug_tail(ctx, F, TAIL_RES_INIT_ADD, p, 24.0 + 32.0 + 24.0);
+  RC(aug_tail(ctx, F, TAIL_RES_INIT, p, 24.0 + (degree > 1 ? 40.0 : 32.0)));
+  return cheb_fused(ctx, F, degree, ratio, t, zc, zout, true);
+}
+
+// the mask of aug_tail_kernel for the operator whose Ct is m (setup workspace: released with it)
+static int build_tail_mask(alfd_ctx *ctx, const DevCsr &m, int64_t npad, uint8_t **mask) {
+  *mask = nullptr;
+  if (ctx->nranks > 1 || !m.present || npad == 0 || m.nrows > npad) return ALFD_OK;
+  double *q = nullptr;
+  RC(ws_alloc_zero(ctx, &q, npad / 8));
+  *mask = reinterpret_cast<uint8_t *>(q);
+  if (m.n_list > 0)
+    hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((m.n_list + 255) / 256)), dim3(256), 0, ctx->stream, m.n_list,
+                       m.sparse ? m.rows : (const int32_t *)nullptr, *mask);
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+
 // y = Aug_l x
 static int level_op(alfd_ctx *ctx, int l, const double *x, double *y) {
   if (l == 0) return op_apply(ctx, OP_AUG, x, y);
@@ -3591,6 +3747,8 @@ static int level_op(alfd_ctx *ctx, int l, const double *x, double *y) {
 // z = p_k(D^-1 Aug_l) D^-1 r on level l (Chebyshev, zero start)
 static int level_cheb(alfd_ctx *ctx, int l, int degree, double ratio, const double *r, double *z) {
   MlLevel &L = ctx->ml[l];
+  const FusedAug F = level_fused(ctx, l);
+  if (fused_ok(ctx, F)) return cheb_fused(ctx, F, degree, ratio, r, z, nullptr, false);
   const double lmax = L.lmax, lmin = lmax / ratio;
   const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
   const double sigma = theta / delta;
@@ -3669,9 +3827,16 @@ static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
   }
   MlLevel &L = ctx->ml[l], &N = ctx->ml[l + 1];
   const int sdeg = l > 0 && c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
+  const FusedAug F = level_fused(ctx, l);
+  const bool fuse = fused_ok(ctx, F);
   RC(level_cheb(ctx, l, sdeg, c.ml_smooth_ratio, r, z));                     // pre-smoothing from zero
-  RC(level_op(ctx, l, z, L.t));
-  VEC_LAUNCH(sub_from_kernel, L.npad, 24, r, L.t);                           // t = r - Aug z
+  if (fuse) {
+    RC(fused_AC(ctx, F, z, L.t));
+    RC(fused_residual(ctx, F, r, L.t));
+  } else {
+    RC(level_op(ctx, l, z, L.t));
+    VEC_LAUNCH(sub_from_kernel, L.npad, 24, r, L.t);                         // t = r - Aug z
+  }
   RC(spmv_m(ctx, N.R, ALFD_T_SPMV_OTHER, L.t, N.r, 0));                      // r_c = P^T t
   if (l + 1 == ctx->ml_rep_level) {
     // the restricted residual is gathered once; everything below runs replicated, without exchanges
@@ -3689,6 +3854,11 @@ static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
   } else {
     RC(ml_cycle(ctx, l + 1, N.r, N.z));
     RC(spmv_m(ctx, N.P, ALFD_T_SPMV_OTHER, N.z, z, 1, 1.0));                 // z += P e_c
+  }
+  if (fuse) {
+    RC(fused_AC(ctx, F, z, L.t));
+    RC(fused_correct(ctx, F, sdeg, c.ml_smooth_ratio, r, L.t, L.r, z));      // z += post-smoothing of r - Aug z
+    return ALFD_OK;
   }
   RC(level_op(ctx, l, z, L.t));
   VEC_LAUNCH(sub_from_kernel, L.npad, 24, r, L.t);
@@ -3715,6 +3885,8 @@ static int patch_op(alfd_ctx *ctx, const double *x, double *y) {
 static int patch_cheb(alfd_ctx *ctx, const double *r, double *z) {
   alfd_ctx::Patch &Q = ctx->patch;
   const int degree = ctx->cfg.ml_patch_degree;
+  const FusedAug F = patch_fused(ctx);
+  if (fused_ok(ctx, F)) return cheb_fused(ctx, F, degree, ctx->cfg.ml_patch_ratio, r, z, nullptr, false);
   const double lmax = Q.lmax, lmin = lmax / ctx->cfg.ml_patch_ratio;
   const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
   const double sigma = theta / delta;
@@ -3799,12 +3971,18 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   RC(ml_cycle(ctx, 0, Q.rr, z));
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.zS, z);
   RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));                           // (Aug z) on S
-  if (pen) {
+  const FusedAug F = patch_fused(ctx);
+  if (fused_ok(ctx, F)) {
     RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
-    RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
+    RC(fused_correct(ctx, F, ctx->cfg.ml_patch_degree, ctx->cfg.ml_patch_ratio, Q.rS, Q.uS, Q.eS, nullptr));
+  } else {
+    if (pen) {
+      RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
+      RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
+    }
+    VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);                          // uS = r_S - (Aug z)_S
+    RC(patch_cheb(ctx, Q.uS, Q.eS));
   }
-  VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);                            // uS = r_S - (Aug z)_S
-  RC(patch_cheb(ctx, Q.uS, Q.eS));
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.eS, z);
   HIPC(hipGetLastError());
   return ALFD_OK;
@@ -4094,6 +4272,7 @@ static int patch_setup(alfd_ctx *ctx, const HostCsr *A_full, const HostCsr &C, c
   Q.lmax = lam * c.cheb_safety;
   HIPC(hipMemsetAsync(Q.rS, 0, Q.mpad * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(Q.zS, 0, Q.mpad * sizeof(double), ctx->stream));
+  RC(build_tail_mask(ctx, Q.Cts, Q.mpad, &Q.tail_mask));
   HIPC(hipStreamSynchronize(ctx->stream));
   Q.on = true;
   if (c.log_level > 0 && ctx->rank == 0)
@@ -5411,6 +5590,8 @@ static int ml_setup(alfd_ctx *ctx) {
     }
     ctx->ml_rep_level = rep_from;
   }
+  for (int l = 0; l <= nlev; ++l)
+    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->ml[l].Ct, ctx->ml[l].npad, &ctx->ml[l].tail_mask));
   return ALFD_OK;
 }
 
@@ -5780,6 +5961,7 @@ int alfd_create(alfd_ctx_t *out, int device_id) {
   if (const char *e = std::getenv("ALFD_SPMV_WINDOW_MAXW")) ctx->win_maxW = std::min(16384, std::max(256, std::atoi(e)));
   if (const char *e = std::getenv("ALFD_ML_REPLICATE")) ctx->ml_rep_threshold = std::atoll(e);
   if (const char *e = std::getenv("ALFD_ML_GPU_GALERKIN")) ctx->ml_gpu_galerkin = std::atoi(e);
+  if (const char *e = std::getenv("ALFD_ML_FUSE")) ctx->ml_fuse = std::atoi(e) != 0;
   if (const char *e = std::getenv("ALFD_SPMV_VI_LEVELS")) ctx->vi_levels = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR")) ctx->vs_enable = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR_ROWS")) ctx->vs_RB = std::max(4, std::min(kVsMaxRows, std::atoi(e)));
@@ -7057,6 +7239,10 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "batch_major_xcd") == 0) {
     ctx->vs_xcd = value != 0;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "ml_fuse") == 0) {   // 0: every smoother step as separate launches (same bits either way)
+    ctx->ml_fuse = value != 0;
     return ALFD_OK;
   }
   if (std::strcmp(name, "nested_mp_group") == 0) {   // iterations of the device-stepped nested Mp CG per state read

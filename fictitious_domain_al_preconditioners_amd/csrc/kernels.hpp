@@ -1252,6 +1252,131 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(double c1, double c2,
   }
 }
 
+// z = inv_theta * (dinv .* r): cheb_init_kernel without its two copies.  The fused sweep (aug_tail_kernel) reads
+// the first direction back from z and the first residual from r itself.
+__global__ __launch_bounds__(kBlock) void cheb_init_z_kernel(double inv_theta, const double *__restrict__ dinv,
+                                                             const double *__restrict__ r, double *__restrict__ z) {
+  ALFD_FOR_PAIRS(i) {
+    const double2 dv = ld2(dinv, i), rv = ld2(r, i);
+    double2 o;
+    o.x = inv_theta * (dv.x * rv.x);
+    o.y = inv_theta * (dv.y * rv.y);
+    st2(z, i, o);
+  }
+}
+
+// --------------------------------------------------------------------------
+// Tail of a factored augmented operator y = A x + gamma Ct t, t = invW .* (C x): ONE launch forms
+// y += gamma Ct t (the EPI 1 product of spmv_kernel) and the element-wise kernel that followed it.  The
+// expressions are those of spmv_kernel, cheb_step_kernel, sub_from_kernel, cheb_init_kernel and axpy_kernel,
+// each element goes through them in the same order => same bits as the separate launches.
+//   TAIL_STEP           res = rin - y; d = fma(c1, din, c2 * (dinv .* res)); z += d      stores res, d, z
+//   TAIL_LAST           the same                                                        stores z
+//   TAIL_LAST_ADD       the same, then zout = fma(1, z, zout)                           stores zout
+//   TAIL_RES            res = rin - y                                                   stores res
+//   TAIL_RES_INIT       res = rin - y; z = c1 * (dinv .* res)   (c1 = 1 / theta)        stores z (res: store_res)
+//   TAIL_RES_INIT_ADD   the same, then zout = fma(1, z, zout)                           stores zout
+// rin / din may be the arrays res / d / z themselves (every element is read and written by one thread only).
+enum { TAIL_STEP = 0, TAIL_LAST = 1, TAIL_LAST_ADD = 2, TAIL_RES = 3, TAIL_RES_INIT = 4, TAIL_RES_INIT_ADD = 5 };
+struct AugTailArgs {
+  double gamma = 0, c1 = 0, c2 = 0;
+  const double *dinv = nullptr, *y = nullptr, *rin = nullptr, *din = nullptr;
+  double *res = nullptr, *d = nullptr, *z = nullptr, *zout = nullptr;
+  int store_res = 0;
+};
+
+template <int MODE>
+__device__ __forceinline__ void aug_tail_math(const AugTailArgs &p, double y, double dinv, double rin, double din,
+                                              double zin, double zo, double &res, double &d, double &z, double &zout) {
+  res = rin - y;
+  if (MODE <= TAIL_LAST_ADD) {
+    d = fma(p.c1, din, p.c2 * (dinv * res));
+    z = zin + d;
+    if (MODE == TAIL_LAST_ADD) zout = fma(1.0, z, zo);
+  } else if (MODE >= TAIL_RES_INIT) {
+    z = p.c1 * (dinv * res);
+    if (MODE == TAIL_RES_INIT_ADD) zout = fma(1.0, z, zo);
+  }
+}
+
+// element i, whose operator value is y
+template <int MODE>
+__device__ __forceinline__ void aug_tail_elem(const AugTailArgs &p, int64_t i, double y) {
+  constexpr bool kStep = MODE <= TAIL_LAST_ADD, kAdd = MODE == TAIL_LAST_ADD || MODE == TAIL_RES_INIT_ADD;
+  const double dinv = MODE != TAIL_RES ? p.dinv[i] : 0.0, rin = p.rin[i];
+  const double din = kStep ? p.din[i] : 0.0, zin = kStep ? p.z[i] : 0.0, zo = kAdd ? p.zout[i] : 0.0;
+  double res, d = 0.0, z = 0.0, zout = 0.0;
+  aug_tail_math<MODE>(p, y, dinv, rin, din, zin, zo, res, d, z, zout);
+  if (MODE == TAIL_STEP || MODE == TAIL_RES || (MODE == TAIL_RES_INIT && p.store_res)) p.res[i] = res;
+  if (MODE == TAIL_STEP) p.d[i] = d;
+  if (MODE == TAIL_STEP || MODE == TAIL_LAST || MODE == TAIL_RES_INIT) p.z[i] = z;
+  if (kAdd) p.zout[i] = zout;
+}
+
+// Workgroups [0, nb_rows): the rows of Ct (n_list of them; rows[] lists them when Ct is in row-list form), L lanes
+// per row as in spmv_kernel<L, 1, *>, lane 0 goes on with the element-wise tail of its row.
+// Workgroups [nb_rows, nb_rows + npad / kChunk): the padded vector in the ALFD_FOR_PAIRS mapping; elements whose
+// mask byte is set belong to the first party and are skipped (a row of Ct that is not listed is never touched by
+// the separate product either: y_r stays the A x value).
+template <int L, int MODE>
+__global__ __launch_bounds__(kBlock) void aug_tail_kernel(int64_t n_list, const int64_t *__restrict__ rp,
+                                                          const int32_t *__restrict__ col,
+                                                          const double *__restrict__ val,
+                                                          const int32_t *__restrict__ rows,
+                                                          const double *__restrict__ t, int nb_rows,
+                                                          const uint8_t *__restrict__ mask, AugTailArgs p) {
+  if ((int)blockIdx.x < nb_rows) {
+    constexpr int RPB = kBlock / L;
+    const int lane = threadIdx.x % L;
+    const int sub = threadIdx.x / L;
+    const int64_t ngroups = (n_list + RPB - 1) / RPB;
+    for (int64_t g = blockIdx.x; g < ngroups; g += nb_rows) {
+      const int64_t r = g * RPB + sub;
+      if (r < n_list) {  // uniform within the L-lane group
+        const int64_t k0 = rp[r], k1 = rp[r + 1];
+        double acc = 0.0;
+        for (int64_t k = k0 + lane; k < k1; k += L) acc = fma(val[k], t[col[k]], acc);
+        acc = group_reduce<L>(acc);
+        if (lane == 0) {
+          const int64_t ro = rows ? (int64_t)rows[r] : r;
+          aug_tail_elem<MODE>(p, ro, fma(p.gamma, acc, p.y[ro]));
+        }
+      }
+    }
+    return;
+  }
+  constexpr bool kStep = MODE <= TAIL_LAST_ADD, kAdd = MODE == TAIL_LAST_ADD || MODE == TAIL_RES_INIT_ADD;
+  const int64_t base = (int64_t)((int)blockIdx.x - nb_rows) * kChunk;
+#pragma unroll
+  for (int e = 0; e < 8; ++e) {
+    const int64_t i = base + e * 512 + 2 * threadIdx.x;
+    const uchar2 mk = *reinterpret_cast<const uchar2 *>(mask + i);
+    if (mk.x | mk.y) {
+      if (!mk.x) aug_tail_elem<MODE>(p, i, p.y[i]);
+      if (!mk.y) aug_tail_elem<MODE>(p, i + 1, p.y[i + 1]);
+      continue;
+    }
+    const double2 zero = {0.0, 0.0};
+    const double2 yv = ld2(p.y, i), rv = ld2(p.rin, i);
+    const double2 dv = MODE != TAIL_RES ? ld2(p.dinv, i) : zero;
+    const double2 dd = kStep ? ld2(p.din, i) : zero, zi = kStep ? ld2(p.z, i) : zero;
+    const double2 zo = kAdd ? ld2(p.zout, i) : zero;
+    double2 res, d = zero, z = zero, zout = zero;
+    aug_tail_math<MODE>(p, yv.x, dv.x, rv.x, dd.x, zi.x, zo.x, res.x, d.x, z.x, zout.x);
+    aug_tail_math<MODE>(p, yv.y, dv.y, rv.y, dd.y, zi.y, zo.y, res.y, d.y, z.y, zout.y);
+    if (MODE == TAIL_STEP || MODE == TAIL_RES || (MODE == TAIL_RES_INIT && p.store_res)) st2(p.res, i, res);
+    if (MODE == TAIL_STEP) st2(p.d, i, d);
+    if (MODE == TAIL_STEP || MODE == TAIL_LAST || MODE == TAIL_RES_INIT) st2(p.z, i, z);
+    if (kAdd) st2(p.zout, i, zout);
+  }
+}
+
+// mask[row] = 1 for the rows aug_tail_kernel's first party owns
+__global__ void mark_rows_kernel(int64_t n_list, const int32_t *__restrict__ rows, uint8_t *__restrict__ mask) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i < n_list) mask[rows ? (int64_t)rows[i] : i] = 1;
+}
+
 // ---- batched lock-step CG (RationalPreconditioner: 21 independent SPD solves on
 // the immersed matrices, rational_preconditioner.h:41-56).  All systems advance
 // together, one workgroup-chunk per 4096 entries; segment s owns chunks

@@ -557,6 +557,12 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
  *                  "nested_mp_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
+ *   "ml_fuse"      1 (default; environment ALFD_ML_FUSE, read at alfd_create): inside ALFD_PREC_MULTILEVEL the product
+ *                  y += gamma Ct t that ends every factored operator A + gamma Ct invW C and the element-wise kernel
+ *                  after it (Chebyshev step, residual, residual + first direction, final z += correction) are one
+ *                  launch (aug_tail_kernel); 0: separate launches.  Same bits either way; takes effect at the next
+ *                  apply.  Operators whose Ct is not in the plain row-per-lane-group form, partitioned contexts,
+ *                  grad_div_in_A = 0, w_inverse != diagonal and aug_assembled always use the separate launches.
  * Returns ALFD_E_INVALID for an unknown name. */
 int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value);
 /* Kernel-class timing of the last solve, accumulated with HIP events when
