@@ -1042,27 +1042,46 @@ static const double *op_dinv(const alfd_ctx *ctx, int op) {
          : op == OP_K ? ctx->dinv_k : op == OP_MASS ? ctx->dinv_m : ctx->diag[ALFD_MP_LUMPED_INV];
 }
 
-// Chebyshev sweep z = p_k(D^-1 Op) D^-1 r
-static int cheb_apply(alfd_ctx *ctx, int op, const double *r, double *z, int64_t npad) {
-  const double lmax = ctx->lam_max[op], lmin = lmax / ctx->cfg.cheb_eig_ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  const int k = ctx->cfg.cheb_degree;
-  const double *dinv = op_dinv(ctx, op);
-  VEC_LAUNCH(cheb_init_kernel, npad, k > 1 ? 40 : 32, 1.0 / theta, dinv, r, ctx->c_d, z, ctx->c_res,
-             k > 1 ? 1 : 0);
-  // SpMV writes rows only: padding of the product vector must be zero
-  if (k > 1) HIPC(hipMemsetAsync(ctx->c_tmp, 0, npad * sizeof(double), ctx->stream));
-  for (int j = 1; j < k; ++j) {
-    RC(op_apply(ctx, op, ctx->c_d, ctx->c_tmp));
+// Chebyshev coefficients for the spectrum [lmax / ratio, lmax]: the first direction is (1 / theta) D^-1 r,
+// step() gives c1, c2 of the next one (d = c1 d + c2 D^-1 res)
+struct ChebCoef {
+  double theta, delta, sigma, rho;
+  ChebCoef(double lmax, double ratio) {
+    const double lmin = lmax / ratio;
+    theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
+    sigma = theta / delta;
+    rho = 1.0 / sigma;
+  }
+  void step(double &c1, double &c2) {
     const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-    VEC_LAUNCH(cheb_step_kernel, npad, 64, c1, c2, dinv, ctx->c_tmp, ctx->c_res, ctx->c_d, z);
+    c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
     rho = rho_new;
+  }
+};
+
+// Chebyshev sweep z = p_k(D^-1 Op) D^-1 r from a zero start, k = degree; apply(x, y): y = Op x.
+// cd / cres / ctmp: direction, residual and product vectors of the sweep.
+template <class Apply>
+static int cheb_sweep(alfd_ctx *ctx, int64_t npad, const double *dinv, double lmax, double ratio, int degree, double *cd,
+                      double *cres, double *ctmp, const double *r, double *z, Apply apply) {
+  ChebCoef k(lmax, ratio);
+  VEC_LAUNCH(cheb_init_kernel, npad, degree > 1 ? 40 : 32, 1.0 / k.theta, dinv, r, cd, z, cres, degree > 1 ? 1 : 0);
+  for (int j = 1; j < degree; ++j) {
+    RC(apply(cd, ctmp));
+    double c1, c2;
+    k.step(c1, c2);
+    VEC_LAUNCH(cheb_step_kernel, npad, 64, c1, c2, dinv, ctmp, cres, cd, z);
   }
   HIPC(hipGetLastError());
   return ALFD_OK;
+}
+
+static int cheb_apply(alfd_ctx *ctx, int op, const double *r, double *z, int64_t npad) {
+  const int k = ctx->cfg.cheb_degree;
+  // SpMV writes rows only: padding of the product vector must be zero
+  if (k > 1) HIPC(hipMemsetAsync(ctx->c_tmp, 0, npad * sizeof(double), ctx->stream));
+  return cheb_sweep(ctx, npad, op_dinv(ctx, op), ctx->lam_max[op], ctx->cfg.cheb_eig_ratio, k, ctx->c_d, ctx->c_res,
+                    ctx->c_tmp, r, z, [&](const double *x, double *y) { return op_apply(ctx, op, x, y); });
 }
 
 // deal.II SolverCG via inverse_operator (zero initial guess) [EXT]; b and x are
@@ -3379,6 +3398,35 @@ static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *
   return ALFD_OK;
 }
 
+// *lambda = |D^-1 Op v| after cheb_power_its normalised steps from the start vector in v; apply(x, y): y = Op x.
+// v and wv (the second work vector) change roles every step and hold no result afterwards.
+template <class Apply>
+static int power_lambda(alfd_ctx *ctx, int64_t npad, const double *dinv, double *v, double *wv, Apply apply, double *lambda) {
+  *lambda = 0;
+  for (int it = 0; it < ctx->cfg.cheb_power_its; ++it) {
+    RC(dot_async(ctx, npad, v, v, S_TMP));
+    RC(read_scalars(ctx, S_TMP, 1));
+    const double nv = std::sqrt(ctx->sc_host[S_TMP]);
+    VEC_LAUNCH(scale_kernel, npad, 16, (const double *)nullptr, 0, 0, 1.0 / nv, v);
+    RC(apply(v, wv));
+    VEC_LAUNCH(pmul_scale_kernel, npad, 24, 1.0, dinv, wv, wv);
+    RC(dot_async(ctx, npad, wv, wv, S_TMP));
+    RC(read_scalars(ctx, S_TMP, 1));
+    *lambda = std::sqrt(ctx->sc_host[S_TMP]);
+    std::swap(v, wv);
+  }
+  return ALFD_OK;
+}
+
+// Reductions over replicated vectors for the lifetime of the guard: the flag is cleared on every way out
+struct ReplicatedDots {
+  alfd_ctx *ctx;
+  explicit ReplicatedDots(alfd_ctx *c) : ctx(c) { ctx->dots_replicated = true; }
+  ~ReplicatedDots() { ctx->dots_replicated = false; }
+  ReplicatedDots(const ReplicatedDots &) = delete;
+  ReplicatedDots &operator=(const ReplicatedDots &) = delete;
+};
+
 // lambda_max(D^-1 Op) by power iteration from the integer-hash start vector
 static int power_iteration(alfd_ctx *ctx, int op) {
   const alfd_config &c = ctx->cfg;
@@ -3398,18 +3446,7 @@ static int power_iteration(alfd_ctx *ctx, int op) {
     fill((op == OP_AUG || op == OP_K) ? 0 : 1, v);
   }
   double lam = 0;
-  for (int it = 0; it < c.cheb_power_its; ++it) {
-    RC(dot_async(ctx, npad, v, v, S_TMP));
-    RC(read_scalars(ctx, S_TMP, 1));
-    const double nv = std::sqrt(ctx->sc_host[S_TMP]);
-    VEC_LAUNCH(scale_kernel, npad, 16, (const double *)nullptr, 0, 0, 1.0 / nv, v);
-    RC(op_apply(ctx, op, v, wv));
-    VEC_LAUNCH(pmul_scale_kernel, npad, 24, 1.0, op_dinv(ctx, op), wv, wv);
-    RC(dot_async(ctx, npad, wv, wv, S_TMP));
-    RC(read_scalars(ctx, S_TMP, 1));
-    lam = std::sqrt(ctx->sc_host[S_TMP]);
-    std::swap(v, wv);
-  }
+  RC(power_lambda(ctx, npad, op_dinv(ctx, op), v, wv, [&](const double *x, double *y) { return op_apply(ctx, op, x, y); }, &lam));
   ctx->lam_max[op] = lam * c.cheb_safety;
   HIPC(hipMemsetAsync(ctx->w_p, 0, ctx->wmax * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(ctx->w_Ap, 0, ctx->wmax * sizeof(double), ctx->stream));
@@ -3581,13 +3618,13 @@ static int upload_level(alfd_ctx *ctx, DevCsr &dst, const HostCsr &h) {
   return ALFD_OK;
 }
 
-// ---- fused smoother steps ("ml_fuse").  One application of a factored operator
-// Aug = A + gamma Ct invW C inside a Chebyshev sweep or a residual is three dependent launches plus the element-wise
-// kernel that consumes it.  Here the last two become one (aug_tail); the arithmetic of every element is the same,
-// so are the bits.
-struct FusedAug {   // the operands of one factored operator and the sweep vectors that go with it
+// ---- the factored operators of the hierarchy: Aug = A + gamma Ct invW C of a level (rank-local or replicated) and of
+// the interface patch.  level_view() / patch_aug() are the only places that know which of these an AugOp names.
+struct AugOp {   // the operands of one factored operator and the sweep vectors that go with it
   DevCsr *A = nullptr, *C = nullptr, *Ct = nullptr;
   int clsA = ALFD_T_SPMV_OTHER;
+  const double *w = nullptr;   // invW over the multipliers that C addresses
+  double *tlam = nullptr;      // invW .* (C x)
   const uint8_t *mask = nullptr;
   int64_t npad = 0;
   const double *dinv = nullptr;
@@ -3595,37 +3632,48 @@ struct FusedAug {   // the operands of one factored operator and the sweep vecto
   double lmax = 0;
 };
 
-// does spmv_launch_local run m on spmv_kernel<L, *, *> (no batch-major, window or stream form)?
-static bool plain_form(const alfd_ctx *ctx, const DevCsr &m) {
-  return m.present && !m.vs.on && !m.win && !(m.L == 64 && !m.sparse && ctx->spmv_stream_R > 0);
-}
+// One level as the V-cycle sees it: its operator, its vectors, and the transfer pair to the next coarser level with
+// that level's r / z (null on the coarsest level)
+struct LevelView {
+  AugOp op;
+  double *r = nullptr, *z = nullptr, *t = nullptr;
+  DevCsr *R = nullptr, *P = nullptr;
+  double *rc = nullptr, *zc = nullptr;
+};
 
-// Everything else keeps the separate launches: Ct in another storage form, partitioned contexts (halo exchanges),
-// the nested grad-div term, the exact W^-1, a level without mask.
-static bool fused_ok(const alfd_ctx *ctx, const FusedAug &F) {
-  return ctx->ml_fuse && ctx->nranks == 1 && !ctx->cfg.aug_assembled && !gd_nested(ctx) &&
-         ctx->cfg.w_inverse == ALFD_W_DIAGONAL && F.mask && F.A->present && F.C->present && plain_form(ctx, *F.Ct);
-}
-
-static FusedAug level_fused(alfd_ctx *ctx, int l) {
+// Levels from ml_rep_level on are replicated.  The level above the first replicated one keeps the rank-local pair:
+// ml_cycle gathers the restricted residual there.
+static LevelView level_view(alfd_ctx *ctx, int l) {
   MlLevel &L = ctx->ml[l];
-  FusedAug F;
-  F.A = l == 0 ? &ctx->mat[ALFD_A] : &L.A;
-  F.C = l == 0 ? &ctx->mat[ALFD_C] : &L.C;
-  F.Ct = l == 0 ? &ctx->mat[ALFD_CT] : &L.Ct;
+  const bool rep = ctx->ml_rep_level >= 0 && l >= ctx->ml_rep_level;
+  LevelView V;
+  AugOp &F = V.op;
+  F.A = rep ? &L.gA : l == 0 ? &ctx->mat[ALFD_A] : &L.A;
+  F.C = rep ? &L.gC : l == 0 ? &ctx->mat[ALFD_C] : &L.C;
+  F.Ct = rep ? &L.gCt : l == 0 ? &ctx->mat[ALFD_CT] : &L.Ct;
   F.clsA = l == 0 ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
+  F.w = rep ? ctx->g_w : ctx->diag[ALFD_INVW];
+  F.tlam = rep ? ctx->g_tlam : ctx->t_lam;
   F.mask = L.tail_mask;
-  F.npad = L.npad;
-  F.dinv = L.dinv;
-  F.cd = L.cd, F.cres = L.cres, F.ctmp = L.ctmp;
+  F.npad = rep ? L.gnpad : L.npad;
+  F.dinv = rep ? L.gdinv : L.dinv;
+  F.cd = rep ? L.gcd : L.cd, F.cres = rep ? L.gcres : L.cres, F.ctmp = rep ? L.gctmp : L.ctmp;
   F.lmax = L.lmax;
-  return F;
+  V.r = rep ? L.gr : L.r, V.z = rep ? L.gz : L.z, V.t = rep ? L.gt : L.t;
+  if (l + 1 < (int)ctx->ml.size()) {
+    MlLevel &N = ctx->ml[l + 1];
+    V.R = rep ? &N.gR : &N.R, V.P = rep ? &N.gP : &N.P;
+    V.rc = rep ? N.gr : N.r, V.zc = rep ? N.gz : N.z;
+  }
+  return V;
 }
 
-static FusedAug patch_fused(alfd_ctx *ctx) {
+static AugOp patch_aug(alfd_ctx *ctx) {
   alfd_ctx::Patch &Q = ctx->patch;
-  FusedAug F;
+  AugOp F;
   F.A = &Q.Ass, F.C = &Q.Cs, F.Ct = &Q.Cts;
+  F.w = Q.rep ? ctx->g_w : ctx->diag[ALFD_INVW];       // replicated patch: the whole multiplier space
+  F.tlam = Q.rep ? ctx->g_tlam : ctx->t_lam;
   F.mask = Q.tail_mask;
   F.npad = Q.mpad;
   F.dinv = Q.dinv;
@@ -3634,14 +3682,38 @@ static FusedAug patch_fused(alfd_ctx *ctx) {
   return F;
 }
 
-// y = A x and t_lam = invW .* (C x), as level_op / patch_op launch them
-static int fused_AC(alfd_ctx *ctx, const FusedAug &F, const double *x, double *y) {
+// y = A x and tlam = invW .* (C x): the first two launches of aug_apply
+static int fused_AC(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) {
   RC(spmv_m(ctx, *F.A, F.clsA, x, y, 0));
-  return spmv_m(ctx, *F.C, ALFD_T_SPMV_OTHER, x, ctx->t_lam, 2, 0.0, ctx->diag[ALFD_INVW]);
+  return spmv_m(ctx, *F.C, ALFD_T_SPMV_OTHER, x, F.tlam, 2, 0.0, F.w);
 }
 
-// p.y += gamma Ct t_lam, then the element-wise operation of the mode; vec_bytes: per element, of the kernel(s) replaced
-static int aug_tail(alfd_ctx *ctx, const FusedAug &F, int mode, const AugTailArgs &p, double vec_bytes) {
+// y = Aug x.  On level 0 these are the launches of op_apply(OP_AUG) with the diagonal weight: setup() refuses the
+// multilevel preconditioner together with the nested grad-div term.
+static int aug_apply(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) {
+  if (ctx->cfg.aug_assembled) return spmv_m(ctx, *F.A, F.clsA, x, y, 0);   // operator form: A already holds the AL term
+  RC(fused_AC(ctx, F, x, y));
+  return spmv_m(ctx, *F.Ct, ALFD_T_SPMV_OTHER, F.tlam, y, 1, ctx->cfg.gamma);
+}
+
+// ---- fused smoother steps ("ml_fuse").  One application of a factored operator inside a Chebyshev
+// sweep or a residual is three dependent launches plus the element-wise kernel that consumes it.  Here the last two
+// become one (aug_tail); the arithmetic of every element is the same, so are the bits.
+
+// does spmv_launch_local run m on spmv_kernel<L, *, *> (no batch-major, window or stream form)?
+static bool plain_form(const alfd_ctx *ctx, const DevCsr &m) {
+  return m.present && !m.vs.on && !m.win && !(m.L == 64 && !m.sparse && ctx->spmv_stream_R > 0);
+}
+
+// Everything else keeps the separate launches: Ct in another storage form, partitioned contexts (halo exchanges),
+// the nested grad-div term, the exact W^-1, a level without mask.
+static bool fused_ok(const alfd_ctx *ctx, const AugOp &F) {
+  return ctx->ml_fuse && ctx->nranks == 1 && !ctx->cfg.aug_assembled && !gd_nested(ctx) &&
+         ctx->cfg.w_inverse == ALFD_W_DIAGONAL && F.mask && F.A->present && F.C->present && plain_form(ctx, *F.Ct);
+}
+
+// p.y += gamma Ct tlam, then the element-wise operation of the mode; vec_bytes: per element, of the kernel(s) replaced
+static int aug_tail(alfd_ctx *ctx, const AugOp &F, int mode, const AugTailArgs &p, double vec_bytes) {
   const DevCsr &m = *F.Ct;
   const int nb_rows = m.n_list > 0 ? grid_for_rows(m.n_list, m.L) : 0;
   const unsigned grid = (unsigned)nb_rows + (unsigned)(F.npad / kChunk);
@@ -3650,7 +3722,7 @@ static int aug_tail(alfd_ctx *ctx, const FusedAug &F, int mode, const AugTailArg
            m.streamed_bytes(false) + vec_bytes * (double)F.npad);
 #define ALFD_TAIL(LL, MM)                                                                                         \
   hipLaunchKernelGGL((aug_tail_kernel<LL, MM>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp, m.col,  \
-                     m.val, m.sparse ? m.rows : (const int32_t *)nullptr, ctx->t_lam, nb_rows, F.mask, p)
+                     m.val, m.sparse ? m.rows : (const int32_t *)nullptr, F.tlam, nb_rows, F.mask, p)
 #define ALFD_TAIL_L(LL)                                      \
   switch (mode) {                                            \
     case TAIL_STEP: ALFD_TAIL(LL, TAIL_STEP); break;         \
@@ -3673,46 +3745,47 @@ static int aug_tail(alfd_ctx *ctx, const FusedAug &F, int mode, const AugTailArg
   return ALFD_OK;
 }
 
-// The Chebyshev sweep of level_cheb / patch_cheb on the operands of F.  have_init: z already holds the first
+// The Chebyshev sweep of cheb_sweep on the operands of F.  have_init: z already holds the first
 // direction inv_theta * (dinv .* r) (fused_correct wrote it).  zout: the result is added to zout, z is scratch.
 // The first step reads its direction from z and its residual from r, the last stores neither: after a sweep
 // cd / cres are only ever read by the next step of the same sweep.
-static int cheb_fused(alfd_ctx *ctx, const FusedAug &F, int degree, double ratio, const double *r, double *z, double *zout,
+static int cheb_fused(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *r, double *z, double *zout,
                       bool have_init) {
-  const double lmax = F.lmax, lmin = lmax / ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  if (!have_init) VEC_LAUNCH(cheb_init_z_kernel, F.npad, 24, 1.0 / theta, F.dinv, r, z);
+  ChebCoef k(F.lmax, ratio);
+  if (!have_init) VEC_LAUNCH(cheb_init_z_kernel, F.npad, 24, 1.0 / k.theta, F.dinv, r, z);
   for (int j = 1; j < degree; ++j) {
     RC(fused_AC(ctx, F, j == 1 ? z : F.cd, F.ctmp));
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
     AugTailArgs p;
-    p.gamma = ctx->cfg.gamma, p.c1 = c1, p.c2 = c2;
+    k.step(p.c1, p.c2);
+    p.gamma = ctx->cfg.gamma;
     p.dinv = F.dinv, p.y = F.ctmp, p.rin = j == 1 ? r : F.cres, p.din = j == 1 ? z : F.cd;
     p.res = F.cres, p.d = F.cd, p.z = z, p.zout = zout;
     const bool last = j == degree - 1;
     RC(aug_tail(ctx, F, !last ? TAIL_STEP : zout ? TAIL_LAST_ADD : TAIL_LAST, p, last && zout ? 88.0 : 64.0));
-    rho = rho_new;
   }
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
 
-// t = r - Aug x, where t holds A x and t_lam holds invW .* (C x)
-static int fused_residual(alfd_ctx *ctx, const FusedAug &F, const double *r, double *t) {
+// z = p_k(D^-1 Aug) D^-1 r, k = degree (Chebyshev, zero start)
+static int aug_cheb(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *r, double *z) {
+  if (fused_ok(ctx, F)) return cheb_fused(ctx, F, degree, ratio, r, z, nullptr, false);
+  return cheb_sweep(ctx, F.npad, F.dinv, F.lmax, ratio, degree, F.cd, F.cres, F.ctmp, r, z,
+                    [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); });
+}
+
+// t = r - Aug x, where t holds A x and tlam holds invW .* (C x)
+static int fused_residual(alfd_ctx *ctx, const AugOp &F, const double *r, double *t) {
   AugTailArgs p;
   p.gamma = ctx->cfg.gamma, p.y = t, p.rin = r, p.res = t;
   return aug_tail(ctx, F, TAIL_RES, p, 24.0);
 }
 
 // The residual t = r - Aug x as above and the sweep on it: zc = q(t), or zout += q(t) with zc as scratch
-static int fused_correct(alfd_ctx *ctx, const FusedAug &F, int degree, double ratio, const double *r, double *t, double *zc,
+static int fused_correct(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *r, double *t, double *zc,
                          double *zout) {
-  const double lmin = F.lmax / ratio, theta = 0.5 * (F.lmax + lmin);
   AugTailArgs p;
-  p.gamma = ctx->cfg.gamma, p.c1 = 1.0 / theta;
+  p.gamma = ctx->cfg.gamma, p.c1 = 1.0 / ChebCoef(F.lmax, ratio).theta;
   p.dinv = F.dinv, p.y = t, p.rin = r, p.res = t, p.z = zc, p.zout = zout;
   p.store_res = degree > 1;
   if (degree <= 1 && zout) return aug_tail(ctx, F, TAIL_RES_INIT_ADD, p, 24.0 + 32.0 + 24.0);
@@ -3734,112 +3807,30 @@ static int build_tail_mask(alfd_ctx *ctx, const DevCsr &m, int64_t npad, uint8_t
   return ALFD_OK;
 }
 
-// y = Aug_l x
-static int level_op(alfd_ctx *ctx, int l, const double *x, double *y) {
-  if (l == 0) return op_apply(ctx, OP_AUG, x, y);
-  MlLevel &L = ctx->ml[l];
-  RC(spmv_m(ctx, L.A, ALFD_T_SPMV_OTHER, x, y, 0));
-  if (ctx->cfg.aug_assembled) return ALFD_OK;
-  RC(spmv_m(ctx, L.C, ALFD_T_SPMV_OTHER, x, ctx->t_lam, 2, 0.0, ctx->diag[ALFD_INVW]));
-  return spmv_m(ctx, L.Ct, ALFD_T_SPMV_OTHER, ctx->t_lam, y, 1, ctx->cfg.gamma);
-}
-
-// z = p_k(D^-1 Aug_l) D^-1 r on level l (Chebyshev, zero start)
-static int level_cheb(alfd_ctx *ctx, int l, int degree, double ratio, const double *r, double *z) {
-  MlLevel &L = ctx->ml[l];
-  const FusedAug F = level_fused(ctx, l);
-  if (fused_ok(ctx, F)) return cheb_fused(ctx, F, degree, ratio, r, z, nullptr, false);
-  const double lmax = L.lmax, lmin = lmax / ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  VEC_LAUNCH(cheb_init_kernel, L.npad, degree > 1 ? 40 : 32, 1.0 / theta, L.dinv, r, L.cd, z, L.cres,
-             degree > 1 ? 1 : 0);
-  for (int j = 1; j < degree; ++j) {
-    RC(level_op(ctx, l, L.cd, L.ctmp));
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-    VEC_LAUNCH(cheb_step_kernel, L.npad, 64, c1, c2, L.dinv, L.ctmp, L.cres, L.cd, z);
-    rho = rho_new;
-  }
-  HIPC(hipGetLastError());
-  return ALFD_OK;
-}
-
-// ---- replicated levels: every rank holds the global operators and vectors and does the same work
-static int level_op_rep(alfd_ctx *ctx, int l, const double *x, double *y) {
-  MlLevel &L = ctx->ml[l];
-  RC(spmv_m(ctx, L.gA, ALFD_T_SPMV_OTHER, x, y, 0));
-  if (ctx->cfg.aug_assembled) return ALFD_OK;
-  RC(spmv_m(ctx, L.gC, ALFD_T_SPMV_OTHER, x, ctx->g_tlam, 2, 0.0, ctx->g_w));
-  return spmv_m(ctx, L.gCt, ALFD_T_SPMV_OTHER, ctx->g_tlam, y, 1, ctx->cfg.gamma);
-}
-
-static int level_cheb_rep(alfd_ctx *ctx, int l, int degree, double ratio, const double *r, double *z) {
-  MlLevel &L = ctx->ml[l];
-  const double lmax = L.lmax, lmin = lmax / ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  VEC_LAUNCH(cheb_init_kernel, L.gnpad, degree > 1 ? 40 : 32, 1.0 / theta, L.gdinv, r, L.gcd, z, L.gcres,
-             degree > 1 ? 1 : 0);
-  for (int j = 1; j < degree; ++j) {
-    RC(level_op_rep(ctx, l, L.gcd, L.gctmp));
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-    VEC_LAUNCH(cheb_step_kernel, L.gnpad, 64, c1, c2, L.gdinv, L.gctmp, L.gcres, L.gcd, z);
-    rho = rho_new;
-  }
-  HIPC(hipGetLastError());
-  return ALFD_OK;
-}
-
-static int ml_cycle_rep(alfd_ctx *ctx, int l, const double *r, double *z) {
-  const alfd_config &c = ctx->cfg;
-  const int last = (int)ctx->ml.size() - 1;
-  if (l == last) {
-    if (ctx->ml_inv.present) return spmv_m(ctx, ctx->ml_inv, ALFD_T_SPMV_OTHER, r, z, 0);
-    return level_cheb_rep(ctx, l, c.ml_coarse_degree, c.ml_coarse_ratio, r, z);
-  }
-  MlLevel &L = ctx->ml[l], &N = ctx->ml[l + 1];
-  const int sdeg = l > 0 && c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
-  RC(level_cheb_rep(ctx, l, sdeg, c.ml_smooth_ratio, r, z));
-  RC(level_op_rep(ctx, l, z, L.gt));
-  VEC_LAUNCH(sub_from_kernel, L.gnpad, 24, r, L.gt);
-  RC(spmv_m(ctx, N.gR, ALFD_T_SPMV_OTHER, L.gt, N.gr, 0));
-  RC(ml_cycle_rep(ctx, l + 1, N.gr, N.gz));
-  RC(spmv_m(ctx, N.gP, ALFD_T_SPMV_OTHER, N.gz, z, 1, 1.0));
-  RC(level_op_rep(ctx, l, z, L.gt));
-  VEC_LAUNCH(sub_from_kernel, L.gnpad, 24, r, L.gt);
-  RC(level_cheb_rep(ctx, l, sdeg, c.ml_smooth_ratio, L.gt, L.gr));
-  VEC_LAUNCH(axpy_kernel, L.gnpad, 24, (const double *)nullptr, 0, 1.0, L.gr, z);
-  HIPC(hipGetLastError());
-  return ALFD_OK;
-}
-
 // z = V-cycle(r) on level l
 static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
   const alfd_config &c = ctx->cfg;
   const int last = (int)ctx->ml.size() - 1;
+  const LevelView L = level_view(ctx, l);
+  const AugOp &F = L.op;
   if (l == last) {
     if (ctx->ml_inv.present) return spmv_m(ctx, ctx->ml_inv, ALFD_T_SPMV_OTHER, r, z, 0);   // z = Aug_c^-1 r
-    return level_cheb(ctx, l, c.ml_coarse_degree, c.ml_coarse_ratio, r, z);
+    return aug_cheb(ctx, F, c.ml_coarse_degree, c.ml_coarse_ratio, r, z);
   }
-  MlLevel &L = ctx->ml[l], &N = ctx->ml[l + 1];
   const int sdeg = l > 0 && c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
-  const FusedAug F = level_fused(ctx, l);
   const bool fuse = fused_ok(ctx, F);
-  RC(level_cheb(ctx, l, sdeg, c.ml_smooth_ratio, r, z));                     // pre-smoothing from zero
+  RC(aug_cheb(ctx, F, sdeg, c.ml_smooth_ratio, r, z));                       // pre-smoothing from zero
   if (fuse) {
     RC(fused_AC(ctx, F, z, L.t));
     RC(fused_residual(ctx, F, r, L.t));
   } else {
-    RC(level_op(ctx, l, z, L.t));
-    VEC_LAUNCH(sub_from_kernel, L.npad, 24, r, L.t);                         // t = r - Aug z
+    RC(aug_apply(ctx, F, z, L.t));
+    VEC_LAUNCH(sub_from_kernel, F.npad, 24, r, L.t);                         // t = r - Aug z
   }
-  RC(spmv_m(ctx, N.R, ALFD_T_SPMV_OTHER, L.t, N.r, 0));                      // r_c = P^T t
+  RC(spmv_m(ctx, *L.R, ALFD_T_SPMV_OTHER, L.t, L.rc, 0));                    // r_c = P^T t
   if (l + 1 == ctx->ml_rep_level) {
     // the restricted residual is gathered once; everything below runs replicated, without exchanges
+    MlLevel &N = ctx->ml[l + 1];
     HIPC(hipMemcpyAsync(N.g_send, N.r, N.n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     RC(comm_allgather(ctx, N.g_send, N.g_stage, (size_t)N.g_maxpiece * sizeof(double)));
     for (int p = 0; p < ctx->nranks; ++p) {
@@ -3848,57 +3839,22 @@ static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
         HIPC(hipMemcpyAsync(N.gr + N.g_offs[p], N.g_stage + (int64_t)p * N.g_maxpiece, np * sizeof(double),
                             hipMemcpyDeviceToDevice, ctx->stream));
     }
-    RC(ml_cycle_rep(ctx, l + 1, N.gr, N.gz));
+    RC(ml_cycle(ctx, l + 1, N.gr, N.gz));
     // z += P e_c: aggregates -> my slice of e_c; CSR prolongators address the replicated vector by global ids
     RC(spmv_m(ctx, N.P, ALFD_T_SPMV_OTHER, N.P_global_cols ? N.gz : N.gz + N.g_offs[ctx->rank], z, 1, 1.0));
   } else {
-    RC(ml_cycle(ctx, l + 1, N.r, N.z));
-    RC(spmv_m(ctx, N.P, ALFD_T_SPMV_OTHER, N.z, z, 1, 1.0));                 // z += P e_c
+    RC(ml_cycle(ctx, l + 1, L.rc, L.zc));
+    RC(spmv_m(ctx, *L.P, ALFD_T_SPMV_OTHER, L.zc, z, 1, 1.0));               // z += P e_c
   }
   if (fuse) {
     RC(fused_AC(ctx, F, z, L.t));
     RC(fused_correct(ctx, F, sdeg, c.ml_smooth_ratio, r, L.t, L.r, z));      // z += post-smoothing of r - Aug z
     return ALFD_OK;
   }
-  RC(level_op(ctx, l, z, L.t));
-  VEC_LAUNCH(sub_from_kernel, L.npad, 24, r, L.t);
-  RC(level_cheb(ctx, l, sdeg, c.ml_smooth_ratio, L.t, L.r));                 // post-smoothing correction
-  VEC_LAUNCH(axpy_kernel, L.npad, 24, (const double *)nullptr, 0, 1.0, L.r, z);
-  HIPC(hipGetLastError());
-  return ALFD_OK;
-}
-
-static int ws_alloc_zero(alfd_ctx *ctx, double **p, int64_t count);
-
-// ---- interface patch (alfd_config::ml_patch_degree): y = Aug_SS x on patch-compact vectors
-static int patch_op(alfd_ctx *ctx, const double *x, double *y) {
-  alfd_ctx::Patch &Q = ctx->patch;
-  RC(spmv_m(ctx, Q.Ass, ALFD_T_SPMV_OTHER, x, y, 0));
-  if (ctx->cfg.aug_assembled) return ALFD_OK;
-  double *t = Q.rep ? ctx->g_tlam : ctx->t_lam;                       // replicated patch: the whole multiplier space
-  const double *w = Q.rep ? ctx->g_w : ctx->diag[ALFD_INVW];
-  RC(spmv_m(ctx, Q.Cs, ALFD_T_SPMV_OTHER, x, t, 2, 0.0, w));
-  return spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, t, y, 1, ctx->cfg.gamma);
-}
-
-// z = q(D^-1 Aug_SS) D^-1 r, q = Chebyshev polynomial of degree ml_patch_degree (zero start)
-static int patch_cheb(alfd_ctx *ctx, const double *r, double *z) {
-  alfd_ctx::Patch &Q = ctx->patch;
-  const int degree = ctx->cfg.ml_patch_degree;
-  const FusedAug F = patch_fused(ctx);
-  if (fused_ok(ctx, F)) return cheb_fused(ctx, F, degree, ctx->cfg.ml_patch_ratio, r, z, nullptr, false);
-  const double lmax = Q.lmax, lmin = lmax / ctx->cfg.ml_patch_ratio;
-  const double theta = 0.5 * (lmax + lmin), delta = 0.5 * (lmax - lmin);
-  const double sigma = theta / delta;
-  double rho = 1.0 / sigma;
-  VEC_LAUNCH(cheb_init_kernel, Q.mpad, degree > 1 ? 40 : 32, 1.0 / theta, Q.dinv, r, Q.cd, z, Q.cres, degree > 1 ? 1 : 0);
-  for (int j = 1; j < degree; ++j) {
-    RC(patch_op(ctx, Q.cd, Q.ctmp));
-    const double rho_new = 1.0 / (2.0 * sigma - rho);
-    const double c1 = rho_new * rho, c2 = 2.0 * rho_new / delta;
-    VEC_LAUNCH(cheb_step_kernel, Q.mpad, 64, c1, c2, Q.dinv, Q.ctmp, Q.cres, Q.cd, z);
-    rho = rho_new;
-  }
+  RC(aug_apply(ctx, F, z, L.t));
+  VEC_LAUNCH(sub_from_kernel, F.npad, 24, r, L.t);
+  RC(aug_cheb(ctx, F, sdeg, c.ml_smooth_ratio, L.t, L.r));                   // post-smoothing correction
+  VEC_LAUNCH(axpy_kernel, F.npad, 24, (const double *)nullptr, 0, 1.0, L.r, z);
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
@@ -3927,9 +3883,12 @@ static int ml_apply_rep(alfd_ctx *ctx, const double *r, double *z) {
   const bool pen = !ctx->cfg.aug_assembled;
   const int last = ctx->nblocks - 1;
   const int64_t s0 = Q.soff[ctx->rank];
+  const AugOp F = patch_aug(ctx);
+  const int pdeg = ctx->cfg.ml_patch_degree;
+  const double pratio = ctx->cfg.ml_patch_ratio;
   if (Q.m_loc > 0) hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m_loc, Q.S, r, Q.loc);
   RC(allgather_pieces(ctx, Q.loc, Q.soff, Q.piece, Q.send, Q.stage, Q.rS));
-  RC(patch_cheb(ctx, Q.rS, Q.zS));
+  RC(aug_cheb(ctx, F, pdeg, pratio, Q.rS, Q.zS));
   VEC_LAUNCH(scale_copy_kernel, n0p, 16, 1.0, r, Q.rr);
   RC(spmv_m(ctx, Q.Ats, ALFD_T_SPMV_OTHER, Q.zS, Q.rr, 1, -1.0));
   if (pen) {
@@ -3946,7 +3905,7 @@ static int ml_apply_rep(alfd_ctx *ctx, const double *r, double *z) {
   }
   RC(allgather_pieces(ctx, Q.loc, Q.soff, Q.piece, Q.send, Q.stage, Q.uS));
   VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);
-  RC(patch_cheb(ctx, Q.uS, Q.eS));
+  RC(aug_cheb(ctx, F, pdeg, pratio, Q.uS, Q.eS));
   if (Q.m_loc > 0) hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m_loc, Q.S, Q.eS + s0, z);
   HIPC(hipGetLastError());
   return ALFD_OK;
@@ -3960,8 +3919,11 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   const unsigned gm = (unsigned)((Q.m + 255) / 256);
   const bool pen = !ctx->cfg.aug_assembled;
   const double *w = ctx->diag[ALFD_INVW];
+  const AugOp F = patch_aug(ctx);
+  const int pdeg = ctx->cfg.ml_patch_degree;
+  const double pratio = ctx->cfg.ml_patch_ratio;
   hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, r, Q.rS);
-  RC(patch_cheb(ctx, Q.rS, Q.zS));
+  RC(aug_cheb(ctx, F, pdeg, pratio, Q.rS, Q.zS));
   VEC_LAUNCH(scale_copy_kernel, n0p, 16, 1.0, r, Q.rr);                           // rr = r (a blit copy costs 10x this kernel)
   RC(spmv_m(ctx, Q.Ats, ALFD_T_SPMV_OTHER, Q.zS, Q.rr, 1, -1.0));                 // rr -= A[:,S] zS
   if (pen) {
@@ -3971,17 +3933,16 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   RC(ml_cycle(ctx, 0, Q.rr, z));
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.zS, z);
   RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));                           // (Aug z) on S
-  const FusedAug F = patch_fused(ctx);
   if (fused_ok(ctx, F)) {
     RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
-    RC(fused_correct(ctx, F, ctx->cfg.ml_patch_degree, ctx->cfg.ml_patch_ratio, Q.rS, Q.uS, Q.eS, nullptr));
+    RC(fused_correct(ctx, F, pdeg, pratio, Q.rS, Q.uS, Q.eS, nullptr));
   } else {
     if (pen) {
       RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
       RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
     }
     VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);                          // uS = r_S - (Aug z)_S
-    RC(patch_cheb(ctx, Q.uS, Q.eS));
+    RC(aug_cheb(ctx, F, pdeg, pratio, Q.uS, Q.eS));
   }
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.eS, z);
   HIPC(hipGetLastError());
@@ -4072,9 +4033,7 @@ static void extract_host(const HostCsr &A, const std::vector<int32_t> &rows, con
   for (; next <= out.nrows; ++next) out.rp[next] = (int64_t)out.col.size();
 }
 
-static int upload_level(alfd_ctx *ctx, DevCsr &dst, const HostCsr &h);
 static int upload_level_part(alfd_ctx *ctx, DevCsr &dst, const HostCsr &h, const int64_t *col_offsets, bool local_only);
-static int level_op(alfd_ctx *ctx, int l, const double *x, double *y);
 
 // A CSR matrix in plain device arrays (intermediate products of the Galerkin setup)
 struct DevRawCsr {
@@ -4258,17 +4217,8 @@ static int patch_setup(alfd_ctx *ctx, const HostCsr *A_full, const HostCsr &C, c
   double *v = Q.rS, *wv = Q.zS;
   hipLaunchKernelGGL(hash_vector_kernel, dim3(gm), dim3(256), 0, ctx->stream, m, (int64_t)0, v);
   double lam = 0;
-  for (int it = 0; it < c.cheb_power_its; ++it) {
-    RC(dot_async(ctx, Q.mpad, v, v, S_TMP));
-    RC(read_scalars(ctx, S_TMP, 1));
-    VEC_LAUNCH(scale_kernel, Q.mpad, 16, (const double *)nullptr, 0, 0, 1.0 / std::sqrt(ctx->sc_host[S_TMP]), v);
-    RC(patch_op(ctx, v, wv));
-    VEC_LAUNCH(pmul_scale_kernel, Q.mpad, 24, 1.0, Q.dinv, wv, wv);
-    RC(dot_async(ctx, Q.mpad, wv, wv, S_TMP));
-    RC(read_scalars(ctx, S_TMP, 1));
-    lam = std::sqrt(ctx->sc_host[S_TMP]);
-    std::swap(v, wv);
-  }
+  const AugOp F = patch_aug(ctx);
+  RC(power_lambda(ctx, Q.mpad, Q.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
   Q.lmax = lam * c.cheb_safety;
   HIPC(hipMemsetAsync(Q.rS, 0, Q.mpad * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(Q.zS, 0, Q.mpad * sizeof(double), ctx->stream));
@@ -4938,9 +4888,6 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
   return ALFD_OK;
 }
 
-static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, const HostCsr &Ct, const std::vector<double> &w);
-static int patch_setup_rep(alfd_ctx *ctx);
-
 // The interface patch of a partitioned context: S is split by row ownership, the patch operators are gathered whole on
 // every rank (they are small), the polynomial runs redundantly; see ml_apply_rep.
 static int patch_setup_rep(alfd_ctx *ctx) {
@@ -5043,28 +4990,14 @@ static int patch_setup_rep(alfd_ctx *ctx) {
   if (Q.m_loc) hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m_loc, Q.S, ctx->dinv_aug, Q.loc);
   RC(allgather_pieces(ctx, Q.loc, Q.soff, Q.piece, Q.send, Q.stage, Q.dinv));
   // lambda_max(D^-1 Aug_SS) on the replicated patch: plain reductions, the same on every rank
-  ctx->dots_replicated = true;
   double *v = Q.rS, *wv = Q.zS;
   hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, m, (int64_t)0, v);
   double lam = 0;
-  int rc = ALFD_OK;
-  for (int it = 0; it < c.cheb_power_its && rc == ALFD_OK; ++it) {
-    auto step = [&]() -> int {
-      RC(dot_async(ctx, Q.mpad, v, v, S_TMP));
-      RC(read_scalars(ctx, S_TMP, 1));
-      VEC_LAUNCH(scale_kernel, Q.mpad, 16, (const double *)nullptr, 0, 0, 1.0 / std::sqrt(ctx->sc_host[S_TMP]), v);
-      RC(patch_op(ctx, v, wv));
-      VEC_LAUNCH(pmul_scale_kernel, Q.mpad, 24, 1.0, Q.dinv, wv, wv);
-      RC(dot_async(ctx, Q.mpad, wv, wv, S_TMP));
-      RC(read_scalars(ctx, S_TMP, 1));
-      lam = std::sqrt(ctx->sc_host[S_TMP]);
-      std::swap(v, wv);
-      return ALFD_OK;
-    };
-    rc = step();
+  {
+    ReplicatedDots rd(ctx);
+    const AugOp F = patch_aug(ctx);
+    RC(power_lambda(ctx, Q.mpad, Q.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
   }
-  ctx->dots_replicated = false;
-  if (rc != ALFD_OK) return rc;
   Q.lmax = lam * c.cheb_safety;
   HIPC(hipMemsetAsync(Q.rS, 0, Q.mpad * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(Q.zS, 0, Q.mpad * sizeof(double), ctx->stream));
@@ -5245,27 +5178,17 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
     {
       // diagonal and lambda_max on the replicated operator: plain (single-rank) reductions, the same on every rank
       PhaseClock pl(ctx, ALFD_SETUP_ML_LAMBDA);
-      ctx->dots_replicated = true;
+      ReplicatedDots rd(ctx);
       double *w_save = ctx->diag[ALFD_INVW];
       ctx->diag[ALFD_INVW] = ctx->g_w;        // diag_plus_m reads the weight through the slot
       const int rc = diag_plus_m(ctx, L.gA, L.gCt, c.aug_assembled ? 0.0 : c.gamma, L.gn, L.gdinv);
       ctx->diag[ALFD_INVW] = w_save;
-      if (rc != ALFD_OK) return ctx->dots_replicated = false, rc;
+      if (rc != ALFD_OK) return rc;
       double *v = L.gt, *wv = L.gr;
       hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((L.gn + 255) / 256)), dim3(256), 0, ctx->stream, L.gn, (int64_t)0, v);
       double lam = 0;
-      for (int it = 0; it < c.cheb_power_its; ++it) {
-        RC(dot_async(ctx, L.gnpad, v, v, S_TMP));
-        RC(read_scalars(ctx, S_TMP, 1));
-        VEC_LAUNCH(scale_kernel, L.gnpad, 16, (const double *)nullptr, 0, 0, 1.0 / std::sqrt(ctx->sc_host[S_TMP]), v);
-        RC(level_op_rep(ctx, l, v, wv));
-        VEC_LAUNCH(pmul_scale_kernel, L.gnpad, 24, 1.0, L.gdinv, wv, wv);
-        RC(dot_async(ctx, L.gnpad, wv, wv, S_TMP));
-        RC(read_scalars(ctx, S_TMP, 1));
-        lam = std::sqrt(ctx->sc_host[S_TMP]);
-        std::swap(v, wv);
-      }
-      ctx->dots_replicated = false;
+      const AugOp F = level_view(ctx, l).op;
+      RC(power_lambda(ctx, L.gnpad, L.gdinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
       L.lmax = lam * c.cheb_safety;
       HIPC(hipMemsetAsync(L.gt, 0, L.gnpad * sizeof(double), ctx->stream));
       HIPC(hipMemsetAsync(L.gr, 0, L.gnpad * sizeof(double), ctx->stream));
@@ -5313,6 +5236,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
 
 static int ml_setup(alfd_ctx *ctx) {
   const alfd_config &c = ctx->cfg;
+  ctx->dots_replicated = false;   // the Krylov dots reduce across ranks, whatever an earlier setup left behind
   if (c.ml_smooth_degree < 1 || c.ml_coarse_degree < 1 || !(c.ml_smooth_ratio > 1.0) || !(c.ml_coarse_ratio > 1.0))
     return ctx->err = "bad multilevel parameters", ALFD_E_INVALID;
   // before the dispatch to the replicated setup: a ratio <= 1 (or NaN) makes delta <= 0 and the patch polynomial NaN
@@ -5413,18 +5337,8 @@ static int ml_setup(alfd_ctx *ctx) {
         hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
                            off[l][rk], v);
       double lam = 0;
-      for (int it = 0; it < c.cheb_power_its; ++it) {
-        RC(dot_async(ctx, L.npad, v, v, S_TMP));
-        RC(read_scalars(ctx, S_TMP, 1));
-        VEC_LAUNCH(scale_kernel, L.npad, 16, (const double *)nullptr, 0, 0,
-                   1.0 / std::sqrt(ctx->sc_host[S_TMP]), v);
-        RC(level_op(ctx, l, v, wv));
-        VEC_LAUNCH(pmul_scale_kernel, L.npad, 24, 1.0, L.dinv, wv, wv);
-        RC(dot_async(ctx, L.npad, wv, wv, S_TMP));
-        RC(read_scalars(ctx, S_TMP, 1));
-        lam = std::sqrt(ctx->sc_host[S_TMP]);
-        std::swap(v, wv);
-      }
+      const AugOp F = level_view(ctx, l).op;
+      RC(power_lambda(ctx, L.npad, L.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
       L.lmax = lam * c.cheb_safety;
       HIPC(hipMemsetAsync(L.t, 0, L.npad * sizeof(double), ctx->stream));
       HIPC(hipMemsetAsync(L.r, 0, L.npad * sizeof(double), ctx->stream));

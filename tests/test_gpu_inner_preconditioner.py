@@ -244,8 +244,8 @@ def _rank_context(group, rank, plan, glevels, full, cfg, n, ref):
 
 
 def test_two_ranks_match_one(built):
-    """(i): the collective call on two in-process ranks (levels >= 1 and the patch replicated: ml_cycle_rep,
-    patch_setup_rep) gathers to the single-rank result within HIST_RTOL -- not bit-equal, the level-0 reductions of the
+    """(i): the collective call on two in-process ranks (levels >= 1 and the patch replicated: ml_cycle below
+    ml_rep_level, patch_setup_rep) gathers to the single-rank result within HIST_RTOL -- not bit-equal, the level-0 reductions of the
     power iterations are summed in rank order."""
     n, refine = 8, 1
     full, cfg = cases.case("stokes3d_gmg_patch")
