@@ -5,13 +5,15 @@ pinned (needs a deal.II install, which this repository's pi
 
     python bench/reference_cmake/replay.py run/stokes_immersed_boundary.alfd [--reference-log run/stokes.log]
                                            [--inner-prec multilevel|sa-multilevel|chebyshev] [--support-points points.npy]
+                                           [--sa-drop-tolerance TAU] [--sa-max-row-entries K]
 
 A dump with grad_div_in_A = 0 (`Grad-div stabilization = false`) replays with the identity inner preconditioner, the
 reference's, or with --inner-prec chebyshev; never multilevel.
 
 The inner preconditioner differs from the reference's by construction (Trilinos ML there; here the algebraic aggregation
 of alfd_build_aggregates on the dumped A, or geometric transfers when the caller supplies them; sa-multilevel builds
-ML's algorithm, smoothed aggregation, from the dumped operators with alfd_build_smoothed_aggregation), so OUTER counts
+ML's algorithm, smoothed aggregation, from the dumped operators with alfd_build_smoothed_aggregation;
+--sa-drop-tolerance / --sa-max-row-entries truncate its prolongators as ML does, e.g. --sa-max-row-entries 4), so OUTER counts
 are the comparable quantity: both inner solvers stop at the same absolute tolerance (parameters_stokes_3d.prm:23-24)."""
 import argparse
 import json
@@ -31,6 +33,10 @@ def main():
     ap.add_argument("--inner-max", type=int, default=0, help="override the inner CG cap of the dump (0 = keep)")
     ap.add_argument("--support-points", help=".npy with one support point per row of block 0: front-end renumbering + mesh bricks")
     ap.add_argument("--block-size", type=int, default=0, help="components per node of block 0 (default: 3 for Stokes dumps, else 1)")
+    ap.add_argument("--sa-drop-tolerance", type=float, default=0.0,
+                    help="sa-multilevel: drop the entries of P below this fraction of their row's maximum (0 = none)")
+    ap.add_argument("--sa-max-row-entries", type=int, default=0,
+                    help="sa-multilevel: keep at most this many entries per row of P (0 = no cap)")
     args = ap.parse_args()
     import numpy as np
     from fictitious_domain_al_preconditioners_amd import _abi, opfile, solver
@@ -75,9 +81,15 @@ def main():
         ctx.configure(cfg)
         if args.inner_prec == "sa-multilevel":
             levels, omega = ctx.build_smoothed_aggregation(block_size=bs, threshold=0.02, max_aggregate_nodes=8,
-                                                           damping=4.0 / 3.0, min_coarse=3000, return_omega=True)
+                                                           damping=4.0 / 3.0, min_coarse=3000, return_omega=True,
+                                                           drop_tolerance=args.sa_drop_tolerance,
+                                                           max_row_entries=args.sa_max_row_entries)
+            cut = ""
+            if args.sa_drop_tolerance or args.sa_max_row_entries:
+                cut = (f", truncated (drop tolerance {args.sa_drop_tolerance}, at most {args.sa_max_row_entries} per row): "
+                       f"nnz of P {[int(P.nnz) for P, _ in levels]}")
             print(f"smoothed aggregation (ML's threshold 0.02 and damping 4/3, utilities.h:304-317): levels "
-                  f"{[nc for _, nc in levels]}, omega {[float(o) for o in omega]}")
+                  f"{[nc for _, nc in levels]}, omega {[float(o) for o in omega]}{cut}")
         else:
             levels = ctx.build_aggregates(block_size=bs, threshold=0.02, max_aggregate_nodes=8, min_coarse=3000)
             print(f"algebraic aggregation (ML's threshold 0.02, utilities.h:312): levels {[nc for _, nc in levels]}")

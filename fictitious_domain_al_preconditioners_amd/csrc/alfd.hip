@@ -4791,6 +4791,66 @@ static void sa_rows_host(const HostCsr &A, const std::vector<int32_t> &agg, int6
   }
 }
 
+// The truncation rule of the smoothed prolongator on the host (alfd_host_truncate_prolongator and the overflow fallback
+// of sa_truncated_prolongator_kernel, same bits; canonical order: DESIGN.md section 4).  P has sorted rows, every row
+// with agg[i] >= 0 holds column agg[i]; rows with agg[i] < 0 come out empty.
+static void sa_truncate_host(const HostCsr &P, const std::vector<int32_t> &agg, int bs, double tau, int cap, HostCsr &T) {
+  const int64_t n = P.nrows;
+  T.nrows = n;
+  T.ncols = P.ncols;
+  T.rp.assign(n + 1, 0);
+  T.col.clear();
+  T.val.clear();
+  std::vector<char> keep;
+  std::vector<double> v;
+  std::vector<int64_t> order;
+  for (int64_t i = 0; i < n; ++i) {
+    const int32_t gi = agg[i];
+    const int64_t e0 = P.rp[i], len = P.rp[i + 1] - e0;
+    if (gi >= 0 && len > 0) {
+      const int32_t *J = P.col.data() + e0;
+      v.assign(P.val.begin() + e0, P.val.begin() + e0 + len);
+      double m = 0.0;
+      for (int64_t t = 0; t < len; ++t)
+        if (std::fabs(v[t]) > m) m = std::fabs(v[t]);
+      const double thr = tau * m;
+      keep.assign(len, 0);
+      int64_t nk = 0;
+      for (int64_t t = 0; t < len; ++t) nk += keep[t] = (!(std::fabs(v[t]) < thr) || J[t] == gi) ? 1 : 0;
+      if (cap > 0 && nk > cap) {
+        order.clear();
+        for (int64_t t = 0; t < len; ++t)
+          if (keep[t] && J[t] != gi) order.push_back(t);
+        std::stable_sort(order.begin(), order.end(),
+                         [&](int64_t a, int64_t b) { return std::fabs(v[a]) > std::fabs(v[b]); });
+        for (size_t q = (size_t)(cap - 1); q < order.size(); ++q) keep[order[q]] = 0;
+        nk = cap;
+      }
+      if (nk < len)
+        for (int c = 0; c < bs; ++c) {
+          double t = 0.0, best = -1.0;
+          int64_t at = -1, nd = 0;
+          for (int64_t u = 0; u < len; ++u) {
+            if (J[u] % bs != c) continue;
+            if (keep[u]) {
+              if (std::fabs(P.val[e0 + u]) > best) best = std::fabs(P.val[e0 + u]), at = u;
+            } else {
+              t = t + P.val[e0 + u];
+              ++nd;
+            }
+          }
+          if (nd > 0 && at >= 0) v[at] = v[at] + t;
+        }
+      for (int64_t t = 0; t < len; ++t)
+        if (keep[t]) {
+          T.col.push_back(J[t]);
+          T.val.push_back(v[t]);
+        }
+    }
+    T.rp[i + 1] = (int64_t)T.col.size();
+  }
+}
+
 // f_i = -omega / d_i (rows without an aggregate: 0, never read)
 static void sa_factors(const std::vector<int32_t> &agg, const std::vector<double> &d, double omega, std::vector<double> &f) {
   f.assign(agg.size(), 0.0);
@@ -4812,11 +4872,15 @@ static int sa_penalty_rows(alfd_ctx *ctx, const SaPenalty &pen, const std::vecto
   return ALFD_OK;
 }
 
-// P on the device (sa_prolongator_kernel); *fits = false when a row has more distinct coarse ids than the kernel holds
+// P on the device; *fits = false when a row has more distinct coarse ids than the kernel holds.  tau == 0 and cap == 0:
+// sa_prolongator_kernel; otherwise sa_truncated_prolongator_kernel, whose counts, row pointer and arrays hold the kept
+// entries only (the untruncated P exists nowhere).
 static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector<int32_t> &agg, int64_t nc,
-                              const std::vector<double> &f, const HostCsr &Q, HostCsr &P, bool *fits) {
+                              const std::vector<double> &f, const HostCsr &Q, int bs, double tau, int cap, HostCsr &P,
+                              bool *fits) {
   *fits = false;
   const int64_t n = A.nrows;
+  const bool trunc = tau != 0.0 || cap != 0;
   DevRawCsr dA, dQ, dP;
   RC(upload_raw(ctx, A, dA));
   const bool pen = !Q.rp.empty();
@@ -4848,8 +4912,15 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
   if ((e = hipMemsetAsync(ovf, 0, sizeof(int32_t), ctx->stream)) != hipSuccess) return fail(e);
   const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(n, 256 * 64));
   const int64_t *qrp = pen ? dQ.rp : nullptr;
-  hipLaunchKernelGGL(sa_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val, d_agg, d_f,
-                     qrp, dQ.col, dQ.val, 0, counts, (const int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, ovf);
+  auto launch = [&](int pass, const int64_t *prp, int32_t *pcol, double *pval) {
+    if (trunc)
+      hipLaunchKernelGGL(sa_truncated_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val,
+                         d_agg, d_f, qrp, dQ.col, dQ.val, bs, tau, cap, pass, counts, prp, pcol, pval, ovf);
+    else
+      hipLaunchKernelGGL(sa_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val, d_agg, d_f,
+                         qrp, dQ.col, dQ.val, pass, counts, prp, pcol, pval, ovf);
+  };
+  launch(0, nullptr, nullptr, nullptr);
   if ((e = hipGetLastError()) != hipSuccess) return fail(e);
   std::vector<int32_t> hc(n);
   int32_t hovf = 0;
@@ -4873,8 +4944,7 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
     return fail(e);
   if ((e = hipMalloc((void **)&dP.col, std::max<int64_t>(nnz, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
   if ((e = hipMalloc((void **)&dP.val, std::max<int64_t>(nnz, 1) * sizeof(double))) != hipSuccess) return fail(e);
-  hipLaunchKernelGGL(sa_prolongator_kernel, dim3(grid), dim3(64), 0, ctx->stream, n, dA.rp, dA.col, dA.val, d_agg, d_f,
-                     qrp, dQ.col, dQ.val, 1, counts, (const int64_t *)dP.rp, dP.col, dP.val, ovf);
+  launch(1, dP.rp, dP.col, dP.val);
   if ((e = hipGetLastError()) != hipSuccess) return fail(e);
   P.col.resize(nnz);
   P.val.resize(nnz);
@@ -6206,9 +6276,10 @@ int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacit
   return ALFD_OK;
 }
 
-int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
-                                    double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
-                                    double *omega_out) {
+// alfd_build_smoothed_aggregation (tau = 0, cap = 0: nothing is truncated) and alfd_build_smoothed_aggregation_truncated
+static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
+                                      double damping, double tau, int32_t cap, int64_t min_coarse, int32_t max_levels,
+                                      int32_t *levels_out, double *omega_out) {
   CHECK_CTX();
   if (ctx->nranks > 1) return ctx->err = "alfd_build_smoothed_aggregation is single-rank", ALFD_E_UNSUPPORTED;
   if (ctx->configured && gd_nested(ctx))
@@ -6217,6 +6288,12 @@ int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double t
   if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
       !(damping > 0.0) || !std::isfinite(damping))
     return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
+  if (!(tau >= 0.0) || !(tau < 1.0) || cap < 0) {
+    for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+    ctx->is_setup = false;
+    return ctx->err = "alfd_build_smoothed_aggregation_truncated: drop_tolerance must be in [0, 1), max_row_entries >= 0",
+           ALFD_E_INVALID;
+  }
   if (ctx->mat[ALFD_A].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
   if (ctx->mat[ALFD_A].nrows != ctx->mat[ALFD_A].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
   if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
@@ -6261,8 +6338,15 @@ int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double t
     sa_factors(agg, d, omega, f);
     RC(sa_penalty_rows(ctx, pen, agg, nc, Q));
     bool fits = false;
-    RC(sa_prolongator_dev(ctx, A, agg, nc, f, Q, P, &fits));
-    if (!fits) sa_rows_host(A, agg, nc, f, use_pen ? &Q : nullptr, P);
+    RC(sa_prolongator_dev(ctx, A, agg, nc, f, Q, block_size, tau, cap, P, &fits));
+    if (!fits) {
+      sa_rows_host(A, agg, nc, f, use_pen ? &Q : nullptr, P);
+      if (tau != 0.0 || cap != 0) {
+        HostCsr T;
+        sa_truncate_host(P, agg, block_size, tau, cap, T);
+        std::swap(P, T);
+      }
+    }
     Q = HostCsr();
     if (omega_out) omega_out[nlev] = omega;
     ctx->ml_agg[nlev] = agg;
@@ -6285,6 +6369,21 @@ int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double t
   if (nlev == 0) return ctx->err = "algebraic aggregation found nothing to coarsen", ALFD_E_INVALID;
   if (levels_out) *levels_out = nlev;
   return ALFD_OK;
+}
+
+int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
+                                    double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
+                                    double *omega_out) {
+  return build_smoothed_aggregation(ctx, block_size, threshold, max_aggregate_nodes, damping, 0.0, 0, min_coarse,
+                                    max_levels, levels_out, omega_out);
+}
+
+int alfd_build_smoothed_aggregation_truncated(alfd_ctx_t ctx, int32_t block_size, double threshold,
+                                              int32_t max_aggregate_nodes, double damping, double drop_tolerance,
+                                              int32_t max_row_entries, int64_t min_coarse, int32_t max_levels,
+                                              int32_t *levels_out, double *omega_out) {
+  return build_smoothed_aggregation(ctx, block_size, threshold, max_aggregate_nodes, damping, drop_tolerance,
+                                    max_row_entries, min_coarse, max_levels, levels_out, omega_out);
 }
 
 int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
@@ -6348,6 +6447,39 @@ int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const 
     if (capacity < P.nnz()) return ALFD_E_INVALID;
     if (p_col) std::copy(P.col.begin(), P.col.end(), p_col);
     if (p_val) std::copy(P.val.begin(), P.val.end(), p_val);
+  }
+  return ALFD_OK;
+}
+
+int alfd_host_truncate_prolongator(int64_t nrows, int64_t n_coarse, const int64_t *p_row_ptr, const int32_t *p_col,
+                                   const double *p_val, const int32_t *agg, int32_t block_size, double drop_tolerance,
+                                   int32_t max_row_entries, int64_t *out_row_ptr, int32_t *out_col, double *out_val,
+                                   int64_t capacity, int64_t *nnz) {
+  if (nrows < 1 || n_coarse < 1 || n_coarse > INT32_MAX || !p_row_ptr || !p_col || !p_val || !agg || !nnz ||
+      block_size < 1 || !(drop_tolerance >= 0.0) || !(drop_tolerance < 1.0) || max_row_entries < 0 || p_row_ptr[0] != 0)
+    return ALFD_E_INVALID;
+  for (int64_t i = 0; i < nrows; ++i) {
+    if (p_row_ptr[i + 1] < p_row_ptr[i] || agg[i] < -1 || agg[i] >= n_coarse) return ALFD_E_INVALID;
+    bool has = agg[i] < 0;
+    for (int64_t e = p_row_ptr[i]; e < p_row_ptr[i + 1]; ++e) {
+      if (p_col[e] < 0 || p_col[e] >= n_coarse || (e > p_row_ptr[i] && p_col[e] <= p_col[e - 1])) return ALFD_E_INVALID;
+      has = has || p_col[e] == agg[i];
+    }
+    if (!has) return ALFD_E_INVALID;
+  }
+  HostCsr P, T;
+  P.nrows = nrows;
+  P.ncols = n_coarse;
+  P.rp.assign(p_row_ptr, p_row_ptr + nrows + 1);
+  P.col.assign(p_col, p_col + P.rp[nrows]);
+  P.val.assign(p_val, p_val + P.rp[nrows]);
+  sa_truncate_host(P, std::vector<int32_t>(agg, agg + nrows), block_size, drop_tolerance, max_row_entries, T);
+  *nnz = T.nnz();
+  if (out_row_ptr) std::copy(T.rp.begin(), T.rp.end(), out_row_ptr);
+  if (out_col || out_val) {
+    if (capacity < T.nnz()) return ALFD_E_INVALID;
+    if (out_col) std::copy(T.col.begin(), T.col.end(), out_col);
+    if (out_val) std::copy(T.val.begin(), T.val.end(), out_val);
   }
   return ALFD_OK;
 }

@@ -1823,6 +1823,202 @@ __global__ __launch_bounds__(64) void sa_prolongator_kernel(
   }
 }
 
+// ---------------------------------------------------------------------------------------------------
+// The truncated smoothed-aggregation prolongator (alfd_build_smoothed_aggregation_truncated): the row of
+// sa_prolongator_kernel is computed into LDS and truncated there, so the untruncated P is never stored; counts[] and
+// the row pointer hold KEPT entries.  Candidates (J ascending, p_J with the bits of sa_prolongator_kernel), g = agg[i],
+// tau = drop tolerance, cap = most entries per row (0: no cap), component of J = J mod bs.  Canonical rule (DESIGN.md
+// section 4):
+//   m = max |p_J|;  K0 = {J : |p_J| >= tau * m} U {g};
+//   |K0| > cap > 0:  K = {g} U the first cap - 1 of K0 \ {g} in the order (|p| descending, J ascending), found by
+//                    counting rank (every candidate counts the candidates that precede it: no data-dependent sort);
+//   per component c with dropped candidates D_c and kept ones:  t = 0.0; t = t + p_J over D_c, J ascending;  the kept
+//                    entry of component c that is first in that order (untruncated values) becomes p + t;
+//   the row is K, J ascending.
+// Both passes compute the whole row: pass 0 counts the kept entries, pass 1 lumps, compacts and stores.  A row has at
+// most kSaMaxOut candidates (overflow[0] otherwise: sa_rows_host, then the host truncation, same bits).
+// LDS: 20.6 KiB per workgroup (the 16 KiB of sa_prolongator_kernel, the row's values and its keep flags).
+__global__ __launch_bounds__(64) void sa_truncated_prolongator_kernel(
+    int64_t nrows, const int64_t *__restrict__ arp, const int32_t *__restrict__ acol, const double *__restrict__ aval,
+    const int32_t *__restrict__ agg, const double *__restrict__ f, const int64_t *__restrict__ qrp,
+    const int32_t *__restrict__ qcol, const double *__restrict__ qval, int bs, double tau, int cap, int pass,
+    int32_t *__restrict__ counts, const int64_t *__restrict__ prp, int32_t *__restrict__ pcol,
+    double *__restrict__ pval, int32_t *__restrict__ overflow) {
+  __shared__ int32_t table[kSaTable];
+  __shared__ int32_t keys[kSaMaxOut];
+  __shared__ int32_t sJ[kSaStage];
+  __shared__ double sv[kSaStage];
+  __shared__ double pv[kSaMaxOut];
+  __shared__ uint8_t keep[kSaMaxOut];
+  __shared__ int32_t cnt;
+  const int lane = threadIdx.x;
+  auto insert = [&](int32_t J) {
+    uint32_t h = ((uint32_t)J * 2654435761u) >> 21;   // 11 bits
+    for (;;) {
+      if (*(volatile int32_t *)&cnt > kSaMaxOut) break;   // overflowing row: stop inserting (reported below)
+      const int32_t old = atomicCAS(&table[h], -1, J);
+      if (old == -1) {
+        atomicAdd(&cnt, 1);
+        break;
+      }
+      if (old == J) break;
+      h = (h + 1) & (kSaTable - 1);
+    }
+  };
+  for (int64_t i = blockIdx.x; i < nrows; i += gridDim.x) {
+    const int32_t gi = agg[i];
+    if (gi < 0) {
+      if (pass == 0 && lane == 0) counts[i] = 0;
+      continue;
+    }
+    const int64_t k0 = arp[i], k1 = arp[i + 1];
+    const int64_t q0 = qrp ? qrp[i] : 0, q1 = qrp ? qrp[i + 1] : 0;
+    for (int s = lane; s < kSaTable; s += 64) table[s] = -1;
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    if (lane == 0) insert(gi);
+    for (int64_t k = k0 + lane; k < k1; k += 64) {
+      const int32_t J = agg[acol[k]];
+      if (J >= 0) insert(J);
+    }
+    for (int64_t q = q0 + lane; q < q1; q += 64) insert(qcol[q]);
+    __syncthreads();
+    const int n = cnt;
+    if (n > kSaMaxOut) {
+      if (lane == 0) overflow[0] = 1;
+      if (pass == 0 && lane == 0) counts[i] = 0;
+      __syncthreads();
+      continue;
+    }
+    // compact, pad to a power of two with INT_MAX, bitonic sort (n2 <= kSaMaxOut)
+    int n2 = 64;
+    while (n2 < n) n2 <<= 1;
+    __syncthreads();
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    for (int s = lane; s < kSaTable; s += 64) {
+      const int32_t J = table[s];
+      if (J != -1) keys[atomicAdd(&cnt, 1)] = J;
+    }
+    __syncthreads();
+    for (int s = n + lane; s < n2; s += 64) keys[s] = 0x7fffffff;
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = lane; t < n2 / 2; t += 64) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool up = (lo & size) == 0;
+          const int32_t a = keys[lo], b = keys[hi];
+          if ((a > b) == up) {
+            keys[lo] = b;
+            keys[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    // the candidates' values, in sa_prolongator_kernel's order, and the row maximum
+    const double fi = f[i];
+    double m = 0.0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+      const int t = t0 + lane;
+      const int32_t J = t < n ? keys[t] : -2;
+      double s = 0.0;
+      for (int64_t kb = k0; kb < k1; kb += kSaStage) {
+        const int ms = (int)(k1 - kb < kSaStage ? k1 - kb : kSaStage);
+        __syncthreads();
+        for (int e = lane; e < ms; e += 64) {
+          sJ[e] = agg[acol[kb + e]];
+          sv[e] = aval[kb + e];
+        }
+        __syncthreads();
+        for (int e = 0; e < ms; ++e)
+          if (sJ[e] == J) s = s + sv[e];
+      }
+      for (int64_t q = q0; q < q1; ++q)
+        if (qcol[q] == J) s = s + qval[q];
+      if (t < n) {
+        const double p = fma(fi, s, J == gi ? 1.0 : 0.0);
+        pv[t] = p;
+        if (fabs(p) > m) m = fabs(p);
+      }
+    }
+    for (int o = 32; o > 0; o >>= 1) {
+      const double u = __shfl_xor(m, o);
+      if (u > m) m = u;
+    }
+    const double thr = tau * m;
+    int nk = 0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+      const int t = t0 + lane;
+      const bool k = t < n && (!(fabs(pv[t]) < thr) || keys[t] == gi);
+      if (t < n) keep[t] = (uint8_t)(k ? 1 : 0);
+      nk += __popcll(__ballot(k));
+    }
+    __syncthreads();
+    if (cap > 0 && nk > cap) {
+      // counting rank among K0 \ {g} under (|p| descending, J ascending); lane t decides candidates t, t + 64, ...
+      uint32_t mine = 0;   // bit j: candidate lane + 64 j stays
+      for (int j = 0; lane + 64 * j < n; ++j) {
+        const int t = lane + 64 * j;
+        if (!keep[t]) continue;
+        if (keys[t] == gi) {
+          mine |= 1u << j;
+          continue;
+        }
+        const double a = fabs(pv[t]);
+        int rank = 0;
+        for (int u = 0; u < n; ++u) {
+          const double b = fabs(pv[u]);
+          rank += (keep[u] && keys[u] != gi && (b > a || (b == a && u < t))) ? 1 : 0;
+        }
+        if (rank < cap - 1) mine |= 1u << j;
+      }
+      __syncthreads();
+      for (int j = 0; lane + 64 * j < n; ++j) keep[lane + 64 * j] = (uint8_t)((mine >> j) & 1u);
+      nk = cap;
+      __syncthreads();
+    }
+    if (pass == 0) {
+      if (lane == 0) counts[i] = nk;
+      __syncthreads();
+      continue;
+    }
+    // lump what was dropped: one lane per component walks the candidates in ascending order
+    if (nk < n) {
+      for (int c = lane; c < bs; c += 64) {
+        double t = 0.0, best = -1.0;
+        int at = -1, nd = 0;
+        for (int u = 0; u < n; ++u) {
+          if (keys[u] % bs != c) continue;
+          if (keep[u]) {
+            if (fabs(pv[u]) > best) best = fabs(pv[u]), at = u;
+          } else {
+            t = t + pv[u];
+            ++nd;
+          }
+        }
+        if (nd > 0 && at >= 0) pv[at] = pv[at] + t;
+      }
+      __syncthreads();
+    }
+    const int64_t c0 = prp[i];
+    int base = 0;
+    for (int t0 = 0; t0 < n; t0 += 64) {
+      const int t = t0 + lane;
+      const bool k = t < n && keep[t];
+      const unsigned long long mask = __ballot(k);
+      if (k) {
+        const int at = base + __popcll(mask & ((1ull << lane) - 1ull));
+        pcol[c0 + at] = keys[t];
+        pval[c0 + at] = pv[t];
+      }
+      base += __popcll(mask);
+    }
+    __syncthreads();
+  }
+}
+
 // flag[i] = 1 if row i of the CSR matrix has a column j with mark[j] >= 0 (rows of A that reach the interface patch)
 __global__ void rows_touching_kernel(int64_t nrows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
                                      const int32_t *__restrict__ mark, uint8_t *__restrict__ flag) {

@@ -35,6 +35,7 @@ ABI_SYMBOLS = [
     "alfd_host_row_blocks_from_points", "alfd_host_stream_plan_short", "alfd_set_prolongator", "alfd_set_controls", "alfd_get_timing_streamed", "alfd_get_setup_seconds",
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
+    "alfd_build_smoothed_aggregation_truncated", "alfd_host_truncate_prolongator",
     "alfd_inner_prec_apply",
 ]
 
@@ -110,6 +111,10 @@ def load_library():
         "alfd_get_aggregates": (C.c_int, [vp, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_host_aggregate_level": (C.c_int, [i64, vp, vp, vp, i32, dbl, i32, vp, C.POINTER(i64)]),
         "alfd_build_smoothed_aggregation": (C.c_int, [vp, i32, dbl, i32, dbl, i64, i32, C.POINTER(i32), vp]),
+        "alfd_build_smoothed_aggregation_truncated": (C.c_int, [vp, i32, dbl, i32, dbl, dbl, i32, i64, i32,
+                                                                C.POINTER(i32), vp]),
+        "alfd_host_truncate_prolongator": (C.c_int, [i64, i64, vp, vp, vp, vp, i32, dbl, i32, vp, vp, vp, i64,
+                                                     C.POINTER(i64)]),
         "alfd_get_prolongator": (C.c_int, [vp, C.c_int, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64),
                                            C.POINTER(i64)]),
         "alfd_host_smoothed_prolongator": (C.c_int, [i64, vp, vp, vp, i64, vp, vp, vp, vp, dbl, vp, i64, dbl,
@@ -234,16 +239,25 @@ class Context:
         return out
 
     def build_smoothed_aggregation(self, block_size=1, threshold=0.02, max_aggregate_nodes=8, damping=4.0 / 3.0,
-                                   min_coarse=600, max_levels=7, return_omega=False):
+                                   min_coarse=600, max_levels=7, return_omega=False, drop_tolerance=0.0,
+                                   max_row_entries=0):
         """Smoothed aggregation from the uploaded operators (alfd_build_smoothed_aggregation): every level's
         prolongator P = P_tent - omega D^-1 Aug P_tent, built on the device.  Upload A (and C / Ct / W^-1 and
-        configure an AL variant for the penalty term) first.  Returns [(Csr P, n_coarse), ...] -- the list
-        upload_problem and the oracle take; with return_omega also the damping omega of every level."""
+        configure an AL variant for the penalty term) first.  drop_tolerance / max_row_entries other than 0 truncate
+        every row on the device (alfd_build_smoothed_aggregation_truncated: entries below drop_tolerance * the row
+        maximum go, at most max_row_entries stay, the dropped mass is lumped per component).  Returns
+        [(Csr P, n_coarse), ...] -- the list upload_problem and the oracle take; with return_omega also the damping
+        omega of every level."""
         nlev = C.c_int32(0)
         omega = np.zeros(max(max_levels, 8), np.float64)   # ALFD_MAX_LEVELS - 1 entries when max_levels is out of range
-        self._ck(self._lib.alfd_build_smoothed_aggregation(self._h, block_size, threshold, max_aggregate_nodes,
-                                                           damping, min_coarse, max_levels, C.byref(nlev),
-                                                           omega.ctypes.data))
+        if drop_tolerance == 0.0 and max_row_entries == 0:
+            self._ck(self._lib.alfd_build_smoothed_aggregation(self._h, block_size, threshold, max_aggregate_nodes,
+                                                               damping, min_coarse, max_levels, C.byref(nlev),
+                                                               omega.ctypes.data))
+        else:
+            self._ck(self._lib.alfd_build_smoothed_aggregation_truncated(
+                self._h, block_size, threshold, max_aggregate_nodes, damping, drop_tolerance, max_row_entries,
+                min_coarse, max_levels, C.byref(nlev), omega.ctypes.data))
         out = []
         for level in range(nlev.value):
             P = self.prolongator(level)
@@ -524,6 +538,36 @@ def host_smoothed_prolongator(A, agg, n_coarse, omega, Ct=None, w_inv=None, gamm
     if rc != _abi.OK:
         raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
     return Csr(int(A.nrows), int(n_coarse), prp, pcol, pval)
+
+
+def host_truncate_prolongator(P, agg, block_size=1, drop_tolerance=0.0, max_row_entries=0):
+    """Host-only: the truncation rule of Context.build_smoothed_aggregation(drop_tolerance, max_row_entries) applied to
+    a problems.Csr prolongator (alfd_host_truncate_prolongator, the device's bits); agg as for
+    host_smoothed_prolongator.  Returns a problems.Csr."""
+    from .problems import Csr
+    lib = load_library()
+    rp = np.ascontiguousarray(P.row_ptr, np.int64)
+    col = np.ascontiguousarray(P.col, np.int32)
+    val = np.ascontiguousarray(P.val, np.float64)
+    agg = np.ascontiguousarray(agg, np.int32)
+    if agg.size != P.nrows:
+        raise ValueError("agg must have one entry per row of P")
+    orp = np.empty(P.nrows + 1, np.int64)
+    nnz = C.c_int64(0)
+
+    def call(oc, ov, cap):
+        return lib.alfd_host_truncate_prolongator(P.nrows, P.ncols, rp.ctypes.data, col.ctypes.data, val.ctypes.data,
+                                                  agg.ctypes.data, int(block_size), float(drop_tolerance),
+                                                  int(max_row_entries), orp.ctypes.data, oc, ov, cap, C.byref(nnz))
+    rc = call(None, None, 0)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_truncate_prolongator failed")
+    ocol = np.empty(nnz.value, np.int32)
+    oval = np.empty(nnz.value, np.float64)
+    rc = call(ocol.ctypes.data, oval.ctypes.data, ocol.size)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_truncate_prolongator failed")
+    return Csr(int(P.nrows), int(P.ncols), orp, ocol, oval)
 
 
 def host_window_plan(m, lanes=64, value_index=True):

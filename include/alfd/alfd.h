@@ -354,7 +354,8 @@ int alfd_host_aggregate_level(int64_t nrows, const int64_t *row_ptr, const int32
  *   omega_l = damping / lambda, lambda = lambda_max(D^-1 Aug_l) from cheb_power_its steps of power iteration
  *             (the start vector of alfd_setup, no safety factor), D = diag(Aug_l); ML's default damping is 4/3;
  *   P_l     = P_tent - omega_l D^-1 Aug_l P_tent, P_tent the constant modes of agg_l (one per component), its pattern
- *             the structural union (nothing dropped by value -- ML drops small entries), built on the device;
+ *             the structural union, built on the device (nothing is dropped by value here; ML, hypre and MueLu
+ *             truncate the smoothed prolongator: alfd_build_smoothed_aggregation_truncated does);
  *   A_{l+1} = P_l^T A_l P_l, C_{l+1} = C_l P_l.
  * Coarsening stops at <= min_coarse unknowns or max_levels levels.  The levels are stored as alfd_set_prolongator
  * would store them (alfd_setup forms the Galerkin products again), the aggregates as alfd_set_aggregates
@@ -365,7 +366,25 @@ int alfd_host_aggregate_level(int64_t nrows, const int64_t *row_ptr, const int32
 int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
                                     double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
                                     double *omega_out);
-/* The CSR prolongator of a level (built by alfd_build_smoothed_aggregation or set by alfd_set_prolongator):
+/* The same hierarchy with every row of P_l truncated on the device before it is stored (the untruncated P_l exists
+ * nowhere; allocations are sized by kept entries).  For a row i with g = agg_l[i] >= 0 and the entries (J, p_J) of the
+ * untruncated row, drop_tolerance tau in [0, 1) and max_row_entries k >= 0 (0: no cap):
+ *   m = max |p_J|;  K0 = {J : |p_J| >= tau m} U {g};
+ *   if k > 0 and |K0| > k: K = {g} U the first k - 1 members of K0 \ {g} in the order (|p| descending, J ascending),
+ *   else K = K0;
+ *   per component c (= J mod block_size) with dropped entries D_c and kept ones: t = the sum of p_J over D_c, J
+ *   ascending, is added to the kept entry of component c that comes first in that order (so the constant of every
+ *   component that keeps an entry is still reproduced); a component that keeps nothing loses D_c;
+ *   the row is K, J ascending.
+ * omega_l comes from the same power iteration on the untruncated operator; A_{l+1} and C_{l+1} use the truncated P_l.
+ * tau == 0 and k == 0 give alfd_build_smoothed_aggregation bit for bit.  Same contract and error codes; ALFD_E_INVALID
+ * for tau < 0, tau >= 1, tau not finite or k < 0 also clears the aggregates / prolongators set earlier.
+ * Deterministic, bit for bit (selection by counting rank, no ties left open).  Canonical order: DESIGN.md section 4. */
+int alfd_build_smoothed_aggregation_truncated(alfd_ctx_t ctx, int32_t block_size, double threshold,
+                                              int32_t max_aggregate_nodes, double damping, double drop_tolerance,
+                                              int32_t max_row_entries, int64_t min_coarse, int32_t max_levels,
+                                              int32_t *levels_out, double *omega_out);
+/* The CSR prolongator of a level (built by alfd_build_smoothed_aggregation[_truncated] or set by alfd_set_prolongator):
  * row_ptr[n_fine + 1], col / val [capacity >= nnz].  NULL arrays query the sizes; ALFD_E_INVALID for a level
  * without a CSR prolongator. */
 int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
@@ -379,6 +398,16 @@ int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const 
                                    int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
                                    const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
                                    int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz);
+/* Host-only (no device, no context): the truncation rule of alfd_build_smoothed_aggregation_truncated applied to a CSR
+ * prolongator P (nrows x n_coarse, rows sorted, e.g. from alfd_host_smoothed_prolongator) with the aggregates
+ * agg[nrows] (-1: the row comes out empty), same bits as the device.  Two calls as alfd_host_smoothed_prolongator:
+ * out_col == out_val == NULL returns *nnz (and out_row_ptr[nrows + 1] if given), then arrays with capacity >= nnz.
+ * ALFD_E_INVALID: drop_tolerance < 0, >= 1 or not finite, max_row_entries < 0, block_size < 1, a column outside
+ * [0, n_coarse), a row not strictly ascending, agg out of range, a row with agg[i] >= 0 without the column agg[i]. */
+int alfd_host_truncate_prolongator(int64_t nrows, int64_t n_coarse, const int64_t *p_row_ptr, const int32_t *p_col,
+                                   const double *p_val, const int32_t *agg, int32_t block_size, double drop_tolerance,
+                                   int32_t max_row_entries, int64_t *out_row_ptr, int32_t *out_col, double *out_val,
+                                   int64_t capacity, int64_t *nnz);
 int alfd_configure(alfd_ctx_t ctx, const alfd_config *cfg);
 /* New stop rules for the following solves WITHOUT a new alfd_setup (alfd_configure invalidates the setup): the
  * reference's SolverControl objects are plain members that a caller may change between two solve() calls

@@ -198,14 +198,22 @@ class System {
   }
   // Smoothed-aggregation hierarchy built by the library from the uploaded operators (ML's algorithm,
   // utilities.h:304-317; alfd_build_smoothed_aggregation): after set_matrix / configure, before setup.
-  // Returns the number of levels; omega (optional) receives the damping of every level.
+  // Returns the number of levels; omega (optional) receives the damping of every level.  drop_tolerance /
+  // max_row_entries other than 0 truncate every row of the prolongators on the device
+  // (alfd_build_smoothed_aggregation_truncated: e.g. 0, 4 keeps the iteration counts at about one eighth of the entries).
   int build_smoothed_aggregation(int32_t block_size = 1, double threshold = 0.02, int32_t max_aggregate_nodes = 8,
                                  double damping = 4.0 / 3.0, int64_t min_coarse = 600, int32_t max_levels = 7,
-                                 std::vector<double> *omega = nullptr) {
+                                 std::vector<double> *omega = nullptr, double drop_tolerance = 0.0,
+                                 int32_t max_row_entries = 0) {
     int32_t levels = 0;
     std::vector<double> w(ALFD_MAX_LEVELS, 0.0);
-    check(alfd_build_smoothed_aggregation(ctx_, block_size, threshold, max_aggregate_nodes, damping, min_coarse,
-                                          max_levels, &levels, w.data()));
+    if (drop_tolerance == 0.0 && max_row_entries == 0)
+      check(alfd_build_smoothed_aggregation(ctx_, block_size, threshold, max_aggregate_nodes, damping, min_coarse,
+                                            max_levels, &levels, w.data()));
+    else
+      check(alfd_build_smoothed_aggregation_truncated(ctx_, block_size, threshold, max_aggregate_nodes, damping,
+                                                      drop_tolerance, max_row_entries, min_coarse, max_levels, &levels,
+                                                      w.data()));
     if (omega) omega->assign(w.begin(), w.begin() + levels);
     return levels;
   }
