@@ -299,7 +299,12 @@ def permute_background_nodes(pb: "SyntheticProblem", new_to_old) -> "SyntheticPr
 def laplace2d_circle(n_cells=64, immersed_refine=5, coupling_nq=3, surface_mass=False,
                      immersed_segments=0) -> SyntheticProblem:
     """cfg 1: immersed_laplace 2-D, parameters/circle/Circle_parameters_f0_g1.prm
-    (f = 0, g = 1, R = 0.2, centre (0.4, 0.4)), Q1 background on [0,1]^2."""
+    (f = 0, g = 1, R = 0.2, centre (0.4, 0.4)), Q1 background on [0,1]^2.
+    immersed_segments = N sizes the immersed block directly: the circle is meshed with exactly N P1 segments (a closed
+    curve, so N nodes and block_sizes[1] == N) and immersed_refine is ignored.  That is the way to reach a given number
+    of immersed unknowns on a small background, e.g. the chunk boundaries of the rational preconditioner's batched CG
+    (tests/test_gpu_rational.py); C loses full rank once N outgrows the background, so such problems are for
+    operator and preconditioner applications, not for whole solves."""
     return generate(dim=2, degree=1, ncomp=1, n_cells=n_cells, center=(0.4, 0.4, 0.0), radius=0.2,
                     immersed_refine=immersed_refine, coupling_nq=coupling_nq,
                     body_force=(0.0,), embedded_value=(1.0,), surface_mass=surface_mass,
