@@ -21,6 +21,8 @@ CTRL_ABS, CTRL_REDUCTION, CTRL_FIXED_ITERS = range(3)
 PREC_IDENTITY, PREC_JACOBI, PREC_CHEBYSHEV, PREC_MULTILEVEL = range(4)
 # enum alfd_inner_op (alfd_inner_prec_apply)
 INNER_OP_AUG, INNER_OP_A22, INNER_OP_AUG2 = range(3)
+# enum alfd_spectrum_op (alfd_estimate_spectrum)
+SPECTRUM_CCT = 0
 # enum alfd_orthogonalization
 ORTH_MGS, ORTH_CGS, ORTH_CGS2 = range(3)
 # enum alfd_outer_solver
@@ -72,6 +74,18 @@ class Result(C.Structure):
         ("inner_failures", C.c_int32), ("precond_applications", C.c_int32),
         ("solve_seconds", C.c_double), ("lambda_max", C.c_double),
         ("rational_iterations", C.c_int64), ("mass_iterations", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
+class Spectrum(C.Structure):
+    """alfd_spectrum: the condition-number estimate of alfd_estimate_spectrum."""
+    _fields_ = [
+        ("converged", C.c_int32), ("steps", C.c_int32),
+        ("initial_residual", C.c_double), ("last_residual", C.c_double),
+        ("lambda_min", C.c_double), ("lambda_max", C.c_double), ("condition", C.c_double),
     ]
 
     def as_dict(self):

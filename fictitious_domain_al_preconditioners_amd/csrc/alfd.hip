@@ -29,6 +29,7 @@
 #include <climits>
 #include <condition_variable>
 #include <functional>
+#include <limits>
 #include <mutex>
 #include <string>
 #include <thread>
@@ -248,6 +249,20 @@ struct alfd_ctx {
   double *gd_bx = nullptr, *gd_q = nullptr;
   int nmp_group = 16;               // iterations the host enqueues per state read ("nested_mp_group")
   int nmp_host_stepped = 0;         // "nested_mp_host_stepped" = 1: host-stepped pcg() on one rank too
+  // alfd_estimate_spectrum: CG on C Ct over the compacted interface operators Ct[S,:], C[:,S] (S = non-empty rows of
+  // Ct) -- the patch's when it is on, else extractions of its own (built on first use, released by the next setup)
+  struct Spectrum {
+    DevCsr own_Cs, own_Cts;
+    DevCsr *Cs = nullptr, *Cts = nullptr;
+    int64_t m = 0;                              // |S|
+    double *t = nullptr, *ones = nullptr, *x = nullptr, *coef = nullptr, *linf = nullptr;
+    int64_t coef_cap = 0;
+    std::vector<void *> owned;                  // the vectors above
+    std::vector<double> alpha, beta;            // coefficients of the last estimate
+    bool have = false;
+  } spec;
+  int spec_group = 16;              // "spectrum_group": device-stepped iterations enqueued per state read
+  int spec_host_stepped = 0;        // "spectrum_host_stepped" = 1: the same CG through the host-stepped pcg()
   // RationalPreconditioner state (batched CG over the 21 immersed systems)
   HostCsr h_M, h_K;                                    // host copies of the (tiny) immersed matrices
   // multilevel inner preconditioner
@@ -474,6 +489,14 @@ static int csr_alloc(alfd_ctx *ctx, DevCsr &m, T **p, int64_t count) {
 static void csr_free(DevCsr &m) {
   for (void *q : m.owned) hipFree(q);
   m = DevCsr();
+}
+
+// the compacted operators and vectors of alfd_estimate_spectrum (the coefficients of the last estimate go with them)
+static void spectrum_release(alfd_ctx *ctx) {
+  csr_free(ctx->spec.own_Cs);
+  csr_free(ctx->spec.own_Cts);
+  for (void *q : ctx->spec.owned) hipFree(q);
+  ctx->spec = alfd_ctx::Spectrum();
 }
 
 static inline int grid_for_rows(int64_t nrows, int L) {
@@ -967,10 +990,12 @@ static int read_scalars(alfd_ctx *ctx, int first, int count) {
 //   OP_K     y = A x  (K_inv of the rational branch: UMFPACK in the reference,
 //            immersed_laplace.cc:617-620; here CG to alfd_config::inner)
 //   OP_MASS  y = M x  (the immersed mass matrix of the exact W^-1 = (M^-1)^2, stokes...:979-985)
-enum OpKind { OP_AUG = 0, OP_MP = 1, OP_A22 = 2, OP_AUG2 = 3, OP_K = 4, OP_MASS = 5 };
+//   OP_CCT   y = C[:,S] (Ct[S,:] x) = C Ct x on the multiplier block (the sanity check of the drivers,
+//            elliptic_interface.cc:986-1009; alfd_estimate_spectrum)
+enum OpKind { OP_AUG = 0, OP_MP = 1, OP_A22 = 2, OP_AUG2 = 3, OP_K = 4, OP_MASS = 5, OP_CCT = 6 };
 
 static inline int64_t op_npad(const alfd_ctx *ctx, int op) {
-  if (op == OP_MASS) return pad_chunk(ctx->n[ctx->nblocks - 1]);
+  if (op == OP_MASS || op == OP_CCT) return pad_chunk(ctx->n[ctx->nblocks - 1]);
   return (op == OP_AUG || op == OP_K) ? pad_chunk(ctx->n[0]) : op == OP_AUG2 ? ctx->off[2] : pad_chunk(ctx->n[1]);
 }
 
@@ -1008,6 +1033,9 @@ static int op_apply(alfd_ctx *ctx, int op, const double *x, double *y, bool exac
       return spmv(ctx, ALFD_BT, ctx->gd_q, y, 1, ctx->cfg.gamma_grad_div);
     case OP_MASS:
       return spmv(ctx, ALFD_M, x, y, 0);
+    case OP_CCT:
+      RC(spmv_m(ctx, *ctx->spec.Cts, ALFD_T_SPMV_OTHER, x, ctx->spec.t, 0));
+      return spmv_m(ctx, *ctx->spec.Cs, ALFD_T_SPMV_OTHER, ctx->spec.t, y, 0);
     case OP_MP:
       return spmv(ctx, ALFD_MP, x, y, 0);
     case OP_K:
@@ -1088,8 +1116,13 @@ static int cheb_apply(alfd_ctx *ctx, int op, const double *r, double *z, int64_t
 // padded device vectors of the operator's span.
 static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z);
 static int ml_apply(alfd_ctx *ctx, const double *r, double *z);
+// rec (alfd_estimate_spectrum only): the CG coefficients alpha_j, beta_j come back with the readback of r.r, and a
+// step with p.Ap <= 0 (or NaN) ends the solve as FAILURE at the step before it.
+struct CgRecord {
+  std::vector<double> alpha, beta;
+};
 static int pcg(alfd_ctx *ctx, int op, int prec, const alfd_control &ctrl, const double *b, double *x,
-               int *its_out, State *st_out, double *res_out) {
+               int *its_out, State *st_out, double *res_out, CgRecord *rec = nullptr) {
   const int64_t npad = op_npad(ctx, op);
   const int64_t nb = npad / kChunk;
   const double *dinv = op_dinv(ctx, op);
@@ -1126,7 +1159,18 @@ static int pcg(alfd_ctx *ctx, int op, int prec, const alfd_control &ctrl, const 
     RC(dot_async(ctx, npad, p, Ap, 0, FIN_ALPHA));
     VEC_LAUNCH(xr_update_dot_kernel, npad, 48, ctx->sc, p, Ap, x, r, ctx->partial);
     RC(finish_dots(ctx, nb, 1, S_RR, FIN_STORE));
-    RC(read_scalars(ctx, S_RR, 1));
+    if (rec) {
+      RC(read_scalars(ctx, S_PAP, S_RR - S_PAP + 1));
+      if (!(ctx->sc_host[S_PAP] > 0.0)) {
+        --its;
+        st = FAILURE;
+        break;
+      }
+      rec->alpha.push_back(ctx->sc_host[S_ALPHA]);
+      if (its > 1) rec->beta.push_back(ctx->sc_host[S_BETA]);
+    } else {
+      RC(read_scalars(ctx, S_RR, 1));
+    }
     res = std::sqrt(ctx->sc_host[S_RR]);
     st = sc.check(its, res);
   }
@@ -1165,7 +1209,7 @@ static inline bool is_elliptic(int v) { return v == ALFD_AL_ELL_IDEAL || v == AL
 // The two share that set because they are never live at the same time: mass_solve runs to completion inside
 // winv_scale, before op_apply / system_apply reach the Bt Mp^-1 B term, and neither solve's operator (M, Mp)
 // applies W^-1 or Aug.  n_owner records the holder; a second claim is an internal error.
-enum { NESTED_FREE = 0, NESTED_MASS = 1, NESTED_MP = 2 };
+enum { NESTED_FREE = 0, NESTED_MASS = 1, NESTED_MP = 2, NESTED_CCT = 3 };
 static int nested_claim(alfd_ctx *ctx, int who) {
   if (ctx->n_owner != NESTED_FREE)
     return ctx->err = "nested solve started while another holds its work vectors", ALFD_E_INVALID;
@@ -4231,6 +4275,300 @@ static int patch_setup(alfd_ctx *ctx, const HostCsr *A_full, const HostCsr &C, c
   return ALFD_OK;
 }
 
+// ------------------------------------------------- sanity checks of the drivers
+// cond(C Ct) by unpreconditioned CG (immersed_laplace.cc:987-1010, stokes_immersed_boundary.cc:1157-1180,
+// elliptic_interface.cc:986-1009) and the constraint residual (elliptic_interface.cc:973-984).
+
+// A CSR matrix in the plain row-per-lane-group form with a given lane count (no sparse-row list, no window formats)
+static int upload_plain(alfd_ctx *ctx, DevCsr &m, const HostCsr &h, int L) {
+  csr_free(m);
+  m.nrows = m.n_list = h.nrows;
+  m.ncols = h.ncols;
+  m.n_local_cols = (int32_t)h.ncols;
+  m.nnz = h.nnz();
+  m.L = L;
+  m.tag = 1;
+  RC(csr_alloc(ctx, m, &m.rp, h.nrows + 1));
+  RC(csr_alloc(ctx, m, &m.col, m.nnz));
+  RC(csr_alloc(ctx, m, &m.val, m.nnz));
+  HIPC(hipMemcpyAsync(m.rp, h.rp.data(), (h.nrows + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+  if (m.nnz) {
+    HIPC(hipMemcpyAsync(m.col, h.col.data(), m.nnz * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    HIPC(hipMemcpyAsync(m.val, h.val.data(), m.nnz * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));   // h may go away
+  m.present = true;
+  return ALFD_OK;
+}
+
+static int spectrum_alloc(alfd_ctx *ctx, double **p, int64_t count) {
+  void *q = nullptr;
+  HIPC(hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(double)));
+  ctx->spec.owned.push_back(q);
+  *p = static_cast<double *>(q);
+  HIPC(hipMemsetAsync(q, 0, std::max<int64_t>(count, 1) * sizeof(double), ctx->stream));
+  return ALFD_OK;
+}
+
+// Ct[S,:] and C[:,S]: rows keep their entry order and the lane count of the slot they come from, so C[:,S] (Ct[S,:] x)
+// has the bits of the product through the full slots (an empty row of Ct contributes fma(c, 0, acc) there).
+static int spectrum_prepare(alfd_ctx *ctx) {
+  alfd_ctx::Spectrum &Q = ctx->spec;
+  if (Q.Cs) return ALFD_OK;
+  const DevCsr &dC = ctx->mat[ALFD_C], &dCt = ctx->mat[ALFD_CT];
+  alfd_ctx::Patch &P = ctx->patch;
+  const int64_t nl = ctx->n[ctx->nblocks - 1];
+  if (P.on && !P.rep && !P.Cs.sparse && !P.Cts.sparse && P.Cs.L == dC.L && P.Cts.L == dCt.L && P.Cs.nnz == dC.nnz &&
+      P.Cts.nnz == dCt.nnz) {
+    Q.Cs = &P.Cs;
+    Q.Cts = &P.Cts;
+    Q.m = P.m;
+  } else {
+    HostCsr C, Ct, h;
+    RC(download_csr(ctx, dC, C));
+    RC(download_csr(ctx, dCt, Ct));
+    std::vector<int32_t> S, pos(Ct.nrows, -1), lam_rows(C.nrows);
+    for (int64_t i = 0; i < Ct.nrows; ++i)
+      if (Ct.rp[i + 1] > Ct.rp[i]) {
+        pos[i] = (int32_t)S.size();
+        S.push_back((int32_t)i);
+      }
+    for (int64_t k = 0; k < C.nrows; ++k) lam_rows[k] = (int32_t)k;
+    Q.m = (int64_t)S.size();
+    extract_host(C, lam_rows, pos.data(), Q.m, false, h);
+    RC(upload_plain(ctx, Q.own_Cs, h, dC.L));
+    extract_host(Ct, S, nullptr, Ct.ncols, false, h);
+    RC(upload_plain(ctx, Q.own_Cts, h, dCt.L));
+    Q.Cs = &Q.own_Cs;
+    Q.Cts = &Q.own_Cts;
+  }
+  const int64_t nlp = pad_chunk(nl);
+  RC(spectrum_alloc(ctx, &Q.t, pad_chunk(std::max<int64_t>(Q.m, 1))));
+  RC(spectrum_alloc(ctx, &Q.x, nlp));
+  RC(spectrum_alloc(ctx, &Q.ones, nlp));
+  std::vector<double> one(nl, 1.0);
+  if (nl) HIPC(hipMemcpyAsync(Q.ones, one.data(), nl * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
+}
+
+// The device-stepped CG on C Ct (kernels.hpp: spc_*): pcg_mp_device with the identity preconditioner, two gated
+// products per iteration and the recording finish.  6 launches per iteration and one mirror launch per group,
+// whatever n_u is.  Works on the n_* set (the caller holds it); coef = [alpha_1 .. | beta_1 ..], max_steps each.
+static int pcg_cct_device(alfd_ctx *ctx, const alfd_control &ctrl, int *its_out, State *st_out, double *res_out) {
+  alfd_ctx::Spectrum &Q = ctx->spec;
+  const DevCsr &Cs = *Q.Cs, &Cts = *Q.Cts;
+  const int64_t n = ctx->n[ctx->nblocks - 1], npad = pad_chunk(n), nb = npad / kChunk;
+  double *r = ctx->n_r, *p = ctx->n_p, *Ap = ctx->n_Ap, *sc = ctx->n_sc, *x = Q.x, *t = Q.t;
+  double *part_rr = ctx->n_partial, *part_pap = ctx->n_partial + 2 * ctx->pstride;
+  const unsigned grid = (unsigned)nb;
+  auto update = [&](int first) {
+    Timer tm(ctx, ALFD_T_VEC, first ? 24.0 * npad : 48.0 * npad);
+    hipLaunchKernelGGL(spc_update_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, first, part_pap, nb, n, p, Ap, x,
+                       r, part_rr);
+  };
+  auto finish = [&](int step) {
+    Timer tm(ctx, ALFD_T_DOT, 16.0 * nb);
+    hipLaunchKernelGGL(spc_finish_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, part_rr, part_pap, nb, sc, Q.coef, step,
+                       ctrl.kind, ctrl.max_steps, ctrl.tol, ctrl.reduce);
+  };
+  auto product = [&](const DevCsr &m, const double *in, double *out) {
+    Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes());
+    const int sgrid = grid_for_rows(m.nrows, m.L);
+#define ALFD_SPC_S(LL)                                                                                          \
+  hipLaunchKernelGGL((nmp_spmv_kernel<LL>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows, m.rp, m.col, \
+                     m.val, in, out)
+    switch (m.L) {
+      case 4: ALFD_SPC_S(4); break;
+      case 8: ALFD_SPC_S(8); break;
+      case 16: ALFD_SPC_S(16); break;
+      case 32: ALFD_SPC_S(32); break;
+      default: ALFD_SPC_S(64); break;
+    }
+#undef ALFD_SPC_S
+  };
+  update(1);
+  finish(0);
+  HIPC(hipGetLastError());
+  int enq = 0;   // iterations enqueued so far
+  for (;;) {
+    const int group = std::max(1, ctx->spec_group);
+    for (int g = 0; g < group && enq < ctrl.max_steps; ++g) {
+      const int it = ++enq;
+      {
+        Timer tm(ctx, ALFD_T_VEC, it == 1 ? 16.0 * npad : 24.0 * npad);
+        hipLaunchKernelGGL(nmp_p_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, it == 1 ? 1 : 0, r, p);
+      }
+      product(Cts, p, t);
+      product(Cs, t, Ap);
+      {
+        Timer tm(ctx, ALFD_T_DOT, 16.0 * npad);
+        hipLaunchKernelGGL(nmp_dot_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, sc, p, Ap, part_pap);
+      }
+      update(0);
+      finish(it);
+    }
+    HIPC(hipGetLastError());
+    {
+      Timer tm(ctx, ALFD_T_DOT, 8.0 * (S_NRTOL + 1));
+      hipLaunchKernelGGL(mirror_scalars_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, sc, ctx->n_sc_host, (int)(S_NRTOL + 1));
+    }
+    HIPC(hipGetLastError());
+    HIPC(hipStreamSynchronize(ctx->stream));
+    const double *h = ctx->n_sc_host;
+    if (h[S_NSTATE] != 0.0) {
+      *its_out = (int)h[S_NSTEP];
+      *st_out = h[S_NSTATE] == 1.0 ? SUCCESS : FAILURE;
+      *res_out = std::sqrt(h[S_RR]);
+      return ALFD_OK;
+    }
+    if (enq >= ctrl.max_steps) return ctx->err = "CG on C Ct: the device stop rule did not end the solve", ALFD_E_INVALID;
+  }
+}
+
+// Extreme eigenvalues of the CG-Lanczos matrix T_k (alfd.h) by Sturm-count bisection down to neighbouring doubles.
+static int host_tridiagonal_extremes(int32_t k, const double *alpha, const double *beta, double *lmin, double *lmax) {
+  if (k < 1 || !alpha || !lmin || !lmax || (k > 1 && !beta)) return ALFD_E_INVALID;
+  for (int32_t j = 0; j < k; ++j)
+    if (!std::isfinite(alpha[j]) || !(alpha[j] > 0.0)) return ALFD_E_INVALID;
+  for (int32_t j = 0; j + 1 < k; ++j)
+    if (!std::isfinite(beta[j]) || beta[j] < 0.0) return ALFD_E_INVALID;
+  if (k == 1) {
+    *lmin = *lmax = 1.0 / alpha[0];
+    return ALFD_OK;
+  }
+  std::vector<double> d(k), e2(k, 0.0);   // diagonal; e2[j] = eta_{j+1}^2 couples rows j and j + 1
+  double glo = 0, ghi = 0, emax = 0;
+  for (int32_t j = 0; j < k; ++j) d[j] = 1.0 / alpha[j] + (j > 0 ? beta[j - 1] / alpha[j - 1] : 0.0);
+  std::vector<double> e(k, 0.0);
+  for (int32_t j = 0; j + 1 < k; ++j) {
+    e[j] = std::sqrt(beta[j]) / alpha[j];
+    e2[j] = e[j] * e[j];
+    emax = std::max(emax, e2[j]);
+  }
+  for (int32_t j = 0; j < k; ++j) {
+    const double rad = (j > 0 ? e[j - 1] : 0.0) + e[j];
+    if (!std::isfinite(d[j]) || !std::isfinite(rad) || !std::isfinite(e2[j])) return ALFD_E_INVALID;
+    glo = j == 0 ? d[j] - rad : std::min(glo, d[j] - rad);
+    ghi = j == 0 ? d[j] + rad : std::max(ghi, d[j] + rad);
+  }
+  const double pivmin = std::numeric_limits<double>::min() * std::max(1.0, emax);
+  auto count_below = [&](double x) {   // number of eigenvalues of T_k below x
+    int32_t c = 0;
+    double q = d[0] - x;
+    for (int32_t j = 0;; ++j) {
+      if (std::fabs(q) < pivmin) q = -pivmin;
+      if (q < 0.0) ++c;
+      if (j + 1 == k) return c;
+      q = d[j + 1] - x - e2[j] / q;
+    }
+  };
+  const double norm = std::max(std::fabs(glo), std::fabs(ghi));
+  const double wlo = glo - 1e-12 * norm - pivmin, whi = ghi + 1e-12 * norm + pivmin;   // count(wlo) = 0, count(whi) = k
+  auto bisect = [&](int32_t want) {   // the largest x with count_below(x) < want, between neighbouring doubles
+    double lo = wlo, hi = whi;
+    for (;;) {
+      const double mid = lo + 0.5 * (hi - lo);
+      if (!(mid > lo) || !(mid < hi)) return lo;
+      if (count_below(mid) >= want) hi = mid;
+      else lo = mid;
+    }
+  };
+  *lmin = bisect(1);
+  *lmax = bisect(k);
+  return ALFD_OK;
+}
+
+static int estimate_spectrum(alfd_ctx *ctx, const alfd_control &ctrl, alfd_spectrum *out) {
+  alfd_ctx::Spectrum &Q = ctx->spec;
+  RC(spectrum_prepare(ctx));
+  Q.have = false;
+  Q.alpha.clear();
+  Q.beta.clear();
+  int its = 0;
+  State st = FAILURE;
+  // r_0 = 1 on n_lambda rows: its canonical sum of squares is the integer n_lambda, exactly, in any order
+  const double res0 = std::sqrt((double)ctx->n[ctx->nblocks - 1]);
+  double res = 0;
+  RC(nested_claim(ctx, NESTED_CCT));
+  int rc;
+  if (!ctx->spec_host_stepped) {
+    rc = ALFD_OK;
+    if (Q.coef_cap < 2 * (int64_t)ctrl.max_steps) {
+      rc = spectrum_alloc(ctx, &Q.coef, 2 * (int64_t)ctrl.max_steps);
+      if (rc == ALFD_OK) Q.coef_cap = 2 * (int64_t)ctrl.max_steps;
+    }
+    if (rc == ALFD_OK) rc = pcg_cct_device(ctx, ctrl, &its, &st, &res);
+    if (rc == ALFD_OK && its > 0) {
+      Q.alpha.resize(its);
+      Q.beta.resize(its - 1);
+      hipError_t e = hipMemcpyAsync(Q.alpha.data(), Q.coef, its * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+      if (e == hipSuccess && its > 1)
+        e = hipMemcpyAsync(Q.beta.data(), Q.coef + ctrl.max_steps, (its - 1) * sizeof(double), hipMemcpyDeviceToHost,
+                           ctx->stream);
+      if (e == hipSuccess) e = hipStreamSynchronize(ctx->stream);
+      if (e != hipSuccess) ctx->err = std::string("coefficient readback: ") + hipGetErrorString(e), rc = ALFD_E_HIP;
+    }
+  } else {
+    CgRecord rec;
+    nested_swap_ws(ctx);
+    rc = pcg(ctx, OP_CCT, ALFD_PREC_IDENTITY, ctrl, Q.ones, Q.x, &its, &st, &res, &rec);
+    nested_swap_ws(ctx);
+    Q.alpha = std::move(rec.alpha);
+    Q.beta = std::move(rec.beta);
+  }
+  ctx->n_owner = NESTED_FREE;
+  flush_timers(ctx);
+  if (rc != ALFD_OK) return rc;
+  Q.have = true;
+  std::memset(out, 0, sizeof(*out));
+  out->converged = st == SUCCESS ? 1 : 0;
+  out->steps = its;
+  out->initial_residual = res0;
+  out->last_residual = its == 0 ? res0 : res;
+  out->lambda_min = out->lambda_max = out->condition = std::nan("");
+  if (its == 0) {
+    if (st == SUCCESS) return ALFD_OK;   // the start already met the stop rule: nothing to estimate from
+    return ctx->err = "CG on C Ct broke down in its first step (p.Ap <= 0): no estimate", ALFD_E_BREAKDOWN;
+  }
+  if (host_tridiagonal_extremes(its, Q.alpha.data(), Q.beta.data(), &out->lambda_min, &out->lambda_max) != ALFD_OK)
+    return ctx->err = "CG on C Ct: non-finite coefficients, no estimate", ALFD_E_BREAKDOWN;
+  out->condition = out->lambda_max / out->lambda_min;
+  if (ctx->cfg.log_level >= 1 && ctx->rank == 0) {
+    std::printf("Condition number estimate: %g\n", out->condition);
+    std::fflush(stdout);
+    if (!out->converged) std::fprintf(stderr, "***CCt solve not successfull (see condition number above)***\n");
+  }
+  return ALFD_OK;
+}
+
+static int to_device(alfd_ctx *ctx, const double *const *blocks, double *dev);
+// || (last block row of AA) x - g ||_inf: the last block of system_apply (same launches), then the two-stage max
+static int constraint_residual(alfd_ctx *ctx, const double *const *x_blocks, const double *g, double *linf) {
+  alfd_ctx::Spectrum &Q = ctx->spec;
+  const int last = ctx->nblocks - 1;
+  const int64_t n = ctx->n[last], nb = pad_chunk(n) / kChunk;
+  if (!Q.linf) RC(spectrum_alloc(ctx, &Q.linf, nb + 1 + pad_chunk(n)));
+  double *part = Q.linf + 1, *dg = Q.linf + 1 + nb;
+  RC(to_device(ctx, x_blocks, ctx->st_in));
+  HIPC(hipMemsetAsync(ctx->st_out, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  const double *x = ctx->st_in;
+  double *y = ctx->st_out + ctx->off[last];
+  RC(spmv(ctx, ALFD_C, x + ctx->off[0], y, 0));
+  if (is_elliptic(ctx->cfg.variant)) RC(spmv(ctx, ALFD_M, x + ctx->off[1], y, 1, -1.0));   // y2 = C x0 - M x1
+  if (g && n) HIPC(hipMemcpyAsync(dg, g, n * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  if (nb > 0) {
+    Timer tm(ctx, ALFD_T_VEC, (g ? 16.0 : 8.0) * n);
+    hipLaunchKernelGGL(linf_diff_partial_kernel, dim3((unsigned)nb), dim3(kBlock), 0, ctx->stream, n, y,
+                       g ? dg : (const double *)nullptr, part);
+  }
+  hipLaunchKernelGGL(linf_final_kernel, dim3(1), dim3(kBlock), 0, ctx->stream, part, nb, Q.linf);
+  HIPC(hipGetLastError());
+  HIPC(hipMemcpyAsync(linf, Q.linf, sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
+}
+
 // Explicit inverse of the coarsest Aug_c = A_c + gamma Ct_c W^-1 C_c: dense Cholesky on the host, every entry a
 // sequential fma chain (the oracle repeats the loops), uploaded as a dense CSR so that z = Aug_c^-1 r runs in
 // the canonical SpMV order.  ML solves its coarsest level directly as well (KLU, utilities.h:304-317).
@@ -5648,6 +5986,7 @@ static int setup(alfd_ctx *ctx) {
   HIPC(hipStreamSynchronize(ctx->stream));
   for (void *p : ctx->ws_allocs) hipFree(p);
   ctx->ws_allocs.clear();
+  spectrum_release(ctx);   // may point into the patch of the previous setup
   if (ctx->sc_host) hipHostFree(ctx->sc_host), ctx->sc_host = nullptr;
   const int64_t N = ctx->ntot(), n0p = pad_chunk(ctx->n[0]);
   ctx->wmax = c.variant == ALFD_AL_ELL_IDEAL ? ctx->off[2] : ctx->nmax;
@@ -5682,9 +6021,9 @@ static int setup(alfd_ctx *ctx) {
   if (ctx->n_sc_host) hipHostFree(ctx->n_sc_host), ctx->n_sc_host = nullptr;
   ctx->n_owner = NESTED_FREE;
   // the n_* set of the nested solves (mass_solve, nested_mp_solve): as long as the longer of the two blocks
-  const int64_t n_nested = std::max<int64_t>(c.w_inverse != ALFD_W_DIAGONAL ? pad_chunk(ctx->n[last]) : 0,
-                                             gd_off ? pad_chunk(ctx->n[1]) : 0);
-  if (n_nested > 0) {
+  // (and the CG of alfd_estimate_spectrum on the multiplier block, which is there for every variant)
+  const int64_t n_nested = std::max<int64_t>(pad_chunk(ctx->n[last]), gd_off ? pad_chunk(ctx->n[1]) : 0);
+  {
     RC(ws_alloc_zero(ctx, &ctx->n_r, n_nested));
     RC(ws_alloc_zero(ctx, &ctx->n_z, n_nested));
     RC(ws_alloc_zero(ctx, &ctx->n_p, n_nested));
@@ -5970,6 +6309,7 @@ int alfd_destroy(alfd_ctx_t ctx) {
   hipStreamSynchronize(ctx->stream);
   flush_timers(ctx);
   free_levels(ctx);
+  spectrum_release(ctx);
   csr_free(ctx->rat_mat);
   for (DevCsr &m : ctx->mat) csr_free(m);
   for (void *p : ctx->ws_allocs) hipFree(p);
@@ -7300,7 +7640,63 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
     ctx->nmp_host_stepped = value != 0;
     return ALFD_OK;
   }
+  if (std::strcmp(name, "spectrum_group") == 0) {   // iterations of the device-stepped CG on C Ct per state read
+    if (value < 1 || value > 1000) return ctx->err = "spectrum_group: 1..1000", ALFD_E_INVALID;
+    ctx->spec_group = value;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "spectrum_host_stepped") == 0) {   // 1: alfd_estimate_spectrum through the host-stepped pcg()
+    ctx->spec_host_stepped = value != 0;
+    return ALFD_OK;
+  }
   return ctx->err = std::string("unknown tunable ") + name, ALFD_E_INVALID;
+}
+
+int alfd_host_tridiagonal_extremes(int32_t k, const double *alpha, const double *beta, double *lambda_min,
+                                   double *lambda_max) {
+  return host_tridiagonal_extremes(k, alpha, beta, lambda_min, lambda_max);
+}
+
+int alfd_estimate_spectrum(alfd_ctx_t ctx, int op, const alfd_control *ctrl, alfd_spectrum *out) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!out) return ALFD_E_INVALID;
+  if (op != ALFD_SPECTRUM_CCT) return ctx->err = "alfd_estimate_spectrum: unknown operator", ALFD_E_INVALID;
+  if (ctx->nranks > 1) return ctx->err = "alfd_estimate_spectrum: single rank only", ALFD_E_UNSUPPORTED;
+  const int64_t nl = ctx->n[ctx->nblocks - 1];
+  alfd_control c;
+  if (ctrl) {
+    c = *ctrl;
+  } else {   // SolverControl(lambda.size(), 1e-12)
+    c.kind = ALFD_CTRL_ABS;
+    c.max_steps = (int32_t)std::min<int64_t>(nl, INT32_MAX);
+    c.tol = 1e-12;
+    c.reduce = 0.0;
+  }
+  if (c.kind < ALFD_CTRL_ABS || c.kind > ALFD_CTRL_FIXED_ITERS || c.max_steps < 1)
+    return ctx->err = "alfd_estimate_spectrum: bad control (max_steps >= 1)", ALFD_E_INVALID;
+  if (nl < 1) return ctx->err = "alfd_estimate_spectrum: no multipliers", ALFD_E_INVALID;
+  return estimate_spectrum(ctx, c, out);
+}
+
+int alfd_get_cg_coefficients(alfd_ctx_t ctx, double *alpha, double *beta, int32_t capacity, int32_t *count) {
+  if (!ctx) return ALFD_E_INVALID;
+  if (!ctx->spec.have) return ctx->err = "no spectrum estimate yet", ALFD_E_NOT_SETUP;
+  const int32_t k = (int32_t)ctx->spec.alpha.size();
+  if (count) *count = k;
+  for (int32_t i = 0; i < capacity && i < k; ++i) {
+    if (alpha) alpha[i] = ctx->spec.alpha[i];
+    if (beta && i + 1 < k) beta[i] = ctx->spec.beta[i];
+  }
+  return ALFD_OK;
+}
+
+int alfd_constraint_residual(alfd_ctx_t ctx, const double *const *x_blocks, const double *g, double *linf) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!x_blocks || !linf) return ALFD_E_INVALID;
+  if (ctx->nranks > 1) return ctx->err = "alfd_constraint_residual: single rank only", ALFD_E_UNSUPPORTED;
+  return constraint_residual(ctx, x_blocks, g, linf);
 }
 
 int alfd_set_row_blocks(alfd_ctx_t ctx, int slot, int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows) {

@@ -2214,4 +2214,140 @@ __global__ __launch_bounds__(kBlock) void nmp_dot_kernel(const double *__restric
   if (threadIdx.x == 0) part_pap[blockIdx.x] = s;
 }
 
+// ---- device-stepped unpreconditioned CG on C Ct that records its coefficients (alfd_estimate_spectrum)
+// pcg() with ALFD_PREC_IDENTITY on y = Cs (Cts x), b = 1, from a zero start.  Six launches per iteration, the
+// scheme of the Mp solve above with z = r (one dot instead of two):
+//   P  nmp_p_kernel with z = r          S  t = Cts p, then Ap = Cs t: nmp_spmv_kernel twice
+//   D  nmp_dot_kernel                   U  spc_update_kernel         F  spc_finish_kernel
+// sc[S_RZ] holds r.r of the previous step (identity: r.z == r.r, same canonical dot, same bits).
+
+// U, first = 1: r = 1 on the n rows (0 on the padding), x = 0, Ap = 0; first = 0: alpha = rr / pAp from the p.Ap
+// partials, x = fma(alpha, p, x), r = fma(-alpha, Ap, r).  Then the chunk partials of r.r.
+__global__ __launch_bounds__(kBlock) void spc_update_kernel(const double *__restrict__ sc, int first,
+                                                            const double *__restrict__ part_pap, int64_t nb, int64_t n,
+                                                            const double *__restrict__ p, double *__restrict__ Ap,
+                                                            double *__restrict__ x, double *__restrict__ r,
+                                                            double *__restrict__ part_rr) {
+  __shared__ double lds_a[4], lds_rr[4];
+  if (!first && nmp_stopped(sc)) return;
+  double a = 0.0, na = 0.0;
+  if (!first) {
+    const double pap = nmp_second_stage(part_pap, nb, lds_a);
+    a = sc[S_RZ] / pap;
+    na = -a;
+  }
+  double arr = 0.0;
+  ALFD_FOR_PAIRS(i) {
+    double2 rv, xv;
+    if (first) {
+      rv = make_double2(i < n ? 1.0 : 0.0, i + 1 < n ? 1.0 : 0.0);
+      xv = make_double2(0.0, 0.0);
+      st2(Ap, i, make_double2(0.0, 0.0));
+    } else {
+      const double2 pv = ld2(p, i), av = ld2(Ap, i);
+      xv = ld2(x, i);
+      rv = ld2(r, i);
+      xv.x = fma(a, pv.x, xv.x);
+      xv.y = fma(a, pv.y, xv.y);
+      rv.x = fma(na, av.x, rv.x);
+      rv.y = fma(na, av.y, rv.y);
+    }
+    st2(x, i, xv);
+    st2(r, i, rv);
+    arr = fma(rv.x, rv.x, arr);
+    arr = fma(rv.y, rv.y, arr);
+  }
+  const double srr = block_reduce_256(arr, lds_rr);
+  if (threadIdx.x == 0) part_rr[blockIdx.x] = srr;
+}
+
+// F: one workgroup.  Breakdown test (p.Ap <= 0 or NaN: state FAILURE, step and residual stay those of the step
+// before), then Control::check as nmp_finish_kernel.  A step that counts stores alpha_step = rr_old / pAp into
+// coef[step - 1]; one that goes on also beta_step = rr / rr_old into coef[max_steps + step - 1].  Plain stores of
+// thread 0, the state word last.
+__global__ __launch_bounds__(kBlock) void spc_finish_kernel(const double *__restrict__ part_rr,
+                                                            const double *__restrict__ part_pap, int64_t nb,
+                                                            double *__restrict__ sc, double *__restrict__ coef, int step,
+                                                            int kind, int max_steps, double tol, double reduce) {
+  __shared__ double lds_rr[4], lds_a[4];
+  if (step > 0 && nmp_stopped(sc)) return;
+  const double rr = nmp_second_stage(part_rr, nb, lds_rr);
+  const double pap = step > 0 ? nmp_second_stage(part_pap, nb, lds_a) : 1.0;
+  if (threadIdx.x == 0) {
+    if (!(pap > 0.0)) {
+      sc[S_PAP] = pap;
+      sc[S_NSTATE] = 2.0;
+      return;
+    }
+    const double v = sqrt(rr);
+    if (step == 0) sc[S_NRTOL] = v * reduce;
+    const double reduced_tol = step == 0 ? v * reduce : sc[S_NRTOL];
+    int state = 0;   // ITERATE
+    if (kind == ALFD_CTRL_REDUCTION && v < reduced_tol) state = 1;
+    else if (kind == ALFD_CTRL_FIXED_ITERS && step >= max_steps) state = 1;
+    else if (v <= tol) state = 1;
+    else if (step >= max_steps || isnan(v)) state = 2;
+    const double old = sc[S_RZ];
+    if (step > 0) coef[step - 1] = old / pap;
+    sc[S_RR] = rr;
+    sc[S_NRES] = v;
+    sc[S_NSTEP] = (double)step;
+    if (state == 0) {
+      sc[S_RZ_OLD] = old;
+      sc[S_RZ] = rr;
+      if (step > 0) {
+        const double beta = rr / old;
+        sc[S_BETA] = beta;
+        coef[max_steps + step - 1] = beta;
+      }
+    }
+    sc[S_NSTATE] = (double)state;
+  }
+}
+
+// ---- max-abs reduction of d = y - g (alfd_constraint_residual), two stages, no atomics.  A NaN entry makes the
+// result NaN (fmax would drop it): every stage carries a NaN flag beside the maximum.
+__device__ __forceinline__ double linf_block(double m, double bad, double *lds) {   // lds[8]
+  for (int o = 32; o > 0; o >>= 1) {
+    m = fmax(m, __shfl_xor(m, o, 64));
+    bad = fmax(bad, __shfl_xor(bad, o, 64));
+  }
+  const int wave = threadIdx.x >> 6;
+  if ((threadIdx.x & 63) == 0) lds[wave] = m, lds[4 + wave] = bad;
+  __syncthreads();
+  m = fmax(fmax(lds[0], lds[1]), fmax(lds[2], lds[3]));
+  bad = fmax(fmax(lds[4], lds[5]), fmax(lds[6], lds[7]));
+  return bad > 0.0 ? nan("") : m;
+}
+
+// stage 1: part[b] = max |y_i - g_i| over chunk b (g == nullptr: 0), i < n
+__global__ __launch_bounds__(kBlock) void linf_diff_partial_kernel(int64_t n, const double *__restrict__ y,
+                                                                   const double *__restrict__ g,
+                                                                   double *__restrict__ part) {
+  __shared__ double lds[8];
+  double m = 0.0, bad = 0.0;
+  const int64_t base = (int64_t)blockIdx.x * kChunk;
+  for (int64_t i = base + threadIdx.x; i < base + kChunk && i < n; i += kBlock) {
+    const double d = g ? y[i] - g[i] : y[i];
+    if (isnan(d)) bad = 1.0;
+    m = fmax(m, fabs(d));
+  }
+  const double s = linf_block(m, bad, lds);
+  if (threadIdx.x == 0) part[blockIdx.x] = s;
+}
+
+// stage 2: one workgroup, out[0] = max of the nb chunk results
+__global__ __launch_bounds__(kBlock) void linf_final_kernel(const double *__restrict__ part, int64_t nb,
+                                                            double *__restrict__ out) {
+  __shared__ double lds[8];
+  double m = 0.0, bad = 0.0;
+  for (int64_t i = threadIdx.x; i < nb; i += kBlock) {
+    const double d = part[i];
+    if (isnan(d)) bad = 1.0;
+    m = fmax(m, d);
+  }
+  const double s = linf_block(m, bad, lds);
+  if (threadIdx.x == 0) out[0] = s;
+}
+
 }  // namespace alfd

@@ -37,6 +37,8 @@ ABI_SYMBOLS = [
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
     "alfd_build_smoothed_aggregation_truncated", "alfd_host_truncate_prolongator",
     "alfd_inner_prec_apply",
+    "alfd_estimate_spectrum", "alfd_get_cg_coefficients", "alfd_host_tridiagonal_extremes",
+    "alfd_constraint_residual",
 ]
 
 
@@ -128,6 +130,10 @@ def load_library():
         "alfd_host_numbering_from_points": (C.c_int, [i64, C.c_int32, vp, vp]),
         "alfd_host_brick_blocks_from_points": (C.c_int, [i64, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
         "alfd_host_permute_csr": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp, vp]),
+        "alfd_estimate_spectrum": (C.c_int, [vp, C.c_int, C.POINTER(_abi.Control), C.POINTER(_abi.Spectrum)]),
+        "alfd_get_cg_coefficients": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32)]),
+        "alfd_host_tridiagonal_extremes": (C.c_int, [i32, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]),
+        "alfd_constraint_residual": (C.c_int, [vp, PP, vp, C.POINTER(dbl)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -392,6 +398,36 @@ class Context:
         self._ck(self._lib.alfd_inner_prec_apply(self._h, int(op), r.ctypes.data, z.ctypes.data))
         return z
 
+    # -- sanity checks of the drivers (elliptic_interface.cc:973-1009)
+    def estimate_spectrum(self, op=_abi.SPECTRUM_CCT, control=None):
+        """cond(C Ct) by unpreconditioned CG from the all-ones right-hand side (alfd_estimate_spectrum): the
+        _abi.Spectrum with the extreme Ritz values, their ratio and `converged`, the full-rank verdict.  control
+        None: SolverControl(n_lambda, 1e-12)."""
+        out = _abi.Spectrum()
+        self._ck(self._lib.alfd_estimate_spectrum(self._h, int(op), None if control is None else C.byref(control),
+                                                  C.byref(out)))
+        return out
+
+    def cg_coefficients(self):
+        """(alpha_1..alpha_k, beta_1..beta_{k-1}) of the last estimate_spectrum."""
+        cnt = C.c_int32(0)
+        self._ck(self._lib.alfd_get_cg_coefficients(self._h, None, None, 0, C.byref(cnt)))
+        alpha, beta = np.zeros(cnt.value), np.zeros(max(cnt.value, 1))
+        self._ck(self._lib.alfd_get_cg_coefficients(self._h, alpha.ctypes.data, beta.ctypes.data, cnt.value,
+                                                    C.byref(cnt)))
+        return alpha, beta[:max(cnt.value - 1, 0)].copy()
+
+    def constraint_residual(self, x, g=None):
+        """|| (last block row of the system) x - g ||_inf (alfd_constraint_residual); g None: zero."""
+        x = self._in(x)
+        gv = None if g is None else np.ascontiguousarray(g, np.float64)
+        if gv is not None and gv.size != self.block_sizes[-1]:
+            raise ValueError(f"g has {gv.size} entries, the multiplier block {self.block_sizes[-1]}")
+        out = C.c_double()
+        self._ck(self._lib.alfd_constraint_residual(self._h, _blocks(x), None if gv is None else gv.ctypes.data,
+                                                    C.byref(out)))
+        return out.value
+
     def bench_spmv(self, slot, reps=20):
         ms, nbytes = C.c_double(), C.c_double()
         self._ck(self._lib.alfd_bench_spmv(self._h, slot, reps, C.byref(ms), C.byref(nbytes)))
@@ -483,6 +519,21 @@ def host_halo_plan(col, col_offsets, rank):
     if rc != _abi.OK:
         raise AlfdError(rc, "alfd_host_halo_plan failed")
     return col_local, halo[:n_halo.value].copy(), recv_off
+
+
+def host_tridiagonal_extremes(alpha, beta):
+    """Host-only: (lambda_min, lambda_max) of the Lanczos matrix T_k of the CG coefficients alpha_1..alpha_k,
+    beta_1..beta_{k-1} (alfd_host_tridiagonal_extremes: Sturm-count bisection, no LAPACK)."""
+    a = np.ascontiguousarray(alpha, np.float64)
+    b = np.ascontiguousarray(beta, np.float64)
+    if a.size > 1 and b.size < a.size - 1:
+        raise ValueError("beta needs k - 1 entries")
+    lo, hi = C.c_double(), C.c_double()
+    rc = load_library().alfd_host_tridiagonal_extremes(a.size, a.ctypes.data, b.ctypes.data if b.size else None,
+                                                       C.byref(lo), C.byref(hi))
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_tridiagonal_extremes: bad coefficients")
+    return lo.value, hi.value
 
 
 def host_aggregate_level(m, block_size=1, threshold=0.02, max_aggregate_nodes=8):

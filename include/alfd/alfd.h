@@ -466,6 +466,51 @@ int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double
  * call is collective like alfd_spmv: r, z hold this rank's rows. */
 enum alfd_inner_op { ALFD_INNER_OP_AUG = 0, ALFD_INNER_OP_A22 = 1, ALFD_INNER_OP_AUG2 = 2 };
 int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z);
+/* ------------------------------------------------------------ sanity checks
+ * The diagnostic block that ends every driver's solve (immersed_laplace.cc:987-1010,
+ * stokes_immersed_boundary.cc:1157-1180, elliptic_interface.cc:973-1009, `Perform sanity checks`).
+ *
+ * alfd_estimate_spectrum replaces the unpreconditioned SolverCG on C Ct with connect_condition_number_slot [EXT]:
+ * right-hand side all ones, zero start, SolverControl(lambda.size(), 1e-12) when ctrl == NULL.  The arithmetic is
+ * the inner CG's with ALFD_PREC_IDENTITY on y = C (Ct x), run on the compacted operators
+ * C[:,S], Ct[S,:] (S = non-empty rows of Ct), so an iteration costs O(nnz(C) + n_lambda) whatever n_u is; on one
+ * rank the stop rule runs on the device and the host reads the state once per group of iterations (tunables
+ * "spectrum_group", "spectrum_host_stepped").  With alpha_j = r_{j-1}.r_{j-1} / p_j.(C Ct p_j) and
+ * beta_j = r_j.r_j / r_{j-1}.r_{j-1} the Lanczos matrix T_k of k CG steps is tridiagonal with the diagonal
+ * delta_1 = 1/alpha_1, delta_j = 1/alpha_j + beta_{j-1}/alpha_{j-1} and the off-diagonal
+ * eta_j = sqrt(beta_j)/alpha_j, j < k; its extreme eigenvalues (Ritz values) estimate those of C Ct, which is what
+ * SolverCG's condition-number slot reports [EXT].
+ *   After alfd_setup, every variant (all have C and CT); before it ALFD_E_NOT_SETUP.  Unknown op or
+ *   ctrl->max_steps < 1: ALFD_E_INVALID.  Partitioned context: ALFD_E_UNSUPPORTED (single rank only).
+ *   ALFD_OK whenever an estimate was produced, also when the CG did not converge -- the reference catches that
+ *   exception and keeps the number; `converged` carries the "C Ct does not have full rank" verdict.  A step with
+ *   p.Ap <= 0 (or NaN) ends the solve at the step before it; if that was the first step there is nothing to
+ *   estimate from: ALFD_E_BREAKDOWN.  A start that already meets the stop rule gives steps = 0 and NaN estimates.
+ *   Touches neither a resident right-hand side / solution nor the staging of the depth-1 calls: a solve after it
+ *   gives the same bits as before.  log_level >= 1 prints "Condition number estimate: <kappa>" and, when the CG did
+ *   not converge, the reference's "***CCt solve not successfull (see condition number above)***" to stderr. */
+typedef struct alfd_spectrum {
+  int32_t converged;        /* 1: the CG met its stop rule; 0: it hit max_steps, broke down (p.Ap <= 0) or met a NaN */
+  int32_t steps;            /* CG steps taken = order k of the tridiagonal matrix */
+  double initial_residual, last_residual;
+  double lambda_min, lambda_max, condition;   /* extreme Ritz values of T_k and their ratio */
+} alfd_spectrum;
+enum alfd_spectrum_op { ALFD_SPECTRUM_CCT = 0 };   /* C Ct on the multiplier block */
+int alfd_estimate_spectrum(alfd_ctx_t ctx, int op, const alfd_control *ctrl /* NULL: ABS, max_steps = n_lambda, tol 1e-12 */,
+                           alfd_spectrum *out);
+/* alpha_1..alpha_k and beta_1..beta_{k-1} of the last estimate: *count = k, at most `capacity` entries are written,
+ * beta[k-1] never.  ALFD_E_NOT_SETUP before the first estimate. */
+int alfd_get_cg_coefficients(alfd_ctx_t ctx, double *alpha, double *beta, int32_t capacity, int32_t *count);
+/* Host-only (no device, no context): the smallest and largest eigenvalue of T_k above by Sturm-count bisection down
+ * to neighbouring doubles (no LAPACK); k = 1 gives 1/alpha_1 twice (beta may be NULL).  ALFD_E_INVALID for k < 1, a
+ * non-finite or non-positive alpha, a negative or non-finite beta.  alfd_estimate_spectrum calls this routine. */
+int alfd_host_tridiagonal_extremes(int32_t k, const double *alpha, const double *beta, double *lambda_min, double *lambda_max);
+/* || (last block row of AA) x - g ||_inf for host vectors x_blocks (one pointer per block, as alfd_system_apply);
+ * g == NULL: zero.  The row is C x0 for ALFD_AL2, the Stokes variants and ALFD_RATIONAL, C x0 - M x1 for the elliptic
+ * variants (the "L infty norm of constraints residual" of elliptic_interface.cc:973-984, up to its sign).  The
+ * product is the last block of alfd_system_apply, same bits; a NaN entry makes the result NaN.  Stages through the
+ * buffers of the depth-1 calls.  Single rank: ALFD_E_UNSUPPORTED on a partitioned context. */
+int alfd_constraint_residual(alfd_ctx_t ctx, const double *const *x_blocks, const double *g /* may be NULL */, double *linf);
 /* Lanes per row the canonical SpMV order uses for this slot (after setup). */
 int alfd_matrix_lanes(alfd_ctx_t ctx, int slot, int32_t *lanes);
 /* Benchmark hook: run `reps` back-to-back y = A x launches of `slot` on resident
@@ -586,6 +631,9 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
  *                  "nested_mp_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
+ *   "spectrum_host_stepped" (0/1, default 0): alfd_estimate_spectrum steps its CG on the host (one synchronisation
+ *                  per iteration, through the inner CG's own loop) instead of on the device.  Same bits either way.
+ *                  "spectrum_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
  *   "ml_fuse"      1 (default; environment ALFD_ML_FUSE, read at alfd_create): inside ALFD_PREC_MULTILEVEL the product
  *                  y += gamma Ct t that ends every factored operator A + gamma Ct invW C and the element-wise kernel
  *                  after it (Chebyshev step, residual, residual + first direction, final z += correction) are one

@@ -254,6 +254,34 @@ class System {
     finish_out(rhs);
   }
 
+  // The sanity block that ends the drivers' solve() (immersed_laplace.cc:987-1010, stokes...:1157-1180,
+  // elliptic_interface.cc:973-1009).  estimate_condition_number_CCt replaces the SolverCG on C * Ct with
+  // connect_condition_number_slot: .condition is the printed estimate, .converged == 0 the reference's
+  // "does not have full rank" verdict (the reference throws there; here the caller decides).  Any other failure
+  // throws like every call of this class.  control == nullptr: SolverControl(lambda.size(), 1e-12).
+  alfd_spectrum estimate_condition_number_CCt(const alfd_control *control = nullptr) {
+    alfd_spectrum s{};
+    check(alfd_estimate_spectrum(ctx_, ALFD_SPECTRUM_CCT, control, &s));
+    return s;
+  }
+  // linfty_norm of (last block row of AA) x - g: C u - M u2 for the elliptic variants
+  // (difference_constraints, elliptic_interface.cc:973-984), C u - g otherwise.  Shared by all six
+  // preconditioner classes through this holder.
+  template <class BlockVectorType, class VectorType>
+  double constraint_residual(const BlockVectorType &x, const VectorType &g) {
+    std::vector<const double *> p = in_ptrs(x);
+    double linf = 0;
+    check(alfd_constraint_residual(ctx_, p.data(), &*g.begin(), &linf));
+    return linf;
+  }
+  template <class BlockVectorType>
+  double constraint_residual(const BlockVectorType &x) {   // g = 0
+    std::vector<const double *> p = in_ptrs(x);
+    double linf = 0;
+    check(alfd_constraint_residual(ctx_, p.data(), nullptr, &linf));
+    return linf;
+  }
+
   // The block_operator AA (stokes...:1000-1003) as an object with vmult().
   class SystemOperator {
    public:
