@@ -6978,6 +6978,36 @@ int alfd_spmv(alfd_ctx_t ctx, int slot, const double *x, double *y, int mode, do
   return rc;
 }
 
+int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d, double *y, double *y2) {
+  CHECK_CTX();
+  if (slot < 0 || slot >= ALFD_NSLOTS || !ctx->mat[slot].present) return ALFD_E_INVALID;
+  if (!x || !d || !y || y2 == y) return ALFD_E_INVALID;   // the kernels take y and y2 as __restrict__
+  const DevCsr &m = ctx->mat[slot];
+  const int64_t nx = ctx->nranks > 1 ? (int64_t)m.n_local_cols : m.ncols;
+  const size_t rows = std::max<int64_t>(m.nrows, 1) * sizeof(double), nb = m.nrows * sizeof(double);
+  double *dx = nullptr, *dd = nullptr, *dy = nullptr, *dy2 = nullptr;
+  HIPC(hipMalloc((void **)&dx, std::max<int64_t>(nx, 1) * sizeof(double)));
+  HIPC(hipMalloc((void **)&dd, rows));
+  HIPC(hipMalloc((void **)&dy, rows));
+  if (y2) HIPC(hipMalloc((void **)&dy2, rows));
+  HIPC(hipMemcpyAsync(dx, x, nx * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dd, d, nb, hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dy, y, nb, hipMemcpyHostToDevice, ctx->stream));
+  if (y2) HIPC(hipMemcpyAsync(dy2, y2, nb, hipMemcpyHostToDevice, ctx->stream));
+  // the solver's own call: epilogue 2 (t = W^-1 .* (C x)) or 3 (y_lambda = C x and t beside it)
+  const int rc = spmv(ctx, slot, dx, dy, y2 ? 3 : 2, 0.0, dd, dy2);
+  if (rc == ALFD_OK) {
+    HIPC(hipMemcpyAsync(y, dy, nb, hipMemcpyDeviceToHost, ctx->stream));
+    if (y2) HIPC(hipMemcpyAsync(y2, dy2, nb, hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+  }
+  hipFree(dx);
+  hipFree(dd);
+  hipFree(dy);
+  hipFree(dy2);
+  return rc;
+}
+
 int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z) {
   CHECK_CTX();
   CHECK_SETUP();

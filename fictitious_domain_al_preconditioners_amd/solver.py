@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
     "alfd_build_smoothed_aggregation_truncated", "alfd_host_truncate_prolongator",
-    "alfd_inner_prec_apply",
+    "alfd_inner_prec_apply", "alfd_spmv_scaled",
     "alfd_estimate_spectrum", "alfd_get_cg_coefficients", "alfd_host_tridiagonal_extremes",
     "alfd_constraint_residual",
 ]
@@ -89,6 +89,7 @@ def load_library():
         "alfd_download_solution": (C.c_int, [vp, PP]),
         "alfd_get_history": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
         "alfd_spmv": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, dbl]),
+        "alfd_spmv_scaled": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "alfd_dot": (C.c_int, [vp, i64, vp, vp, C.POINTER(dbl)]),
         "alfd_inner_prec_apply": (C.c_int, [vp, C.c_int, vp, vp]),
         "alfd_matrix_lanes": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
@@ -374,6 +375,21 @@ class Context:
         y = np.ascontiguousarray(y, np.float64).copy()
         self._ck(self._lib.alfd_spmv(self._h, slot, x.ctypes.data, y.ctypes.data, mode, alpha))
         return y, lanes.value
+
+    def spmv_scaled(self, slot, x, d, y, y2=None):
+        """The diagonal-scaled epilogues (alfd_spmv_scaled): y = d .* (A x), or with y2 given y = A x and
+        y2 = d .* (A x).  y (and y2) are uploaded as given before the launch; returns y or (y, y2), as copies."""
+        x = np.ascontiguousarray(x, np.float64)
+        d = np.ascontiguousarray(d, np.float64)
+        y = np.ascontiguousarray(y, np.float64).copy()
+        if d.size != y.size or (y2 is not None and np.size(y2) != y.size):
+            raise ValueError("d, y and y2 have the row count of the slot")
+        if y2 is None:
+            self._ck(self._lib.alfd_spmv_scaled(self._h, slot, x.ctypes.data, d.ctypes.data, y.ctypes.data, None))
+            return y
+        y2 = np.ascontiguousarray(y2, np.float64).copy()
+        self._ck(self._lib.alfd_spmv_scaled(self._h, slot, x.ctypes.data, d.ctypes.data, y.ctypes.data, y2.ctypes.data))
+        return y, y2
 
     def dot(self, x, y):
         x = np.ascontiguousarray(x, np.float64)

@@ -451,6 +451,13 @@ int alfd_get_history(alfd_ctx_t ctx, double *out, int32_t capacity, int32_t *cou
  * (SURVEY.md 8(a) a13/a14).  y = A x (mode 0) or y += alpha A x (mode 1).  On a partitioned context
  * alfd_spmv is collective: x holds this rank's owned columns of the slot's column block, y its rows. */
 int alfd_spmv(alfd_ctx_t ctx, int slot, const double *x, double *y, int mode, double alpha);
+/* The two diagonal-scaled epilogues of the same kernels, which carry the augmented-Lagrangian and the nested
+ * grad-div terms of the solver (t = W^-1 .* (C x), q = Mp_lumped^-1 .* (B u)): with y2 == NULL y = d .* (A x); with
+ * y2 != NULL y = A x and y2 = d .* (A x).  d, y and y2 have the slot's (this rank's) row count.  Goes through the
+ * solver's own dispatch (storage form, halo overlap, tunables); collective on a partitioned context like alfd_spmv.
+ * y and y2 are uploaded as given before the launch.  ALFD_E_INVALID for a null ctx, x, d or y, an unset slot, and
+ * y2 == y (the kernels take both as restrict pointers). */
+int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d, double *y, double *y2);
 int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double *result);
 /* z = M^-1 r: ONE application of the preconditioner of the inner CG, with no CG around it -- exactly the operator
  * the configured variant's inner solve calls once per iteration (alfd_config::inner_prec: identity, Jacobi, the

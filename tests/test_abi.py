@@ -63,6 +63,17 @@ def test_argument_validation_without_gpu():
     assert (_abi.INNER_OP_AUG, _abi.INNER_OP_A22, _abi.INNER_OP_AUG2) == (0, 1, 2)
     hdr = open(os.path.join(ROOT, "include", "alfd", "alfd.h")).read()
     assert "ALFD_INNER_OP_AUG = 0, ALFD_INNER_OP_A22 = 1, ALFD_INNER_OP_AUG2 = 2" in hdr
+    # the scaled-epilogue primitive: a null context is refused before anything is read, whatever the other pointers
+    # are; null x / d / y, an unset slot and y2 == y on a live context need a GPU (tests/test_gpu_spmv_epilogues.py)
+    p = z.ctypes.data
+    for args in ((p, p, p, None), (p, p, p, p), (None, p, p, None), (p, None, p, None), (p, p, None, None),
+                 (None, None, None, None)):
+        assert lib.alfd_spmv_scaled(None, _abi.A, *args) == _abi.E_INVALID, args
+    assert lib.alfd_spmv_scaled(None, -1, p, p, p, None) == _abi.E_INVALID
+    assert "alfd_spmv_scaled" in solver.ABI_SYMBOLS and "alfd_spmv_scaled" in _declared_symbols()
+    assert re.search(r"int alfd_spmv_scaled\(alfd_ctx_t ctx, int slot, const double \*x, const double \*d, double \*y, "
+                     r"double \*y2\);", hdr)
+    assert lib.alfd_spmv_scaled.argtypes == [C.c_void_p, C.c_int] + [C.c_void_p] * 4     # the mirror resolves it
 
 
 def test_no_cpu_fallback():

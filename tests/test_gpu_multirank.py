@@ -14,6 +14,7 @@ import pytest
 import cases
 from fictitious_domain_al_preconditioners_amd import _abi, partition, problems, solver
 from oracle import oracle
+from spmv_reference import Case
 
 pytestmark = pytest.mark.gpu
 
@@ -243,7 +244,10 @@ def test_partitioned_batch_major_spmv_bitwise(built, world, overlap, monkeypatch
     """The A-SpMV of a partition large enough for the LDS-window / batch-major formats (>= 256 row blocks per
     rank; the solves above are too small for them): halo columns inside the staged x windows, mesh-brick row
     blocks per rank.  Every rank's rows must equal the unpartitioned product bit for bit -- with the halo exchange
-    running beside the interior row blocks (the default on this transport) and with ALFD_SPMV_OVERLAP_HALO=0."""
+    running beside the interior row blocks (the default on this transport) and with ALFD_SPMV_OVERLAP_HALO=0.  The
+    split launch passes its epilogue to both halves: besides y = A x also y += alpha A x, y = d .* (A x) and the pair
+    y = A x, y2 = d .* (A x), each rank with its slice of d and of the prefilled y (NaN for the overwriting epilogues),
+    against the references of spmv_reference.Case on the unpartitioned matrix."""
     if overlap is not None:
         monkeypatch.setenv("ALFD_SPMV_OVERLAP_HALO", overlap)     # read when a context is created
     n, ref = 28 + 8 * (world - 2), 0
@@ -252,8 +256,11 @@ def test_partitioned_batch_major_spmv_bitwise(built, world, overlap, monkeypatch
     a = full.mats["A"]
     x = np.random.default_rng(3).uniform(-1, 1, a.ncols)
     want, _ = oracle.spmv(a, x, None, mode=0)
+    case = Case(a, 17)                  # inputs and references of the scaled epilogues, on the unpartitioned matrix
+    want1, _ = oracle.spmv(a, case.x, case.y0, mode=1, alpha=-0.75)
     group = solver.LocalGroup(world)
     out, fmt, errs = [None] * world, [None] * world, []
+    out1, out2, out3 = [None] * world, [None] * world, [None] * world
     uoff = plan.offsets[0]
 
     def work(rank):
@@ -268,6 +275,11 @@ def test_partitioned_batch_major_spmv_bitwise(built, world, overlap, monkeypatch
             fmt[rank] = ctx.matrix_info(_abi.A)
             xl = x[uoff[rank]:uoff[rank + 1]]
             out[rank], _ = ctx.spmv(_abi.A, xl, np.zeros(pb.mats["A"].nrows), mode=0)
+            rows = slice(uoff[rank], uoff[rank + 1])
+            nan = np.full(pb.mats["A"].nrows, np.nan)
+            out1[rank], _ = ctx.spmv(_abi.A, case.x[rows], case.y0[rows], mode=1, alpha=-0.75)
+            out2[rank] = ctx.spmv_scaled(_abi.A, case.x[rows], case.d[rows], nan)
+            out3[rank] = ctx.spmv_scaled(_abi.A, case.x[rows], case.d[rows], nan, nan)
             ctx.close()
         except Exception as e:   # noqa: BLE001
             errs.append((rank, repr(e)))
@@ -283,6 +295,10 @@ def test_partitioned_batch_major_spmv_bitwise(built, world, overlap, monkeypatch
     # the row blocks without a halo column lead the plan: they run while the exchange is in flight
     assert all(0 < f["batch_major_interior_blocks"] < f["batch_major_blocks"] for f in fmt), fmt
     assert np.array_equal(np.concatenate(out), want)
+    assert np.array_equal(np.concatenate(out1), want1)
+    case.check_scaled(np.concatenate(out2), "epilogue 2")
+    assert np.array_equal(np.concatenate([y for y, _ in out3]), case.s)
+    case.check_scaled(np.concatenate([y2 for _, y2 in out3]), "epilogue 3: y2")
 
 
 def _run_interface_ranks(world, plan, make_local, cfg):

@@ -57,7 +57,8 @@ def test_spmv_bitwise(ctxs, name, mode):
 def test_batch_major_format_bitwise(built, blocks):
     """The batch-major value-indexed format (kernels_vs.hpp, tunable batch_major): row blocks as runs of
     the numbering, as mesh bricks handed in through alfd_set_row_blocks, and as ragged random-size
-    blocks of a random row permutation; every epilogue; against the oracle's canonical SpMV."""
+    blocks of a random row permutation; epilogues 0 and 1 (the diagonal-scaled epilogues 2 and 3:
+    tests/test_gpu_spmv_epilogues.py); against the oracle's canonical SpMV."""
     big = problems.generate(dim=3, degree=2, ncomp=3, n_cells=20, stokes=False, grad_div=True,
                             gamma_grad_div=10.0, radius=0.1, immersed_refine=0)
     m = big.mats["A"]
@@ -147,7 +148,7 @@ def test_batch_major_format_edge_rows_bitwise(built):
 def test_batch_major_short_rows_bitwise(built, kind):
     """spmv_vss_kernel: the batch-major form for short rows (canonical L = 32 / 16 / 8 lanes per row): one stored
     template row per batch of translate rows.  Stencil operators of uniform grids, and one with every 7th row
-    perturbed (rows without a translate partner are batches of one); both epilogues; against the oracle."""
+    perturbed (rows without a translate partner are batches of one); epilogues 0 and 1; against the oracle."""
     gen = {"lap3d_L32": dict(dim=3, degree=1, ncomp=1, n_cells=74), "q2_2d_L16": dict(dim=2, degree=2, ncomp=1, n_cells=365),
            "lap2d_L8": dict(dim=2, degree=1, ncomp=1, n_cells=724), "lap3d_perturbed": dict(dim=3, degree=1, ncomp=1, n_cells=74)}[kind]
     m = problems.generate(radius=0.1, **gen).mats["A"]
@@ -179,7 +180,8 @@ def test_batch_major_short_rows_bitwise(built, kind):
 def test_divergence_and_gradient_blocks_bitwise(built):
     """B and Bt of the Stokes system at a size where the storage formats apply (N = 36: 50 653 pressure rows): B takes the
     batch-major form with blocks split for their x windows, Bt (short rows) whichever of its two forms the upload-time
-    timing keeps; both equal the oracle's canonical SpMV bit for bit, in every epilogue the solver uses."""
+    timing keeps; both equal the oracle's canonical SpMV bit for bit, in epilogues 0 and 1 (B under the scale of the
+    nested grad-div term, epilogue 2: tests/test_gpu_spmv_epilogues.py)."""
     pb = problems.stokes3d_sphere(n_cells=36, immersed_refine=2)
     ctx = solver.Context(0)
     try:
