@@ -265,12 +265,20 @@ struct alfd_ctx {
   int spec_host_stepped = 0;        // "spectrum_host_stepped" = 1: the same CG through the host-stepped pcg()
   // RationalPreconditioner state (batched CG over the 21 immersed systems)
   HostCsr h_M, h_K;                                    // host copies of the (tiny) immersed matrices
-  // multilevel inner preconditioner
-  std::vector<int32_t> ml_agg[ALFD_MAX_LEVELS];
-  std::vector<double> ml_wgt[ALFD_MAX_LEVELS];
-  int64_t ml_ncoarse[ALFD_MAX_LEVELS] = {0, 0, 0, 0, 0, 0, 0, 0};
-  HostCsr ml_P[ALFD_MAX_LEVELS];               // CSR prolongator of a level (alfd_set_prolongator), replaces its aggregates
-  DevCsr ml_inv;                               // explicit inverse of the coarsest operator (alfd_config::ml_coarse_direct)
+  // multilevel inner preconditioner: hier[0] on the augmented (1,1) block (A, C, Ct, gamma), hier[1] on the immersed
+  // block A22 = A2 + gamma2 M invW M of the elliptic variants (A2, M, M, gamma2; CSR prolongators, one rank)
+  struct Hierarchy {
+    std::vector<int32_t> agg[ALFD_MAX_LEVELS];
+    std::vector<double> wgt[ALFD_MAX_LEVELS];
+    int64_t ncoarse[ALFD_MAX_LEVELS] = {0, 0, 0, 0, 0, 0, 0, 0};
+    HostCsr P[ALFD_MAX_LEVELS];                // CSR prolongator of a level (alfd_set_prolongator), replaces its aggregates
+    DevCsr inv;                                // explicit inverse of the coarsest operator (alfd_config::ml_coarse_direct)
+    std::vector<MlLevel> ml;
+    TailTable *tail_tab = nullptr;             // level descriptors of ml_tail_kernel (hierarchy 1; setup workspace)
+    void clear_input() {
+      for (int l = 0; l < ALFD_MAX_LEVELS; ++l) agg[l].clear(), wgt[l].clear(), P[l] = HostCsr(), ncoarse[l] = 0;
+    }
+  } hier[2];
   // interface patch (alfd_config::ml_patch_degree > 0): S = non-empty rows of Ct, vectors of length |S|
   struct Patch {
     bool on = false;
@@ -290,11 +298,12 @@ struct alfd_ctx {
     DevCsr Cts_loc, Ctg;
     double *send = nullptr, *stage = nullptr, *lam_send = nullptr, *lam_stage = nullptr, *loc = nullptr;
   } patch;
-  std::vector<MlLevel> ml;
   int ml_rep_level = -1;                      // first replicated level (multi-rank), -1: none
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
   int ml_fuse = 1;                            // fused smoother steps: aug_tail_kernel ("ml_fuse", ALFD_ML_FUSE)
+  int ml_tail_rows = 0;                       // "ml_tail_rows": levels >= 1 of hierarchy 1 with at most this many unknowns
+                                              // run in one launch (ml_tail_kernel); 0 = off (the measured default)
   int ml_gpu_galerkin = 1;                    // Galerkin products of CSR-prolongator levels on the device (ALFD_ML_GPU_GALERKIN)
   double *g_w = nullptr, *g_tlam = nullptr;   // global W^-1 diagonal and multiplier work vector of the replicated levels
   std::vector<int64_t> ml_coff[ALFD_MAX_LEVELS];       // rank offsets of the coarse dofs of each level
@@ -316,6 +325,7 @@ struct alfd_ctx {
   double lambda_max = 0, lambda_min = 0;
   // stats of the current solve
   int64_t inner_its = 0, mp_its = 0;
+  int64_t inner_its_op[3] = {0, 0, 0};            // inner_its by alfd_inner_op (alfd_get_inner_iterations)
   int inner_failures = 0, precond_applications = 0;
   std::vector<double> history;
   // timing
@@ -1114,8 +1124,20 @@ static int cheb_apply(alfd_ctx *ctx, int op, const double *r, double *z, int64_t
 
 // deal.II SolverCG via inverse_operator (zero initial guess) [EXT]; b and x are
 // padded device vectors of the operator's span.
-static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z);
+static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z);
 static int ml_apply(alfd_ctx *ctx, const double *r, double *z);
+// ALFD_PREC_MULTILEVEL on the inner operator op: the augmented (1,1) block always; A22 and the 2-block operator of the ideal
+// variant when the immersed hierarchy is set up (setup() refuses the ideal variant without it), else the Chebyshev sweep
+static bool ml_covers(const alfd_ctx *ctx, int op) {
+  return op == OP_AUG || ((op == OP_A22 || op == OP_AUG2) && !ctx->hier[1].ml.empty());
+}
+// z = M^-1 r there: the V-cycle of the block, and for the 2-block operator the block diagonal z = [ml_apply(r0); V1(r1)]
+// ({{AMG_A1, 0}, {0, AMG_A2}}, elliptic_interface.cc:930-942)
+static int ml_prec(alfd_ctx *ctx, int op, const double *r, double *z) {
+  if (op == OP_A22) return ml_cycle(ctx, 1, 0, r, z);
+  RC(ml_apply(ctx, r, z));
+  return op == OP_AUG2 ? ml_cycle(ctx, 1, 0, r + ctx->off[1], z + ctx->off[1]) : ALFD_OK;
+}
 // rec (alfd_estimate_spectrum only): the CG coefficients alpha_j, beta_j come back with the readback of r.r, and a
 // step with p.Ap <= 0 (or NaN) ends the solve as FAILURE at the step before it.
 struct CgRecord {
@@ -1147,8 +1169,8 @@ static int pcg(alfd_ctx *ctx, int op, int prec, const alfd_control &ctrl, const 
     } else if (prec == ALFD_PREC_JACOBI) {
       VEC_LAUNCH(jacobi_dot_kernel, npad, 24, dinv, r, z, ctx->partial);
       RC(finish_dots(ctx, nb, 1, 0, FIN_RZ));
-    } else if (prec == ALFD_PREC_MULTILEVEL && op == OP_AUG) {
-      RC(ml_apply(ctx, r, z));
+    } else if (prec == ALFD_PREC_MULTILEVEL && ml_covers(ctx, op)) {
+      RC(ml_prec(ctx, op, r, z));
       RC(dot_async(ctx, npad, r, z, 0, FIN_RZ));
     } else {
       RC(cheb_apply(ctx, op, r, z, npad));
@@ -1188,6 +1210,8 @@ static int inner_solve(alfd_ctx *ctx, int op, const double *b, double *x) {
   RC(pcg(ctx, op, mp ? (int)ALFD_PREC_JACOBI : ctx->cfg.inner_prec, mp ? ctx->cfg.mp_inner : ctx->cfg.inner, b,
          x, &its, &st, &res));
   (mp ? ctx->mp_its : ctx->inner_its) += its;
+  if (op == OP_AUG || op == OP_A22 || op == OP_AUG2)
+    ctx->inner_its_op[op == OP_AUG ? ALFD_INNER_OP_AUG : op == OP_A22 ? ALFD_INNER_OP_A22 : ALFD_INNER_OP_AUG2] += its;
   if (ctx->cfg.log_level >= 3 && ctx->rank == 0)
     std::printf("DEAL:%s:cg::%s step %d value %.17g\n", mp ? "mp" : "aug",
                 st == SUCCESS ? "Convergence" : "Failure", its, res);
@@ -3507,10 +3531,13 @@ static int power_iteration(alfd_ctx *ctx, int op) {
 // high-degree Chebyshev sweep.  Every piece is a fixed polynomial in SPD
 // operators, so the preconditioner is a fixed SPD operator and plain CG applies.
 static void free_levels(alfd_ctx *ctx) {
-  for (MlLevel &L : ctx->ml)
-    for (DevCsr *m : {&L.A, &L.C, &L.Ct, &L.P, &L.R, &L.gA, &L.gC, &L.gCt, &L.gP, &L.gR}) csr_free(*m);
-  ctx->ml.clear();
-  csr_free(ctx->ml_inv);
+  for (alfd_ctx::Hierarchy &H : ctx->hier) {
+    for (MlLevel &L : H.ml)
+      for (DevCsr *m : {&L.A, &L.C, &L.Ct, &L.P, &L.R, &L.gA, &L.gC, &L.gCt, &L.gP, &L.gR}) csr_free(*m);
+    H.ml.clear();
+    H.tail_tab = nullptr;   // setup workspace
+    csr_free(H.inv);
+  }
   for (DevCsr *m : {&ctx->patch.Ass, &ctx->patch.As, &ctx->patch.Ats, &ctx->patch.Cs, &ctx->patch.Cts, &ctx->patch.Cts_loc,
                     &ctx->patch.Ctg})
     csr_free(*m);
@@ -3554,8 +3581,9 @@ static int ensure_window_plan(alfd_ctx *ctx, DevCsr &m) {
 }
 static int ensure_window_plans(alfd_ctx *ctx) {
   for (DevCsr &m : ctx->mat) RC(ensure_window_plan(ctx, m));
-  for (MlLevel &L : ctx->ml)
-    for (DevCsr *m : {&L.A, &L.gA}) RC(ensure_window_plan(ctx, *m));
+  for (alfd_ctx::Hierarchy &H : ctx->hier)
+    for (MlLevel &L : H.ml)
+      for (DevCsr *m : {&L.A, &L.gA}) RC(ensure_window_plan(ctx, *m));
   return ALFD_OK;
 }
 
@@ -3668,6 +3696,7 @@ struct AugOp {   // the operands of one factored operator and the sweep vectors 
   DevCsr *A = nullptr, *C = nullptr, *Ct = nullptr;
   int clsA = ALFD_T_SPMV_OTHER;
   const double *w = nullptr;   // invW over the multipliers that C addresses
+  double gamma = 0;            // the penalty weight: gamma, or gamma2 on the immersed hierarchy
   double *tlam = nullptr;      // invW .* (C x)
   const uint8_t *mask = nullptr;
   int64_t npad = 0;
@@ -3685,18 +3714,20 @@ struct LevelView {
   double *rc = nullptr, *zc = nullptr;
 };
 
-// Levels from ml_rep_level on are replicated.  The level above the first replicated one keeps the rank-local pair:
-// ml_cycle gathers the restricted residual there.
-static LevelView level_view(alfd_ctx *ctx, int l) {
-  MlLevel &L = ctx->ml[l];
-  const bool rep = ctx->ml_rep_level >= 0 && l >= ctx->ml_rep_level;
+// Hierarchy h = 1 (the immersed block) reads (A2, M, M, gamma2) where hierarchy 0 reads (A, C, Ct, gamma); it is never
+// partitioned.  Levels of hierarchy 0 from ml_rep_level on are replicated.  The level above the first replicated one
+// keeps the rank-local pair: ml_cycle gathers the restricted residual there.
+static LevelView level_view(alfd_ctx *ctx, int h, int l) {
+  MlLevel &L = ctx->hier[h].ml[l];
+  const bool rep = h == 0 && ctx->ml_rep_level >= 0 && l >= ctx->ml_rep_level;
   LevelView V;
   AugOp &F = V.op;
-  F.A = rep ? &L.gA : l == 0 ? &ctx->mat[ALFD_A] : &L.A;
-  F.C = rep ? &L.gC : l == 0 ? &ctx->mat[ALFD_C] : &L.C;
-  F.Ct = rep ? &L.gCt : l == 0 ? &ctx->mat[ALFD_CT] : &L.Ct;
-  F.clsA = l == 0 ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
+  F.A = rep ? &L.gA : l > 0 ? &L.A : &ctx->mat[h == 0 ? ALFD_A : ALFD_A2];
+  F.C = rep ? &L.gC : l > 0 ? &L.C : &ctx->mat[h == 0 ? ALFD_C : ALFD_M];
+  F.Ct = rep ? &L.gCt : l > 0 ? &L.Ct : &ctx->mat[h == 0 ? ALFD_CT : ALFD_M];
+  F.clsA = l == 0 && h == 0 ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
   F.w = rep ? ctx->g_w : ctx->diag[ALFD_INVW];
+  F.gamma = h == 0 ? ctx->cfg.gamma : ctx->cfg.gamma2;
   F.tlam = rep ? ctx->g_tlam : ctx->t_lam;
   F.mask = L.tail_mask;
   F.npad = rep ? L.gnpad : L.npad;
@@ -3704,8 +3735,8 @@ static LevelView level_view(alfd_ctx *ctx, int l) {
   F.cd = rep ? L.gcd : L.cd, F.cres = rep ? L.gcres : L.cres, F.ctmp = rep ? L.gctmp : L.ctmp;
   F.lmax = L.lmax;
   V.r = rep ? L.gr : L.r, V.z = rep ? L.gz : L.z, V.t = rep ? L.gt : L.t;
-  if (l + 1 < (int)ctx->ml.size()) {
-    MlLevel &N = ctx->ml[l + 1];
+  if (l + 1 < (int)ctx->hier[h].ml.size()) {
+    MlLevel &N = ctx->hier[h].ml[l + 1];
     V.R = rep ? &N.gR : &N.R, V.P = rep ? &N.gP : &N.P;
     V.rc = rep ? N.gr : N.r, V.zc = rep ? N.gz : N.z;
   }
@@ -3718,6 +3749,7 @@ static AugOp patch_aug(alfd_ctx *ctx) {
   F.A = &Q.Ass, F.C = &Q.Cs, F.Ct = &Q.Cts;
   F.w = Q.rep ? ctx->g_w : ctx->diag[ALFD_INVW];       // replicated patch: the whole multiplier space
   F.tlam = Q.rep ? ctx->g_tlam : ctx->t_lam;
+  F.gamma = ctx->cfg.gamma;
   F.mask = Q.tail_mask;
   F.npad = Q.mpad;
   F.dinv = Q.dinv;
@@ -3737,7 +3769,7 @@ static int fused_AC(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) {
 static int aug_apply(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) {
   if (ctx->cfg.aug_assembled) return spmv_m(ctx, *F.A, F.clsA, x, y, 0);   // operator form: A already holds the AL term
   RC(fused_AC(ctx, F, x, y));
-  return spmv_m(ctx, *F.Ct, ALFD_T_SPMV_OTHER, F.tlam, y, 1, ctx->cfg.gamma);
+  return spmv_m(ctx, *F.Ct, ALFD_T_SPMV_OTHER, F.tlam, y, 1, F.gamma);
 }
 
 // ---- fused smoother steps ("ml_fuse").  One application of a factored operator inside a Chebyshev
@@ -3801,7 +3833,7 @@ static int cheb_fused(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, c
     RC(fused_AC(ctx, F, j == 1 ? z : F.cd, F.ctmp));
     AugTailArgs p;
     k.step(p.c1, p.c2);
-    p.gamma = ctx->cfg.gamma;
+    p.gamma = F.gamma;
     p.dinv = F.dinv, p.y = F.ctmp, p.rin = j == 1 ? r : F.cres, p.din = j == 1 ? z : F.cd;
     p.res = F.cres, p.d = F.cd, p.z = z, p.zout = zout;
     const bool last = j == degree - 1;
@@ -3821,7 +3853,7 @@ static int aug_cheb(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, con
 // t = r - Aug x, where t holds A x and tlam holds invW .* (C x)
 static int fused_residual(alfd_ctx *ctx, const AugOp &F, const double *r, double *t) {
   AugTailArgs p;
-  p.gamma = ctx->cfg.gamma, p.y = t, p.rin = r, p.res = t;
+  p.gamma = F.gamma, p.y = t, p.rin = r, p.res = t;
   return aug_tail(ctx, F, TAIL_RES, p, 24.0);
 }
 
@@ -3829,7 +3861,7 @@ static int fused_residual(alfd_ctx *ctx, const AugOp &F, const double *r, double
 static int fused_correct(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *r, double *t, double *zc,
                          double *zout) {
   AugTailArgs p;
-  p.gamma = ctx->cfg.gamma, p.c1 = 1.0 / ChebCoef(F.lmax, ratio).theta;
+  p.gamma = F.gamma, p.c1 = 1.0 / ChebCoef(F.lmax, ratio).theta;
   p.dinv = F.dinv, p.y = t, p.rin = r, p.res = t, p.z = zc, p.zout = zout;
   p.store_res = degree > 1;
   if (degree <= 1 && zout) return aug_tail(ctx, F, TAIL_RES_INIT_ADD, p, 24.0 + 32.0 + 24.0);
@@ -3851,14 +3883,87 @@ static int build_tail_mask(alfd_ctx *ctx, const DevCsr &m, int64_t npad, uint8_t
   return ALFD_OK;
 }
 
-// z = V-cycle(r) on level l
-static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
+// ---- the coarse tail of hierarchy 1 in one launch ("ml_tail_rows", ml_tail_kernel)
+static_assert(kTailMaxLevels == ALFD_MAX_LEVELS + 1, "TailTable holds every level of a hierarchy");
+
+// ml_tail_kernel walks the CSR arrays of m: everything spmv_launch_local runs on spmv_kernel or, for 64-lane rows, on
+// the streaming kernel (which reads the same arrays and forms the canonical sums)
+static bool tail_form(const DevCsr &m) { return m.present && !m.vs.on && !m.win; }
+
+static TailCsr tail_csr(const DevCsr &m) {
+  TailCsr t;
+  t.rp = m.rp, t.col = m.col, t.val = m.val, t.rows = m.sparse ? m.rows : nullptr;
+  t.n_list = m.n_list, t.nrows = m.nrows;
+  t.L = m.L, t.sparse = m.sparse ? 1 : 0;
+  return t;
+}
+
+// The level descriptors: operands as level_view() names them, Chebyshev coefficients as cheb_sweep() steps them
+static int build_tail_table(alfd_ctx *ctx) {
   const alfd_config &c = ctx->cfg;
-  const int last = (int)ctx->ml.size() - 1;
-  const LevelView L = level_view(ctx, l);
+  alfd_ctx::Hierarchy &H = ctx->hier[1];
+  const int last = (int)H.ml.size() - 1;
+  std::vector<TailTable> tab(1);
+  TailTable &T = tab[0];
+  std::memset(&T, 0, sizeof(T));
+  T.nlev = last + 1;
+  T.has_inv = H.inv.present ? 1 : 0;
+  if (H.inv.present) T.inv = tail_csr(H.inv);
+  for (int l = 1; l <= last; ++l) {
+    const LevelView V = level_view(ctx, 1, l);
+    TailLevel &F = T.lev[l];
+    F.A = tail_csr(*V.op.A), F.C = tail_csr(*V.op.C), F.Ct = tail_csr(*V.op.Ct);
+    if (l < last) F.R = tail_csr(*V.R), F.P = tail_csr(*V.P);
+    F.dinv = V.op.dinv, F.w = V.op.w, F.tlam = V.op.tlam;
+    F.r = V.r, F.z = V.z, F.t = V.t, F.cd = V.op.cd, F.cres = V.op.cres, F.ctmp = V.op.ctmp;
+    F.gamma = V.op.gamma, F.npad = V.op.npad;
+    F.degree = l == last ? c.ml_coarse_degree : c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
+    ChebCoef k(V.op.lmax, l == last ? c.ml_coarse_ratio : c.ml_smooth_ratio);
+    F.inv_theta = 1.0 / k.theta;
+    for (int j = 1; j < F.degree && j <= kTailMaxDegree; ++j) k.step(F.c1[j - 1], F.c2[j - 1]);
+  }
+  double *q = nullptr;
+  RC(ws_alloc_zero(ctx, &q, (int64_t)((sizeof(TailTable) + 7) / 8)));
+  H.tail_tab = reinterpret_cast<TailTable *>(q);
+  HIPC(hipMemcpyAsync(H.tail_tab, &T, sizeof(TailTable), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));   // T leaves scope
+  return ALFD_OK;
+}
+
+// May ml_tail_kernel take levels l .. last of hierarchy 1, called with (r, z)?  Every operator there in CSR form, the
+// factored diagonal-weight operator on one rank (as fused_ok), coefficients within the descriptor.
+static bool tail_ok(alfd_ctx *ctx, int l, const double *r, const double *z) {
+  const alfd_config &c = ctx->cfg;
+  alfd_ctx::Hierarchy &H = ctx->hier[1];
+  const int last = (int)H.ml.size() - 1;
+  if (!H.tail_tab || l < 1 || H.ml[l].n > ctx->ml_tail_rows || r != H.ml[l].r || z != H.ml[l].z) return false;
+  if (ctx->nranks != 1 || c.aug_assembled || c.w_inverse != ALFD_W_DIAGONAL) return false;
+  const int sdeg = c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
+  if (sdeg - 1 > kTailMaxDegree || (!H.inv.present && c.ml_coarse_degree - 1 > kTailMaxDegree)) return false;
+  if (H.inv.present && !tail_form(H.inv)) return false;
+  for (int j = l; j <= last; ++j) {
+    const MlLevel &L = H.ml[j];
+    if (!tail_form(L.A) || !tail_form(L.C) || !tail_form(L.Ct)) return false;
+    if (j > l && (!tail_form(L.R) || !tail_form(L.P))) return false;
+  }
+  return true;
+}
+
+// z = V-cycle(r) on level l of hierarchy h
+static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
+  const alfd_config &c = ctx->cfg;
+  alfd_ctx::Hierarchy &H = ctx->hier[h];
+  const int last = (int)H.ml.size() - 1;
+  if (h == 1 && ctx->ml_tail_rows > 0 && tail_ok(ctx, l, r, z)) {
+    Timer tm(ctx, ALFD_T_SPMV_OTHER, 0.0);
+    hipLaunchKernelGGL(ml_tail_kernel, dim3(1), dim3(kTailBlock), 0, ctx->stream, H.tail_tab, l);
+    HIPC(hipGetLastError());
+    return ALFD_OK;
+  }
+  const LevelView L = level_view(ctx, h, l);
   const AugOp &F = L.op;
   if (l == last) {
-    if (ctx->ml_inv.present) return spmv_m(ctx, ctx->ml_inv, ALFD_T_SPMV_OTHER, r, z, 0);   // z = Aug_c^-1 r
+    if (H.inv.present) return spmv_m(ctx, H.inv, ALFD_T_SPMV_OTHER, r, z, 0);   // z = Aug_c^-1 r
     return aug_cheb(ctx, F, c.ml_coarse_degree, c.ml_coarse_ratio, r, z);
   }
   const int sdeg = l > 0 && c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
@@ -3872,9 +3977,9 @@ static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
     VEC_LAUNCH(sub_from_kernel, F.npad, 24, r, L.t);                         // t = r - Aug z
   }
   RC(spmv_m(ctx, *L.R, ALFD_T_SPMV_OTHER, L.t, L.rc, 0));                    // r_c = P^T t
-  if (l + 1 == ctx->ml_rep_level) {
+  if (h == 0 && l + 1 == ctx->ml_rep_level) {
     // the restricted residual is gathered once; everything below runs replicated, without exchanges
-    MlLevel &N = ctx->ml[l + 1];
+    MlLevel &N = H.ml[l + 1];
     HIPC(hipMemcpyAsync(N.g_send, N.r, N.n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
     RC(comm_allgather(ctx, N.g_send, N.g_stage, (size_t)N.g_maxpiece * sizeof(double)));
     for (int p = 0; p < ctx->nranks; ++p) {
@@ -3883,11 +3988,11 @@ static int ml_cycle(alfd_ctx *ctx, int l, const double *r, double *z) {
         HIPC(hipMemcpyAsync(N.gr + N.g_offs[p], N.g_stage + (int64_t)p * N.g_maxpiece, np * sizeof(double),
                             hipMemcpyDeviceToDevice, ctx->stream));
     }
-    RC(ml_cycle(ctx, l + 1, N.gr, N.gz));
+    RC(ml_cycle(ctx, h, l + 1, N.gr, N.gz));
     // z += P e_c: aggregates -> my slice of e_c; CSR prolongators address the replicated vector by global ids
     RC(spmv_m(ctx, N.P, ALFD_T_SPMV_OTHER, N.P_global_cols ? N.gz : N.gz + N.g_offs[ctx->rank], z, 1, 1.0));
   } else {
-    RC(ml_cycle(ctx, l + 1, L.rc, L.zc));
+    RC(ml_cycle(ctx, h, l + 1, L.rc, L.zc));
     RC(spmv_m(ctx, *L.P, ALFD_T_SPMV_OTHER, L.zc, z, 1, 1.0));               // z += P e_c
   }
   if (fuse) {
@@ -3939,7 +4044,7 @@ static int ml_apply_rep(alfd_ctx *ctx, const double *r, double *z) {
     RC(spmv_m(ctx, Q.Cs, ALFD_T_SPMV_OTHER, Q.zS, ctx->g_tlam, 2, 0.0, ctx->g_w));
     RC(spmv_m(ctx, Q.Ctg, ALFD_T_SPMV_OTHER, ctx->g_tlam, Q.rr, 1, -ctx->cfg.gamma));
   }
-  RC(ml_cycle(ctx, 0, Q.rr, z));
+  RC(ml_cycle(ctx, 0, 0, Q.rr, z));
   if (Q.m_loc > 0) hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m_loc, Q.S, Q.zS + s0, z);
   RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.loc, 0));                          // my rows of (A z) on S
   if (pen) {
@@ -3957,7 +4062,7 @@ static int ml_apply_rep(alfd_ctx *ctx, const double *r, double *z) {
 
 static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   alfd_ctx::Patch &Q = ctx->patch;
-  if (!Q.on) return ml_cycle(ctx, 0, r, z);
+  if (!Q.on) return ml_cycle(ctx, 0, 0, r, z);
   if (Q.rep) return ml_apply_rep(ctx, r, z);
   const int64_t n0p = pad_chunk(ctx->n[0]);
   const unsigned gm = (unsigned)((Q.m + 255) / 256);
@@ -3974,7 +4079,7 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
     RC(spmv_m(ctx, Q.Cs, ALFD_T_SPMV_OTHER, Q.zS, ctx->t_lam, 2, 0.0, w));
     RC(spmv(ctx, ALFD_CT, ctx->t_lam, Q.rr, 1, -ctx->cfg.gamma));                 // rr -= gamma Ct W^-1 C[:,S] zS
   }
-  RC(ml_cycle(ctx, 0, Q.rr, z));
+  RC(ml_cycle(ctx, 0, 0, Q.rr, z));
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.zS, z);
   RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));                           // (Aug z) on S
   if (fused_ok(ctx, F)) {
@@ -4572,7 +4677,8 @@ static int constraint_residual(alfd_ctx *ctx, const double *const *x_blocks, con
 // Explicit inverse of the coarsest Aug_c = A_c + gamma Ct_c W^-1 C_c: dense Cholesky on the host, every entry a
 // sequential fma chain (the oracle repeats the loops), uploaded as a dense CSR so that z = Aug_c^-1 r runs in
 // the canonical SpMV order.  ML solves its coarsest level directly as well (KLU, utilities.h:304-317).
-static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, const HostCsr &Ct, const std::vector<double> &w) {
+static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, const HostCsr &Ct, const std::vector<double> &w,
+                          double gamma, DevCsr &inv) {
   const int64_t n = A.nrows;
   std::vector<double> D((size_t)n * n, 0.0);
   for (int64_t i = 0; i < n; ++i)
@@ -4581,7 +4687,7 @@ static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, con
     for (int64_t i = 0; i < n; ++i)
       for (int64_t k = Ct.rp[i]; k < Ct.rp[i + 1]; ++k) {
         const int64_t lam = Ct.col[k];
-        const double sfac = (ctx->cfg.gamma * w[lam]) * Ct.val[k];
+        const double sfac = (gamma * w[lam]) * Ct.val[k];
         for (int64_t e = C.rp[lam]; e < C.rp[lam + 1]; ++e)
           D[i * n + C.col[e]] = std::fma(sfac, C.val[e], D[i * n + C.col[e]]);
       }
@@ -4640,7 +4746,7 @@ static int coarse_inverse(alfd_ctx *ctx, const HostCsr &A, const HostCsr &C, con
       });
     for (auto &x : th) x.join();
   }
-  RC(upload_level_part(ctx, ctx->ml_inv, X, nullptr, true));   // never partitioned: every rank that has it has it whole
+  RC(upload_level_part(ctx, inv, X, nullptr, true));   // never partitioned: every rank that has it has it whole
   return ALFD_OK;
 }
 
@@ -5425,22 +5531,22 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
   const alfd_config &c = ctx->cfg;
   const int P = ctx->nranks, rk = ctx->rank, last = ctx->nblocks - 1;
   for (int l = 0; l < nlev; ++l)
-    if (ctx->ml_P[l].rp.empty())
+    if (ctx->hier[0].P[l].rp.empty())
       return ctx->err = "partitioned context: CSR prolongators and aggregates cannot be mixed", ALFD_E_UNSUPPORTED;
   const std::vector<int64_t> &off0 = ctx->part[0], &coff = ctx->ml_coff[0];
-  const HostCsr &P0 = ctx->ml_P[0];
+  const HostCsr &P0 = ctx->hier[0].P[0];
   const int64_t n_loc = ctx->n[0], n1 = P0.ncols;
   if ((int)coff.size() != P + 1 || coff.back() != n1 || P0.nrows != n_loc)
     return ctx->err = "partitioned CSR prolongator: level 0 needs this rank's rows and alfd_set_aggregate_partition(0, coarse offsets)",
            ALFD_E_INVALID;
   for (int l = 1; l < nlev; ++l)
-    if (ctx->ml_P[l].nrows != ctx->ml_P[l - 1].ncols)
+    if (ctx->hier[0].P[l].nrows != ctx->hier[0].P[l - 1].ncols)
       return ctx->err = "partitioned CSR prolongator: levels >= 1 must be given whole on every rank", ALFD_E_INVALID;
   free_levels(ctx);
-  ctx->ml.assign(nlev + 1, MlLevel());
+  ctx->hier[0].ml.assign(nlev + 1, MlLevel());
   // ---- level 0 (partitioned): vectors only, operators are the slots
   {
-    MlLevel &L = ctx->ml[0];
+    MlLevel &L = ctx->hier[0].ml[0];
     L.n = n_loc;
     L.npad = pad_chunk(n_loc);
     for (double **v : {&L.r, &L.z, &L.t, &L.cd, &L.cres, &L.ctmp}) RC(ws_alloc_zero(ctx, v, L.npad));
@@ -5552,7 +5658,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
     HostCsr Rg = Rl;
     Rg.ncols = off0.back();
     for (size_t k = 0; k < Rg.col.size(); ++k) Rg.col[k] = (int32_t)colgA[Rl.col[k]];
-    MlLevel &N = ctx->ml[1];
+    MlLevel &N = ctx->hier[0].ml[1];
     PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
     RC(upload_level_part(ctx, N.R, Rg, off0.data(), false));
     RC(upload_level_part(ctx, N.P, P0, nullptr, true));
@@ -5566,7 +5672,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
   ctx->ml_rep_level = 1;
   HostCsr A = std::move(A1), C = std::move(C1), Ct = std::move(Ct1), An, Cn, Ctn, R;
   for (int l = 1; l <= nlev; ++l) {
-    MlLevel &L = ctx->ml[l];
+    MlLevel &L = ctx->hier[0].ml[l];
     L.gn = A.nrows;
     L.gnpad = pad_chunk(L.gn);
     L.g_offs.assign(P + 1, 0);
@@ -5595,7 +5701,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
       double *v = L.gt, *wv = L.gr;
       hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((L.gn + 255) / 256)), dim3(256), 0, ctx->stream, L.gn, (int64_t)0, v);
       double lam = 0;
-      const AugOp F = level_view(ctx, l).op;
+      const AugOp F = level_view(ctx, 0, l).op;
       RC(power_lambda(ctx, L.gnpad, L.gdinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
       L.lmax = lam * c.cheb_safety;
       HIPC(hipMemsetAsync(L.gt, 0, L.gnpad * sizeof(double), ctx->stream));
@@ -5608,7 +5714,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
       RC(ws_alloc_zero(ctx, &L.g_stage, L.g_maxpiece * P));
     }
     if (l == nlev) break;
-    const HostCsr &Pm = ctx->ml_P[l];
+    const HostCsr &Pm = ctx->hier[0].P[l];
     {
       PhaseClock pg(ctx, ALFD_SETUP_ML_GALERKIN);
       HostCsr AP;
@@ -5618,7 +5724,7 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
       RC(product(ctx, C, Pm, Cn));
       transpose_host(Cn, Ctn);
     }
-    MlLevel &N = ctx->ml[l + 1];
+    MlLevel &N = ctx->hier[0].ml[l + 1];
     PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
     RC(upload_level_part(ctx, N.gP, Pm, nullptr, true));
     RC(upload_level_part(ctx, N.gR, R, nullptr, true));
@@ -5627,18 +5733,105 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
     C = std::move(Cn);
     Ct = std::move(Ctn);
   }
-  if (c.ml_coarse_direct > 0 && ctx->ml[nlev].gn > 0 && ctx->ml[nlev].gn <= c.ml_coarse_direct) {
+  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].gn > 0 && ctx->hier[0].ml[nlev].gn <= c.ml_coarse_direct) {
     PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
     std::vector<double> w(lam_global);
     HIPC(hipMemcpyAsync(w.data(), ctx->g_w, w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
-    RC(coarse_inverse(ctx, A, C, Ct, w));
-    ctx->ml_inv.rep = true;
+    RC(coarse_inverse(ctx, A, C, Ct, w, c.gamma, ctx->hier[0].inv));
+    ctx->hier[0].inv.rep = true;
   }
   if (c.ml_patch_degree > 0) {
     PhaseClock pc(ctx, ALFD_SETUP_ML_PATCH);
     RC(patch_setup_rep(ctx));
   }
+  return ALFD_OK;
+}
+
+// Vectors of level l of hierarchy h (n unknowns, the first of them the global index goff).  Level 0 takes 1 / diag and
+// lambda_max from its inner operator; a level below gets 1 / diag(Aug_l) and lambda_max(D^-1 Aug_l) by power iteration
+// from the integer-hash vector (global index) -- its operators are in place by then.
+static int level_init(alfd_ctx *ctx, int h, int l, int64_t n, int64_t goff) {
+  const alfd_config &c = ctx->cfg;
+  MlLevel &L = ctx->hier[h].ml[l];
+  L.n = n;
+  L.npad = pad_chunk(n);
+  RC(ws_alloc_zero(ctx, &L.r, L.npad));
+  RC(ws_alloc_zero(ctx, &L.z, L.npad));
+  RC(ws_alloc_zero(ctx, &L.t, L.npad));
+  RC(ws_alloc_zero(ctx, &L.cd, L.npad));
+  RC(ws_alloc_zero(ctx, &L.cres, L.npad));
+  RC(ws_alloc_zero(ctx, &L.ctmp, L.npad));
+  if (l == 0) {
+    L.dinv = h == 0 ? ctx->dinv_aug : ctx->dinv_a22;
+    L.lmax = ctx->lam_max[h == 0 ? OP_AUG : OP_A22];
+    return ALFD_OK;
+  }
+  PhaseClock pc(ctx, ALFD_SETUP_ML_LAMBDA);
+  RC(ws_alloc_zero(ctx, &L.dinv, L.npad));
+  const AugOp F = level_view(ctx, h, l).op;
+  RC(diag_plus_m(ctx, L.A, L.Ct, c.aug_assembled ? 0.0 : F.gamma, n, L.dinv));
+  double *v = L.t, *wv = L.r;
+  if (n > 0)
+    hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, goff, v);
+  double lam = 0;
+  RC(power_lambda(ctx, L.npad, L.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
+  L.lmax = lam * c.cheb_safety;
+  HIPC(hipMemsetAsync(L.t, 0, L.npad * sizeof(double), ctx->stream));
+  HIPC(hipMemsetAsync(L.r, 0, L.npad * sizeof(double), ctx->stream));
+  return ALFD_OK;
+}
+
+// The next level Nx through a general CSR prolongator Pm (single rank): A_c = P^T (A P), C_c = C P, Ct_c = C_c^T from the
+// device operators dA, dC.  The three products run on the device (spgemm_rows_kernel; results fetched for the format
+// planner) when gpu_products allows and they fit, else on the host from hA / hC (null: fetched from the device here).
+// An, Cn, Ctn return the host copies of the new level.
+static int csr_level(alfd_ctx *ctx, const HostCsr &Pm, DevCsr &dA, DevCsr &dC, bool gpu_products, const HostCsr *hA,
+                     const HostCsr *hC, MlLevel &Nx, HostCsr &An, HostCsr &Cn, HostCsr &Ctn) {
+  HostCsr R;
+  {
+    PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
+    transpose_host(Pm, R);
+    RC(upload_level_part(ctx, Nx.P, Pm, nullptr, true));
+    RC(upload_level_part(ctx, Nx.R, R, nullptr, true));
+  }
+  bool done = false;
+  if (gpu_products && !dA.sparse && !dC.sparse && !Nx.P.sparse && !Nx.R.sparse && dA.nnz > 0) {
+    PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
+    DevRawCsr AP, RAP, CP;
+    bool f1 = false, f2 = false, f3 = false;
+    RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, AP, &f1));
+    if (f1) RC(dev_spgemm(ctx, Nx.R.nrows, Nx.R.rp, Nx.R.col, Nx.R.val, AP.rp, AP.col, AP.val, Pm.ncols, RAP, &f2));
+    AP.release();
+    if (f2) RC(dev_spgemm(ctx, dC.nrows, dC.rp, dC.col, dC.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, CP, &f3));
+    if (f3) {
+      RC(download_raw(ctx, RAP, An));
+      RC(download_raw(ctx, CP, Cn));
+      transpose_host(Cn, Ctn);
+      done = true;
+    }
+    RAP.release();
+    CP.release();
+  }
+  if (!done) {
+    HostCsr fA, fC;
+    if (!hA || !hC) {
+      PhaseClock pc(ctx, ALFD_SETUP_ML_FETCH);
+      if (!hA) RC(download_csr(ctx, dA, fA));
+      if (!hC) RC(download_csr(ctx, dC, fC));
+    }
+    PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
+    HostCsr AP;
+    spgemm_host(hA ? *hA : fA, Pm, AP);
+    spgemm_host(R, AP, An);
+    AP = HostCsr();
+    spgemm_host(hC ? *hC : fC, Pm, Cn);
+    transpose_host(Cn, Ctn);
+  }
+  PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
+  RC(upload_level_part(ctx, Nx.A, An, nullptr, false));
+  RC(upload_level_part(ctx, Nx.C, Cn, nullptr, false));
+  RC(upload_level_part(ctx, Nx.Ct, Ctn, nullptr, false));
   return ALFD_OK;
 }
 
@@ -5652,8 +5845,8 @@ static int ml_setup(alfd_ctx *ctx) {
   if (c.ml_patch_degree > 0 && !(c.ml_patch_ratio > 1.0)) return ctx->err = "bad ml_patch_ratio", ALFD_E_INVALID;
   int nlev = 0;
   bool any_P = false;
-  while (nlev < ALFD_MAX_LEVELS && (!ctx->ml_agg[nlev].empty() || !ctx->ml_P[nlev].rp.empty())) {
-    any_P = any_P || !ctx->ml_P[nlev].rp.empty();
+  while (nlev < ALFD_MAX_LEVELS && (!ctx->hier[0].agg[nlev].empty() || !ctx->hier[0].P[nlev].rp.empty())) {
+    any_P = any_P || !ctx->hier[0].P[nlev].rp.empty();
     ++nlev;
   }
   if (nlev == 0)
@@ -5667,22 +5860,22 @@ static int ml_setup(alfd_ctx *ctx) {
   if (ctx->nranks > 1) {
     off[0] = ctx->part[0];
     for (int l = 0; l < nlev; ++l) {
-      if ((int)ctx->ml_coff[l].size() != ctx->nranks + 1 || ctx->ml_coff[l].back() != ctx->ml_ncoarse[l])
+      if ((int)ctx->ml_coff[l].size() != ctx->nranks + 1 || ctx->ml_coff[l].back() != ctx->hier[0].ncoarse[l])
         return ctx->err = "alfd_set_aggregate_partition missing or inconsistent for level " + std::to_string(l),
                ALFD_E_INVALID;
       off[l + 1] = ctx->ml_coff[l];
     }
   } else {
     off[0] = {0, ctx->n[0]};
-    for (int l = 0; l < nlev; ++l) off[l + 1] = {0, ctx->ml_ncoarse[l]};
+    for (int l = 0; l < nlev; ++l) off[l + 1] = {0, ctx->hier[0].ncoarse[l]};
   }
   for (int l = 0; l < nlev; ++l) {
-    const bool isP = !ctx->ml_P[l].rp.empty();
-    if ((isP ? ctx->ml_P[l].nrows : (int64_t)ctx->ml_agg[l].size()) != off[l][rk + 1] - off[l][rk])
+    const bool isP = !ctx->hier[0].P[l].rp.empty();
+    if ((isP ? ctx->hier[0].P[l].nrows : (int64_t)ctx->hier[0].agg[l].size()) != off[l][rk + 1] - off[l][rk])
       return ctx->err = "aggregates / prolongator of level " + std::to_string(l) + " do not match this rank's unknowns", ALFD_E_INVALID;
   }
   free_levels(ctx);
-  ctx->ml.assign(nlev + 1, MlLevel());
+  ctx->hier[0].ml.assign(nlev + 1, MlLevel());
   // multi-rank: levels with few unknowns are replicated on every rank after the partitioned build
   // (their kernels take microseconds, their halo exchanges would dominate)
   int rep_from = -1;
@@ -5714,7 +5907,7 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(download_csr(ctx, ctx->mat[ALFD_CT], Ct));
   }
   const bool gpu_products = ctx->ml_gpu_galerkin && ctx->nranks == 1;
-  if (!gpu_products || ctx->ml_P[0].rp.empty()) RC(fetch_A(ctx->mat[ALFD_A]));
+  if (!gpu_products || ctx->hier[0].P[0].rp.empty()) RC(fetch_A(ctx->mat[ALFD_A]));
   const int64_t lam0 = ctx->nranks > 1 ? ctx->part[last][rk] : 0;
   const int64_t lam_global = ctx->nranks > 1 ? ctx->part[last].back() : ctx->n[last];
   if (c.ml_patch_degree > 0) {
@@ -5722,81 +5915,14 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(patch_setup(ctx, have_host_A ? &A : nullptr, C, Ct));
   }
   for (int l = 0; l <= nlev; ++l) {
-    MlLevel &L = ctx->ml[l];
+    MlLevel &L = ctx->hier[0].ml[l];
     const int64_t n = off[l][rk + 1] - off[l][rk];
-    L.n = n;
-    L.npad = pad_chunk(n);
-    RC(ws_alloc_zero(ctx, &L.r, L.npad));
-    RC(ws_alloc_zero(ctx, &L.z, L.npad));
-    RC(ws_alloc_zero(ctx, &L.t, L.npad));
-    RC(ws_alloc_zero(ctx, &L.cd, L.npad));
-    RC(ws_alloc_zero(ctx, &L.cres, L.npad));
-    RC(ws_alloc_zero(ctx, &L.ctmp, L.npad));
-    if (l == 0) {
-      L.dinv = ctx->dinv_aug;
-      L.lmax = ctx->lam_max[OP_AUG];
-    } else {
-      PhaseClock pc(ctx, ALFD_SETUP_ML_LAMBDA);
-      RC(ws_alloc_zero(ctx, &L.dinv, L.npad));
-      RC(diag_plus_m(ctx, L.A, L.Ct, c.aug_assembled ? 0.0 : c.gamma, n, L.dinv));
-      // lambda_max(D^-1 Aug_l): power iteration from the integer-hash vector (global index)
-      double *v = L.t, *wv = L.r;
-      if (n > 0)
-        hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n,
-                           off[l][rk], v);
-      double lam = 0;
-      const AugOp F = level_view(ctx, l).op;
-      RC(power_lambda(ctx, L.npad, L.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
-      L.lmax = lam * c.cheb_safety;
-      HIPC(hipMemsetAsync(L.t, 0, L.npad * sizeof(double), ctx->stream));
-      HIPC(hipMemsetAsync(L.r, 0, L.npad * sizeof(double), ctx->stream));
-    }
+    RC(level_init(ctx, 0, l, n, off[l][rk]));
     if (l == nlev) break;
-    if (!ctx->ml_P[l].rp.empty()) {
-      // ---- next level through a general CSR prolongator (single rank): A_c = P^T (A P), C_c = C P, Ct_c = C_c^T
-      const HostCsr &Pm = ctx->ml_P[l];
-      MlLevel &Nx = ctx->ml[l + 1];
-      DevCsr &dA = l == 0 ? ctx->mat[ALFD_A] : L.A;
-      DevCsr &dC = l == 0 ? ctx->mat[ALFD_C] : L.C;
-      {
-        PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
-        transpose_host(Pm, R);
-        RC(upload_level_part(ctx, Nx.P, Pm, nullptr, true));
-        RC(upload_level_part(ctx, Nx.R, R, nullptr, true));
-      }
-      bool done = false;
-      if (gpu_products && !dA.sparse && !dC.sparse && !Nx.P.sparse && !Nx.R.sparse && dA.nnz > 0) {
-        // the three products on the device (spgemm_rows_kernel), results fetched for the format planner
-        PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
-        DevRawCsr AP, RAP, CP;
-        bool f1 = false, f2 = false, f3 = false;
-        RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, AP, &f1));
-        if (f1) RC(dev_spgemm(ctx, Nx.R.nrows, Nx.R.rp, Nx.R.col, Nx.R.val, AP.rp, AP.col, AP.val, Pm.ncols, RAP, &f2));
-        AP.release();
-        if (f2) RC(dev_spgemm(ctx, dC.nrows, dC.rp, dC.col, dC.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, CP, &f3));
-        if (f3) {
-          RC(download_raw(ctx, RAP, An));
-          RC(download_raw(ctx, CP, Cn));
-          transpose_host(Cn, Ctn);
-          done = true;
-        }
-        RAP.release();
-        CP.release();
-      }
-      if (!done) {
-        if (l == 0) RC(fetch_A(dA));
-        PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
-        HostCsr AP;
-        spgemm_host(A, Pm, AP);
-        spgemm_host(R, AP, An);
-        AP = HostCsr();
-        spgemm_host(C, Pm, Cn);
-        transpose_host(Cn, Ctn);
-      }
-      PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
-      RC(upload_level_part(ctx, Nx.A, An, nullptr, false));
-      RC(upload_level_part(ctx, Nx.C, Cn, nullptr, false));
-      RC(upload_level_part(ctx, Nx.Ct, Ctn, nullptr, false));
+    if (!ctx->hier[0].P[l].rp.empty()) {
+      // ---- next level through a general CSR prolongator (single rank)
+      RC(csr_level(ctx, ctx->hier[0].P[l], l == 0 ? ctx->mat[ALFD_A] : L.A, l == 0 ? ctx->mat[ALFD_C] : L.C, gpu_products,
+                   have_host_A ? &A : nullptr, &C, ctx->hier[0].ml[l + 1], An, Cn, Ctn));
       if (l + 1 < nlev) {
         A = std::move(An);      // host copies of the new level: the next level's fallback product, aggregation levels
         have_host_A = true;
@@ -5807,8 +5933,8 @@ static int ml_setup(alfd_ctx *ctx) {
     }
     // ---- next level: Galerkin products of this rank's rows
     if (l == 0) RC(fetch_A(ctx->mat[ALFD_A]));
-    const std::vector<int32_t> &aggG = ctx->ml_agg[l];  // owned fine dof -> GLOBAL coarse id (or -1)
-    const double *w = ctx->ml_wgt[l].empty() ? nullptr : ctx->ml_wgt[l].data();
+    const std::vector<int32_t> &aggG = ctx->hier[0].agg[l];  // owned fine dof -> GLOBAL coarse id (or -1)
+    const double *w = ctx->hier[0].wgt[l].empty() ? nullptr : ctx->hier[0].wgt[l].data();
     if (w && ctx->nranks > 1) return ctx->err = "weighted aggregates are single-rank for now", ALFD_E_UNSUPPORTED;
     const int64_t c0 = off[l + 1][rk], nc_loc = off[l + 1][rk + 1] - c0, nc_glob = off[l + 1].back();
     std::vector<int32_t> agg_rows(n);  // owned fine dof -> LOCAL coarse row
@@ -5846,7 +5972,7 @@ static int ml_setup(alfd_ctx *ctx) {
     }
     transpose_host(P, R);
     ctx->setup_s[ALFD_SETUP_ML_GALERKIN] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count();
-    MlLevel &Nx = ctx->ml[l + 1];
+    MlLevel &Nx = ctx->hier[0].ml[l + 1];
     PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
     RC(upload_level_part(ctx, Nx.A, An, off[l + 1].data(), false));
     RC(upload_level_part(ctx, Nx.C, Cn, off[l + 1].data(), false));
@@ -5867,13 +5993,13 @@ static int ml_setup(alfd_ctx *ctx) {
       RC(download_csr(ctx, Nx.Ct, Ct));
     }
   }
-  if (c.ml_coarse_direct > 0 && ctx->ml[nlev].n > 0 && ctx->ml[nlev].n <= c.ml_coarse_direct) {
+  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].n > 0 && ctx->hier[0].ml[nlev].n <= c.ml_coarse_direct) {
     // An / Cn / Ctn still hold the coarsest level (global = local column ids on one rank)
     std::vector<double> w(ctx->n[last]);
     HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
-    RC(coarse_inverse(ctx, An, Cn, Ctn, w));
+    RC(coarse_inverse(ctx, An, Cn, Ctn, w, c.gamma, ctx->hier[0].inv));
   }
   if (rep_from > 0) {
     // ---- replicate levels rep_from .. nlev: gather operators, diagonals and W on every rank
@@ -5882,7 +6008,7 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(ws_alloc_zero(ctx, &ctx->g_tlam, lam_pad));
     RC(gather_vec(ctx, ctx->diag[ALFD_INVW], ctx->n[last], ctx->g_w));
     for (int l = rep_from; l <= nlev; ++l) {
-      MlLevel &L = ctx->ml[l];
+      MlLevel &L = ctx->hier[0].ml[l];
       L.g_offs = off[l];
       L.gn = off[l].back();
       L.gnpad = pad_chunk(L.gn);
@@ -5913,8 +6039,52 @@ static int ml_setup(alfd_ctx *ctx) {
     ctx->ml_rep_level = rep_from;
   }
   for (int l = 0; l <= nlev; ++l)
-    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->ml[l].Ct, ctx->ml[l].npad, &ctx->ml[l].tail_mask));
+    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].Ct, ctx->hier[0].ml[l].npad, &ctx->hier[0].ml[l].tail_mask));
   return ALFD_OK;
+}
+
+// The second hierarchy (ALFD_PREC_MULTILEVEL on an elliptic variant): the V-cycle for A22 = A2 + gamma2 M invW M, built
+// from (A2, M, M, invW, gamma2) by the steps hierarchy 0 takes on (A, C, Ct, invW, gamma) -- level_init, csr_level, the
+// explicit coarsest inverse, the masks of the fused smoother.  CSR prolongators, one rank, no interface patch (M touches
+// every row).  Without prolongators of block 1 there is no such hierarchy and A22 keeps the Chebyshev sweep.
+static int ml_setup_immersed(alfd_ctx *ctx) {
+  const alfd_config &c = ctx->cfg;
+  alfd_ctx::Hierarchy &H = ctx->hier[1];
+  int nlev = 0;
+  H.tail_tab = nullptr;
+  while (nlev < ALFD_MAX_LEVELS && !H.P[nlev].rp.empty()) ++nlev;
+  if (nlev == 0) return ALFD_OK;
+  if (!is_elliptic(c.variant))
+    return ctx->err = "a block-1 hierarchy needs the immersed operators A2 and M of the elliptic-interface variants", ALFD_E_INVALID;
+  if (ctx->nranks > 1) return ctx->err = "the block-1 hierarchy is single-rank", ALFD_E_UNSUPPORTED;
+  for (int l = 0; l < nlev; ++l)
+    if (H.P[l].nrows != (l == 0 ? ctx->n[1] : H.P[l - 1].ncols))
+      return ctx->err = "block-1 prolongator of level " + std::to_string(l) + " does not match the unknowns of that level",
+             ALFD_E_INVALID;
+  H.ml.assign(nlev + 1, MlLevel());
+  const bool gpu_products = ctx->ml_gpu_galerkin != 0;
+  HostCsr An, Cn, Ctn, A, C;
+  for (int l = 0; l <= nlev; ++l) {
+    MlLevel &L = H.ml[l];
+    RC(level_init(ctx, 1, l, l == 0 ? ctx->n[1] : H.ncoarse[l - 1], 0));
+    if (l == nlev) break;
+    RC(csr_level(ctx, H.P[l], l == 0 ? ctx->mat[ALFD_A2] : L.A, l == 0 ? ctx->mat[ALFD_M] : L.C, gpu_products,
+                 l == 0 ? nullptr : &A, l == 0 ? nullptr : &C, H.ml[l + 1], An, Cn, Ctn));
+    if (l + 1 < nlev) {
+      A = std::move(An);
+      C = std::move(Cn);
+    }
+  }
+  if (c.ml_coarse_direct > 0 && H.ml[nlev].n <= c.ml_coarse_direct) {
+    std::vector<double> w(ctx->n[2]);
+    HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
+    RC(coarse_inverse(ctx, An, Cn, Ctn, w, c.gamma2, H.inv));
+  }
+  for (int l = 0; l <= nlev; ++l)
+    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].Ct, H.ml[l].npad, &H.ml[l].tail_mask));
+  return build_tail_table(ctx);
 }
 
 static int setup(alfd_ctx *ctx) {
@@ -6170,7 +6340,9 @@ static int setup(alfd_ctx *ctx) {
       HIPC(hipMemcpyAsync(ctx->dinv_aug2 + ctx->off[1], ctx->dinv_a22, pad_chunk(ctx->n[1]) * sizeof(double),
                           hipMemcpyDeviceToDevice, ctx->stream));
       if (cheb) RC(power_iteration(ctx, OP_AUG2));
-    } else if (cheb) {
+    }
+    // the modified variant's two inner CGs; the ideal one's block-diagonal multilevel preconditioner smooths with them too
+    if (cheb && (c.variant == ALFD_AL_ELL_MODIFIED || c.inner_prec == ALFD_PREC_MULTILEVEL)) {
       RC(power_iteration(ctx, OP_AUG));
       RC(power_iteration(ctx, OP_A22));
     }
@@ -6181,9 +6353,12 @@ static int setup(alfd_ctx *ctx) {
   diag_clock.reset();
   free_levels(ctx);
   if (c.inner_prec == ALFD_PREC_MULTILEVEL) {
-    if (c.variant == ALFD_AL_ELL_IDEAL)
-      return ctx->err = "multilevel inner preconditioner: not for the 2x2 block CG of the ideal variant", ALFD_E_UNSUPPORTED;
+    if (c.variant == ALFD_AL_ELL_IDEAL &&
+        (ctx->hier[1].P[0].rp.empty() || (ctx->hier[0].P[0].rp.empty() && ctx->hier[0].agg[0].empty())))
+      return ctx->err = "multilevel inner preconditioner: the 2x2 block CG of the ideal variant needs a hierarchy on both "
+                        "blocks (alfd_set_prolongator_block)", ALFD_E_UNSUPPORTED;
     RC(ml_setup(ctx));
+    RC(ml_setup_immersed(ctx));
   }
   HIPC(hipStreamSynchronize(ctx->stream));
   ctx->is_setup = true;
@@ -6209,6 +6384,7 @@ static int to_host(alfd_ctx *ctx, const double *dev, double *const *blocks) {
 
 static void reset_stats(alfd_ctx *ctx) {
   ctx->inner_its = ctx->mp_its = 0;
+  ctx->inner_its_op[0] = ctx->inner_its_op[1] = ctx->inner_its_op[2] = 0;
   ctx->inner_failures = ctx->precond_applications = 0;
   ctx->rational_its = 0;
   ctx->mass_its = 0;
@@ -6512,46 +6688,76 @@ int alfd_set_aggregates(alfd_ctx_t ctx, int level, int64_t n_fine, const int32_t
   if (level < 0 || level >= ALFD_MAX_LEVELS || n_fine < 1 || n_coarse < 1 || !agg) return ALFD_E_INVALID;
   for (int64_t i = 0; i < n_fine; ++i)
     if (agg[i] < -1 || agg[i] >= n_coarse) return ctx->err = "aggregate id out of range", ALFD_E_INVALID;
-  ctx->ml_agg[level].assign(agg, agg + n_fine);
+  ctx->hier[0].agg[level].assign(agg, agg + n_fine);
   if (weight)
-    ctx->ml_wgt[level].assign(weight, weight + n_fine);
+    ctx->hier[0].wgt[level].assign(weight, weight + n_fine);
   else
-    ctx->ml_wgt[level].clear();
-  ctx->ml_ncoarse[level] = n_coarse;
-  ctx->ml_P[level] = HostCsr();
-  for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+    ctx->hier[0].wgt[level].clear();
+  ctx->hier[0].ncoarse[level] = n_coarse;
+  ctx->hier[0].P[level] = HostCsr();
+  for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) ctx->hier[0].agg[l].clear(), ctx->hier[0].wgt[l].clear(), ctx->hier[0].P[l] = HostCsr();
+  ctx->is_setup = false;
+  return ALFD_OK;
+}
+
+// block 1 (the immersed hierarchy): CSR prolongators only, one rank
+static int check_block(alfd_ctx_t ctx, int block) {
+  if (block != 0 && block != 1) return ctx->err = "multigrid hierarchy: block must be 0 or 1", ALFD_E_INVALID;
+  if (block == 1 && ctx->nranks > 1)
+    return ctx->err = "the block-1 (immersed) hierarchy is single-rank", ALFD_E_UNSUPPORTED;
+  return ALFD_OK;
+}
+
+int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_fine, int64_t n_coarse,
+                               const int64_t *row_ptr, const int32_t *col, const double *val) {
+  CHECK_CTX();
+  RC(check_block(ctx, block));
+  const std::string fn = block == 0 ? "alfd_set_prolongator" : "alfd_set_prolongator_block";   // block 0: the call behind alfd_set_prolongator
+  if (level < 0 || level >= ALFD_MAX_LEVELS || n_fine < 0 || n_coarse <= 0 || n_coarse > INT32_MAX || !row_ptr ||
+      row_ptr[0] != 0)
+    return ctx->err = fn + ": bad arguments", ALFD_E_INVALID;
+  for (int64_t i = 0; i < n_fine; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return ctx->err = fn + ": row_ptr must be monotone", ALFD_E_INVALID;
+  const int64_t nnz = row_ptr[n_fine];
+  if (nnz > 0 && (!col || !val)) return ctx->err = fn + ": col / val missing", ALFD_E_INVALID;
+  for (int64_t i = 0; i < n_fine; ++i)
+    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k)
+      if (col[k] < 0 || col[k] >= n_coarse || (k > row_ptr[i] && col[k] <= col[k - 1]))
+        return ctx->err = fn + ": columns must be ascending and inside [0, n_coarse)", ALFD_E_INVALID;
+  alfd_ctx::Hierarchy &H = ctx->hier[block];
+  HostCsr &P = H.P[level];
+  P.nrows = n_fine;
+  P.ncols = n_coarse;
+  P.rp.assign(row_ptr, row_ptr + n_fine + 1);
+  P.col.assign(col, col + nnz);
+  P.val.assign(val, val + nnz);
+  H.agg[level].clear();
+  H.wgt[level].clear();
+  H.ncoarse[level] = n_coarse;
+  for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) {   // levels below are redefined by later calls
+    H.agg[l].clear();
+    H.P[l] = HostCsr();
+  }
   ctx->is_setup = false;
   return ALFD_OK;
 }
 
 int alfd_set_prolongator(alfd_ctx_t ctx, int level, int64_t n_fine, int64_t n_coarse, const int64_t *row_ptr,
                          const int32_t *col, const double *val) {
+  return alfd_set_prolongator_block(ctx, 0, level, n_fine, n_coarse, row_ptr, col, val);
+}
+
+int alfd_clear_hierarchy(alfd_ctx_t ctx, int block) {
   CHECK_CTX();
-  if (level < 0 || level >= ALFD_MAX_LEVELS || n_fine < 0 || n_coarse <= 0 || n_coarse > INT32_MAX || !row_ptr ||
-      row_ptr[0] != 0)
-    return ctx->err = "alfd_set_prolongator: bad arguments", ALFD_E_INVALID;
-  for (int64_t i = 0; i < n_fine; ++i)
-    if (row_ptr[i + 1] < row_ptr[i]) return ctx->err = "alfd_set_prolongator: row_ptr must be monotone", ALFD_E_INVALID;
-  const int64_t nnz = row_ptr[n_fine];
-  if (nnz > 0 && (!col || !val)) return ctx->err = "alfd_set_prolongator: col / val missing", ALFD_E_INVALID;
-  for (int64_t i = 0; i < n_fine; ++i)
-    for (int64_t k = row_ptr[i]; k < row_ptr[i + 1]; ++k)
-      if (col[k] < 0 || col[k] >= n_coarse || (k > row_ptr[i] && col[k] <= col[k - 1]))
-        return ctx->err = "alfd_set_prolongator: columns must be ascending and inside [0, n_coarse)", ALFD_E_INVALID;
-  HostCsr &P = ctx->ml_P[level];
-  P.nrows = n_fine;
-  P.ncols = n_coarse;
-  P.rp.assign(row_ptr, row_ptr + n_fine + 1);
-  P.col.assign(col, col + nnz);
-  P.val.assign(val, val + nnz);
-  ctx->ml_agg[level].clear();
-  ctx->ml_wgt[level].clear();
-  ctx->ml_ncoarse[level] = n_coarse;
-  for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) {   // levels below are redefined by later calls
-    ctx->ml_agg[l].clear();
-    ctx->ml_P[l] = HostCsr();
-  }
+  if (block != 0 && block != 1) return ctx->err = "multigrid hierarchy: block must be 0 or 1", ALFD_E_INVALID;
+  ctx->hier[block].clear_input();
   ctx->is_setup = false;
+  return ALFD_OK;
+}
+
+int alfd_get_inner_iterations(alfd_ctx_t ctx, int64_t counts[3]) {
+  if (!ctx || !counts) return ALFD_E_INVALID;
+  std::copy(ctx->inner_its_op, ctx->inner_its_op + 3, counts);
   return ALFD_OK;
 }
 
@@ -6567,15 +6773,15 @@ int alfd_build_aggregates(alfd_ctx_t ctx, int32_t block_size, double threshold, 
   if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
   HostCsr A, An;
   RC(download_csr(ctx, ctx->mat[ALFD_A], A));
-  for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+  for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->hier[0].agg[l].clear(), ctx->hier[0].wgt[l].clear(), ctx->hier[0].P[l] = HostCsr();
   int nlev = 0;
   while (nlev < max_levels) {
     std::vector<int32_t> agg;
     int64_t nc = 0;
     aggregate_level(A, block_size, threshold, max_aggregate_nodes, agg, nc);
     if (nc < 1 || nc >= A.nrows) break;     // nothing left to coarsen
-    ctx->ml_agg[nlev] = agg;
-    ctx->ml_ncoarse[nlev] = nc;
+    ctx->hier[0].agg[nlev] = agg;
+    ctx->hier[0].ncoarse[nlev] = nc;
     ++nlev;
     if (nc <= min_coarse) break;
     galerkin(A, agg.data(), nullptr, nc, agg.data(), nullptr, nc, An);
@@ -6605,10 +6811,16 @@ int alfd_host_aggregate_level(int64_t nrows, const int64_t *rp, const int32_t *c
 }
 
 int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacity, int64_t *n_fine, int64_t *n_coarse) {
-  if (!ctx || level < 0 || level >= ALFD_MAX_LEVELS || ctx->ml_agg[level].empty()) return ALFD_E_INVALID;
-  const std::vector<int32_t> &a = ctx->ml_agg[level];
+  return alfd_get_aggregates_block(ctx, 0, level, agg, capacity, n_fine, n_coarse);
+}
+
+int alfd_get_aggregates_block(alfd_ctx_t ctx, int block, int level, int32_t *agg, int64_t capacity, int64_t *n_fine,
+                              int64_t *n_coarse) {
+  if (!ctx || (block != 0 && block != 1) || level < 0 || level >= ALFD_MAX_LEVELS || ctx->hier[block].agg[level].empty())
+    return ALFD_E_INVALID;
+  const std::vector<int32_t> &a = ctx->hier[block].agg[level];
   if (n_fine) *n_fine = (int64_t)a.size();
-  if (n_coarse) *n_coarse = ctx->ml_ncoarse[level];
+  if (n_coarse) *n_coarse = ctx->hier[block].ncoarse[level];
   if (agg) {
     if (capacity < (int64_t)a.size()) return ALFD_E_INVALID;
     std::copy(a.begin(), a.end(), agg);
@@ -6617,37 +6829,45 @@ int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacit
 }
 
 // alfd_build_smoothed_aggregation (tau = 0, cap = 0: nothing is truncated) and alfd_build_smoothed_aggregation_truncated
-static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
-                                      double damping, double tau, int32_t cap, int64_t min_coarse, int32_t max_levels,
-                                      int32_t *levels_out, double *omega_out) {
+// on (A, Ct, invW, gamma) for block 0, on (A2, M, invW, gamma2) for block 1 (alfd_build_smoothed_aggregation_block)
+static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_size, double threshold,
+                                      int32_t max_aggregate_nodes, double damping, double tau, int32_t cap, int64_t min_coarse,
+                                      int32_t max_levels, int32_t *levels_out, double *omega_out) {
   CHECK_CTX();
   if (ctx->nranks > 1) return ctx->err = "alfd_build_smoothed_aggregation is single-rank", ALFD_E_UNSUPPORTED;
+  RC(check_block(ctx, block));
+  alfd_ctx::Hierarchy &H = ctx->hier[block];
+  const int slotA = block == 0 ? ALFD_A : ALFD_A2, slotCt = block == 0 ? ALFD_CT : ALFD_M;
+  if (block == 1 && !ctx->mat[slotA].present)
+    return ctx->err = "a block-1 hierarchy needs slot A2 (the elliptic-interface variants)", ALFD_E_INVALID;
   if (ctx->configured && gd_nested(ctx))
     return ctx->err = "alfd_build_smoothed_aggregation: grad_div_in_A = 0 has no multilevel inner preconditioner", ALFD_E_UNSUPPORTED;
-  if (!ctx->mat[ALFD_A].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
+  if (!ctx->mat[slotA].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
   if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
       !(damping > 0.0) || !std::isfinite(damping))
     return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
   if (!(tau >= 0.0) || !(tau < 1.0) || cap < 0) {
-    for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+    H.clear_input();
     ctx->is_setup = false;
     return ctx->err = "alfd_build_smoothed_aggregation_truncated: drop_tolerance must be in [0, 1), max_row_entries >= 0",
            ALFD_E_INVALID;
   }
-  if (ctx->mat[ALFD_A].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
-  if (ctx->mat[ALFD_A].nrows != ctx->mat[ALFD_A].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
+  if (ctx->mat[slotA].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
+  if (ctx->mat[slotA].nrows != ctx->mat[slotA].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
   if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
   const int its = ctx->configured ? ctx->cfg.cheb_power_its : 20;
   if (its < 1) return ctx->err = "cheb_power_its must be >= 1", ALFD_E_INVALID;
   // the penalty term: an AL variant with a diagonal W^-1, a non-zero gamma, A not already augmented, Ct and W^-1 present
   const alfd_config &c = ctx->cfg;
+  const double gamma = block == 0 ? c.gamma : c.gamma2;
   const bool use_pen = ctx->configured && c.variant != ALFD_RATIONAL && c.w_inverse == ALFD_W_DIAGONAL &&
-                       !c.aug_assembled && c.gamma != 0.0 && ctx->mat[ALFD_CT].present && ctx->diag[ALFD_INVW];
+                       !c.aug_assembled && gamma != 0.0 && ctx->mat[slotCt].present && ctx->diag[ALFD_INVW] &&
+                       (block == 0 || is_elliptic(c.variant));
   HostCsr A, An, C, Ct, Cn, Q, P, R, AP;
   std::vector<double> w;
-  RC(download_csr(ctx, ctx->mat[ALFD_A], A));
+  RC(download_csr(ctx, ctx->mat[slotA], A));
   if (use_pen) {
-    RC(download_csr(ctx, ctx->mat[ALFD_CT], Ct));
+    RC(download_csr(ctx, ctx->mat[slotCt], Ct));
     if (Ct.nrows != A.nrows || ctx->diag_n[ALFD_INVW] != Ct.ncols)
       return ctx->err = "alfd_build_smoothed_aggregation: Ct / W^-1 do not match A", ALFD_E_INVALID;
     w.resize(Ct.ncols);
@@ -6656,7 +6876,7 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double
     HIPC(hipStreamSynchronize(ctx->stream));
     transpose_host(Ct, C);
   }
-  for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_wgt[l].clear(), ctx->ml_P[l] = HostCsr();
+  H.clear_input();
   ctx->is_setup = false;
   int nlev = 0;
   std::vector<double> d, f;
@@ -6666,11 +6886,11 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double
     aggregate_level(A, block_size, threshold, max_aggregate_nodes, agg, nc);
     if (nc < 1 || nc >= A.nrows) break;     // nothing left to coarsen
     SaPenalty pen;
-    if (use_pen) pen.Ct = &Ct, pen.C = &C, pen.w = w.data(), pen.gamma = c.gamma;
+    if (use_pen) pen.Ct = &Ct, pen.C = &C, pen.w = w.data(), pen.gamma = gamma;
     sa_diag(A, pen, d);
     const double lam = sa_lambda(A, pen, d, its);
     if (!(lam > 0.0) || !std::isfinite(lam)) {
-      for (int l = 0; l < ALFD_MAX_LEVELS; ++l) ctx->ml_agg[l].clear(), ctx->ml_P[l] = HostCsr();
+      H.clear_input();
       return ctx->err = "alfd_build_smoothed_aggregation: lambda_max(D^-1 Aug) of level " + std::to_string(nlev) +
                         " is not positive and finite (zero diagonal?)", ALFD_E_INVALID;
     }
@@ -6689,9 +6909,9 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double
     }
     Q = HostCsr();
     if (omega_out) omega_out[nlev] = omega;
-    ctx->ml_agg[nlev] = agg;
-    ctx->ml_P[nlev] = P;
-    ctx->ml_ncoarse[nlev] = nc;
+    H.agg[nlev] = agg;
+    H.P[nlev] = P;
+    H.ncoarse[nlev] = nc;
     ++nlev;
     if (nc <= min_coarse || nlev >= max_levels) break;
     // next level: A_{l+1} = P^T (A P), C_{l+1} = C P (the Galerkin products of alfd_setup, same order)
@@ -6714,7 +6934,7 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double
 int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
                                     double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
                                     double *omega_out) {
-  return build_smoothed_aggregation(ctx, block_size, threshold, max_aggregate_nodes, damping, 0.0, 0, min_coarse,
+  return build_smoothed_aggregation(ctx, 0, block_size, threshold, max_aggregate_nodes, damping, 0.0, 0, min_coarse,
                                     max_levels, levels_out, omega_out);
 }
 
@@ -6722,14 +6942,28 @@ int alfd_build_smoothed_aggregation_truncated(alfd_ctx_t ctx, int32_t block_size
                                               int32_t max_aggregate_nodes, double damping, double drop_tolerance,
                                               int32_t max_row_entries, int64_t min_coarse, int32_t max_levels,
                                               int32_t *levels_out, double *omega_out) {
-  return build_smoothed_aggregation(ctx, block_size, threshold, max_aggregate_nodes, damping, drop_tolerance,
+  return build_smoothed_aggregation(ctx, 0, block_size, threshold, max_aggregate_nodes, damping, drop_tolerance,
+                                    max_row_entries, min_coarse, max_levels, levels_out, omega_out);
+}
+
+int alfd_build_smoothed_aggregation_block(alfd_ctx_t ctx, int block, int32_t block_size, double threshold,
+                                          int32_t max_aggregate_nodes, double damping, double drop_tolerance,
+                                          int32_t max_row_entries, int64_t min_coarse, int32_t max_levels,
+                                          int32_t *levels_out, double *omega_out) {
+  return build_smoothed_aggregation(ctx, block, block_size, threshold, max_aggregate_nodes, damping, drop_tolerance,
                                     max_row_entries, min_coarse, max_levels, levels_out, omega_out);
 }
 
 int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
                          int64_t *n_fine, int64_t *n_coarse, int64_t *nnz) {
-  if (!ctx || level < 0 || level >= ALFD_MAX_LEVELS || ctx->ml_P[level].rp.empty()) return ALFD_E_INVALID;
-  const HostCsr &P = ctx->ml_P[level];
+  return alfd_get_prolongator_block(ctx, 0, level, row_ptr, col, val, capacity, n_fine, n_coarse, nnz);
+}
+
+int alfd_get_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t *row_ptr, int32_t *col, double *val,
+                               int64_t capacity, int64_t *n_fine, int64_t *n_coarse, int64_t *nnz) {
+  if (!ctx || (block != 0 && block != 1) || level < 0 || level >= ALFD_MAX_LEVELS || ctx->hier[block].P[level].rp.empty())
+    return ALFD_E_INVALID;
+  const HostCsr &P = ctx->hier[block].P[level];
   if (n_fine) *n_fine = P.nrows;
   if (n_coarse) *n_coarse = P.ncols;
   if (nnz) *nnz = P.nnz();
@@ -7042,8 +7276,8 @@ int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z) {
   } else if (prec == ALFD_PREC_JACOBI) {
     VEC_LAUNCH(jacobi_dot_kernel, npad, 24, op_dinv(ctx, kind), dr, dz, ctx->partial);
     HIPC(hipGetLastError());
-  } else if (prec == ALFD_PREC_MULTILEVEL && kind == OP_AUG) {
-    RC(ml_apply(ctx, dr, dz));
+  } else if (prec == ALFD_PREC_MULTILEVEL && ml_covers(ctx, kind)) {
+    RC(ml_prec(ctx, kind, dr, dz));
   } else {
     RC(cheb_apply(ctx, kind, dr, dz, npad));
   }
@@ -7659,6 +7893,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "ml_fuse") == 0) {   // 0: every smoother step as separate launches (same bits either way)
     ctx->ml_fuse = value != 0;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "ml_tail_rows") == 0) {   // 0: off; levels >= 1 of the immersed hierarchy up to this size in one launch
+    if (value < 0) return ctx->err = "ml_tail_rows: >= 0", ALFD_E_INVALID;
+    ctx->ml_tail_rows = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "nested_mp_group") == 0) {   // iterations of the device-stepped nested Mp CG per state read

@@ -1088,17 +1088,52 @@ __global__ __launch_bounds__(kBlock) void multi_axpy_kernel(const double *__rest
   }
 }
 
+// The element pair i, i + 1 of axpy_kernel, sub_from_kernel, cheb_init_kernel and cheb_step_kernel: the kernels below
+// and ml_tail_kernel (one workgroup, its own loop over the pairs) call the same bodies => same bits.
+__device__ __forceinline__ void axpy_pair(int64_t i, double a, const double *x, double *y) {
+  const double2 xv = ld2(x, i);
+  double2 yv = ld2(y, i);
+  yv.x = fma(a, xv.x, yv.x);
+  yv.y = fma(a, xv.y, yv.y);
+  st2(y, i, yv);
+}
+__device__ __forceinline__ void sub_from_pair(int64_t i, const double *b, double *v) {
+  const double2 bv = ld2(b, i);
+  double2 vv = ld2(v, i);
+  vv.x = bv.x - vv.x;
+  vv.y = bv.y - vv.y;
+  st2(v, i, vv);
+}
+__device__ __forceinline__ void cheb_init_pair(int64_t i, double inv_theta, const double *dinv, const double *r, double *d,
+                                               double *z, double *res, int keep_res) {
+  const double2 dv = ld2(dinv, i), rv = ld2(r, i);
+  double2 o;
+  o.x = inv_theta * (dv.x * rv.x);
+  o.y = inv_theta * (dv.y * rv.y);
+  st2(d, i, o);
+  st2(z, i, o);
+  if (keep_res) st2(res, i, rv);
+}
+__device__ __forceinline__ void cheb_step_pair(int64_t i, double c1, double c2, const double *dinv, const double *tmp,
+                                               double *res, double *d, double *z) {
+  const double2 dv = ld2(dinv, i), tv = ld2(tmp, i);
+  double2 rv = ld2(res, i), dd = ld2(d, i), zv = ld2(z, i);
+  rv.x = rv.x - tv.x;
+  rv.y = rv.y - tv.y;
+  dd.x = fma(c1, dd.x, c2 * (dv.x * rv.x));
+  dd.y = fma(c1, dd.y, c2 * (dv.y * rv.y));
+  zv.x = zv.x + dd.x;
+  zv.y = zv.y + dd.y;
+  st2(res, i, rv);
+  st2(d, i, dd);
+  st2(z, i, zv);
+}
+
 // y = fma(a, x, y); a = sc[ai] when sc != nullptr else aval
 __global__ __launch_bounds__(kBlock) void axpy_kernel(const double *__restrict__ sc, int ai, double aval,
                                                       const double *__restrict__ x, double *__restrict__ y) {
   const double a = sc ? sc[ai] : aval;
-  ALFD_FOR_PAIRS(i) {
-    const double2 xv = ld2(x, i);
-    double2 yv = ld2(y, i);
-    yv.x = fma(a, xv.x, yv.x);
-    yv.y = fma(a, xv.y, yv.y);
-    st2(y, i, yv);
-  }
+  ALFD_FOR_PAIRS(i) axpy_pair(i, a, x, y);
 }
 
 // x *= a  (a = 1/sc[ai] when inv, for the Arnoldi normalisation v /= ||v||)
@@ -1128,13 +1163,7 @@ __global__ __launch_bounds__(kBlock) void scale_copy_kernel(double a, const doub
 // v = b - v
 __global__ __launch_bounds__(kBlock) void sub_from_kernel(const double *__restrict__ b,
                                                           double *__restrict__ v) {
-  ALFD_FOR_PAIRS(i) {
-    const double2 bv = ld2(b, i);
-    double2 vv = ld2(v, i);
-    vv.x = bv.x - vv.x;
-    vv.y = bv.y - vv.y;
-    st2(v, i, vv);
-  }
+  ALFD_FOR_PAIRS(i) sub_from_pair(i, b, v);
 }
 
 // y = a * (d .* x)          (v2 = -gamma invW u2, ...preconditioner.h:32,66)
@@ -1221,15 +1250,7 @@ __global__ __launch_bounds__(kBlock) void cheb_init_kernel(double inv_theta, con
                                                            const double *__restrict__ r,
                                                            double *__restrict__ d, double *__restrict__ z,
                                                            double *__restrict__ res, int keep_res) {
-  ALFD_FOR_PAIRS(i) {
-    const double2 dv = ld2(dinv, i), rv = ld2(r, i);
-    double2 o;
-    o.x = inv_theta * (dv.x * rv.x);
-    o.y = inv_theta * (dv.y * rv.y);
-    st2(d, i, o);
-    st2(z, i, o);
-    if (keep_res) st2(res, i, rv);
-  }
+  ALFD_FOR_PAIRS(i) cheb_init_pair(i, inv_theta, dinv, r, d, z, res, keep_res);
 }
 // res -= tmp; d = fma(c1, d, c2 * (dinv .* res)); z += d
 __global__ __launch_bounds__(kBlock) void cheb_step_kernel(double c1, double c2,
@@ -1237,19 +1258,7 @@ __global__ __launch_bounds__(kBlock) void cheb_step_kernel(double c1, double c2,
                                                            const double *__restrict__ tmp,
                                                            double *__restrict__ res, double *__restrict__ d,
                                                            double *__restrict__ z) {
-  ALFD_FOR_PAIRS(i) {
-    const double2 dv = ld2(dinv, i), tv = ld2(tmp, i);
-    double2 rv = ld2(res, i), dd = ld2(d, i), zv = ld2(z, i);
-    rv.x = rv.x - tv.x;
-    rv.y = rv.y - tv.y;
-    dd.x = fma(c1, dd.x, c2 * (dv.x * rv.x));
-    dd.y = fma(c1, dd.y, c2 * (dv.y * rv.y));
-    zv.x = zv.x + dd.x;
-    zv.y = zv.y + dd.y;
-    st2(res, i, rv);
-    st2(d, i, dd);
-    st2(z, i, zv);
-  }
+  ALFD_FOR_PAIRS(i) cheb_step_pair(i, c1, c2, dinv, tmp, res, d, z);
 }
 
 // z = inv_theta * (dinv .* r): cheb_init_kernel without its two copies.  The fused sweep (aug_tail_kernel) reads
@@ -1376,6 +1385,136 @@ __global__ void mark_rows_kernel(int64_t n_list, const int32_t *__restrict__ row
   const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
   if (i < n_list) mask[rows ? (int64_t)rows[i] : i] = 1;
 }
+
+// --------------------------------------------------------------------------
+// The coarse tail of the V-cycle of the immersed hierarchy in ONE launch ("ml_tail_rows"): one
+// workgroup of kTailBlock threads runs ml_cycle for the levels first .. nlev - 1 from a table of level descriptors,
+// with __syncthreads() where the launches were.  Row sums: L lanes per row, fma over k0 + lane, k0 + lane + L, ..,
+// group_reduce<L> -- spmv_kernel's; element-wise steps: the *_pair bodies above.  Every element keeps its arithmetic
+// and order => the bits of the launch-per-step path (fused or not: those two agree already).
+// The vectors are written and read back by other threads of the workgroup inside the kernel: plain pointers, neither
+// const nor __restrict__ (those would license scalar-cache / non-coherent loads of data this kernel stored).
+constexpr int kTailBlock = 1024;
+constexpr int kTailMaxDegree = 64;   // Chebyshev steps whose coefficients a level descriptor holds
+constexpr int kTailMaxLevels = 9;    // ALFD_MAX_LEVELS + 1
+struct TailCsr {
+  const int64_t *rp;
+  const int32_t *col;
+  const double *val;
+  const int32_t *rows;   // the listed rows when sparse
+  int64_t n_list, nrows;
+  int32_t L, sparse;
+};
+struct TailLevel {
+  TailCsr A, C, Ct;   // Aug = A + gamma Ct diag(w) C of this level
+  TailCsr R, P;       // to / from the next coarser level (unused on the last)
+  const double *dinv, *w;
+  double *tlam, *r, *z, *t, *cd, *cres, *ctmp;
+  double gamma, inv_theta;   // 1 / theta of this level's sweep (the coarsest sweep on the last level)
+  int64_t npad;
+  int32_t degree, pad_;
+  double c1[kTailMaxDegree], c2[kTailMaxDegree];   // ChebCoef::step() in order, computed on the host
+};
+struct TailTable {
+  int32_t nlev, has_inv;
+  TailCsr inv;   // explicit inverse of the coarsest operator
+  TailLevel lev[kTailMaxLevels];
+};
+
+template <int L>
+__device__ __forceinline__ void tail_rows(const TailCsr &m, const double *x, double *y, int epi, double alpha,
+                                          const double *d) {
+  constexpr int RPB = kTailBlock / L;
+  const int lane = threadIdx.x % L;
+  const int sub = threadIdx.x / L;
+  const int64_t ngroups = (m.n_list + RPB - 1) / RPB;
+  for (int64_t g = 0; g < ngroups; ++g) {
+    const int64_t r = g * RPB + sub;
+    if (r < m.n_list) {  // uniform within the L-lane group
+      const int64_t k0 = m.rp[r], k1 = m.rp[r + 1];
+      double acc = 0.0;
+      for (int64_t k = k0 + lane; k < k1; k += L) acc = fma(m.val[k], x[m.col[k]], acc);
+      acc = group_reduce<L>(acc);
+      if (lane == 0) {
+        const int64_t ro = m.sparse ? (int64_t)m.rows[r] : r;
+        if (epi == 0)
+          y[ro] = acc;
+        else if (epi == 1)
+          y[ro] = fma(alpha, acc, y[ro]);
+        else
+          y[ro] = d[ro] * acc;
+      }
+    }
+  }
+}
+
+// spmv_m(m, x, y, epi, alpha, d) on one rank, epi 0 / 1 / 2, and the boundary after it
+__device__ __forceinline__ void tail_spmv(const TailCsr &m, const double *x, double *y, int epi, double alpha,
+                                          const double *d) {
+  if (m.sparse && epi != 1) {   // rows outside the list are structurally empty: their result is 0
+    for (int64_t i = threadIdx.x; i < m.nrows; i += kTailBlock) y[i] = 0.0;
+    __syncthreads();
+  }
+  switch (m.L) {   // as spmv_launch_local
+    case 4: tail_rows<4>(m, x, y, epi, alpha, d); break;
+    case 8: tail_rows<8>(m, x, y, epi, alpha, d); break;
+    case 16: tail_rows<16>(m, x, y, epi, alpha, d); break;
+    case 32: tail_rows<32>(m, x, y, epi, alpha, d); break;
+    default: tail_rows<64>(m, x, y, epi, alpha, d); break;
+  }
+  __syncthreads();
+}
+
+// y = Aug x of a level: the three products of aug_apply
+__device__ __forceinline__ void tail_aug(const TailLevel &F, const double *x, double *y) {
+  tail_spmv(F.A, x, y, 0, 0.0, nullptr);
+  tail_spmv(F.C, x, F.tlam, 2, 0.0, F.w);
+  tail_spmv(F.Ct, F.tlam, y, 1, F.gamma, nullptr);
+}
+
+#define ALFD_TAIL_PAIRS(i, npad) for (int64_t i = 2 * (int64_t)threadIdx.x; i < (npad); i += 2 * kTailBlock)
+
+// t = r - Aug z
+__device__ __forceinline__ void tail_residual(const TailLevel &F, const double *r, const double *z, double *t) {
+  tail_aug(F, z, t);
+  ALFD_TAIL_PAIRS(i, F.npad) sub_from_pair(i, r, t);
+  __syncthreads();
+}
+
+__global__ __launch_bounds__(kTailBlock) void ml_tail_kernel(const TailTable *__restrict__ tab, int first) {
+  const int nl = tab->nlev - first;   // levels of the tail; steps: nl - 1 down, the coarsest, nl - 1 up
+  for (int s = 0; s < 2 * nl - 1; ++s) {
+    const bool up = s > nl - 1, coarsest = s == nl - 1;
+    const int l = first + (up ? 2 * nl - 2 - s : s);
+    const TailLevel &F = tab->lev[l];
+    if (up) {
+      tail_spmv(F.P, tab->lev[l + 1].z, F.z, 1, 1.0, nullptr);   // z += P e_c
+      tail_residual(F, F.r, F.z, F.t);
+    } else if (coarsest && tab->has_inv) {
+      tail_spmv(tab->inv, F.r, F.z, 0, 0.0, nullptr);            // z = Aug_c^-1 r
+      continue;
+    }
+    // cheb_sweep: down and on the coarsest level z = q(r); up the correction F.r = q(t), then z += F.r
+    const double *src = up ? F.t : F.r;
+    double *dst = up ? F.r : F.z;
+    ALFD_TAIL_PAIRS(i, F.npad) cheb_init_pair(i, F.inv_theta, F.dinv, src, F.cd, dst, F.cres, F.degree > 1 ? 1 : 0);
+    __syncthreads();
+    for (int j = 1; j < F.degree; ++j) {
+      tail_aug(F, F.cd, F.ctmp);
+      const double c1 = F.c1[j - 1], c2 = F.c2[j - 1];
+      ALFD_TAIL_PAIRS(i, F.npad) cheb_step_pair(i, c1, c2, F.dinv, F.ctmp, F.cres, F.cd, dst);
+      __syncthreads();
+    }
+    if (up) {
+      ALFD_TAIL_PAIRS(i, F.npad) axpy_pair(i, 1.0, F.r, F.z);
+      __syncthreads();
+    } else if (!coarsest) {
+      tail_residual(F, F.r, F.z, F.t);
+      tail_spmv(F.R, F.t, tab->lev[l + 1].r, 0, 0.0, nullptr);   // r_c = P^T t
+    }
+  }
+}
+#undef ALFD_TAIL_PAIRS
 
 // ---- batched lock-step CG (RationalPreconditioner: 21 independent SPD solves on
 // the immersed matrices, rational_preconditioner.h:41-56).  All systems advance

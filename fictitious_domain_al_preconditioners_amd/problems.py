@@ -252,6 +252,10 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
                   grad_div=grad_div, gamma_grad_div=gamma_grad_div, beta=beta, center=tuple(center),
                   radius=radius, immersed_refine=immersed_refine, coupling_nq=coupling_nq, assembly=assembly,
                   sym_grad=bool(sym_grad))
+    if immersed_box is not None:        # cells per direction of a box-meshed immersed domain (immersed_tensor_prolongators)
+        params["immersed_cells"] = (int(immersed_box[2]),) * 2
+    if immersed_box3d is not None:
+        params["immersed_cells"] = tuple(int(v) for v in immersed_box3d[2])
     owner = _NativeHandle(h)
     pb = SyntheticProblem(params=params, _handle=owner,
                           row_ranges=rr if row_ranges is not None else None)
@@ -548,4 +552,35 @@ def tensor_prolongators(params: dict, min_coarse: int = 400, max_levels: int = 7
         if n_coarse <= min_coarse:
             break
         nf, nc, fine_is_full = nc, (nc + 1) // 2, False
+    return levels
+
+
+def immersed_tensor_prolongators(params: dict, min_coarse: int = 100, max_levels: int = 7):
+    """Geometric multigrid transfers of a box-meshed immersed space (elliptic_interface2d: immersed_box;
+    elasticity3d: immersed_box3d), as CSR prolongators for Context.set_prolongator(level, P, block=1): every level
+    interpolates (bi/tri)linearly from a grid of ceil(n/2) cells per direction (nested when n is even) until a direction
+    is down to one cell.  ALL nodes are unknowns on every level (the immersed space has no Dirichlet rows: A22 is a
+    Neumann operator plus the mass-like penalty), any cell count per direction; nodes lexicographic with x fastest,
+    node-major for several components.  Returns [(Csr P, n_coarse), ...]."""
+    import scipy.sparse as sp
+    cells = params.get("immersed_cells")
+    if cells is None:
+        raise ValueError("immersed_tensor_prolongators needs a box-meshed immersed domain (params['immersed_cells'])")
+    ncomp = params["ncomp"]
+    fine = [int(c) for c in cells]
+    levels = []
+    while len(levels) < max_levels and min(fine) >= 2:
+        coarse = [(c + 1) // 2 for c in fine]
+        pd = None
+        for nf, nc in zip(fine, coarse):                # axis 0 fastest: kron(P_z, kron(P_y, P_x))
+            r, c, v = _interp1d(nf, nc)
+            p1 = sp.csr_matrix((v, (r, c)), shape=(nf + 1, nc + 1))
+            pd = p1 if pd is None else sp.kron(p1, pd)
+        pv = sp.kron(pd, sp.identity(ncomp)).tocsr() if ncomp > 1 else pd.tocsr()
+        pv.eliminate_zeros()
+        pv.sort_indices()
+        levels.append((Csr.from_scipy(pv), int(pv.shape[1])))
+        if pv.shape[1] <= min_coarse:
+            break
+        fine = coarse
     return levels

@@ -39,6 +39,8 @@ ABI_SYMBOLS = [
     "alfd_inner_prec_apply", "alfd_spmv_scaled",
     "alfd_estimate_spectrum", "alfd_get_cg_coefficients", "alfd_host_tridiagonal_extremes",
     "alfd_constraint_residual",
+    "alfd_set_prolongator_block", "alfd_build_smoothed_aggregation_block", "alfd_get_prolongator_block",
+    "alfd_clear_hierarchy", "alfd_get_inner_iterations", "alfd_get_aggregates_block",
 ]
 
 
@@ -135,6 +137,14 @@ def load_library():
         "alfd_get_cg_coefficients": (C.c_int, [vp, vp, vp, i32, C.POINTER(i32)]),
         "alfd_host_tridiagonal_extremes": (C.c_int, [i32, vp, vp, C.POINTER(dbl), C.POINTER(dbl)]),
         "alfd_constraint_residual": (C.c_int, [vp, PP, vp, C.POINTER(dbl)]),
+        "alfd_set_prolongator_block": (C.c_int, [vp, C.c_int, C.c_int, i64, i64, vp, vp, vp]),
+        "alfd_build_smoothed_aggregation_block": (C.c_int, [vp, C.c_int, i32, dbl, i32, dbl, dbl, i32, i64, i32,
+                                                            C.POINTER(i32), vp]),
+        "alfd_get_prolongator_block": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64),
+                                                 C.POINTER(i64)]),
+        "alfd_clear_hierarchy": (C.c_int, [vp, C.c_int]),
+        "alfd_get_aggregates_block": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
+        "alfd_get_inner_iterations": (C.c_int, [vp, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -225,10 +235,32 @@ class Context:
         self._ck(self._lib.alfd_set_aggregates(self._h, level, agg.size, agg.ctypes.data,
                                                None if w is None else w.ctypes.data, int(n_coarse)))
 
-    def set_prolongator(self, level, P):
-        """CSR prolongator (problems.Csr, n_fine x n_coarse) of a multigrid level: alfd_set_prolongator."""
-        self._ck(self._lib.alfd_set_prolongator(self._h, level, P.nrows, P.ncols, P.row_ptr.ctypes.data,
-                                                P.col.ctypes.data, P.val.ctypes.data))
+    def set_prolongator(self, level, P, block=0):
+        """CSR prolongator (problems.Csr, n_fine x n_coarse) of a multigrid level: alfd_set_prolongator_block.
+        block 0: the hierarchy of the augmented (1,1) block; block 1: the one of the immersed block A22 of the
+        elliptic-interface variants (level 0 has the rows of A2)."""
+        self._ck(self._lib.alfd_set_prolongator_block(self._h, int(block), level, P.nrows, P.ncols,
+                                                      P.row_ptr.ctypes.data, P.col.ctypes.data, P.val.ctypes.data))
+
+    def aggregates(self, level, block=0):
+        """(agg, n_coarse) of a level that build_aggregates / build_smoothed_aggregation formed or set_aggregates set
+        (alfd_get_aggregates_block)."""
+        nf, nc = C.c_int64(0), C.c_int64(0)
+        self._ck(self._lib.alfd_get_aggregates_block(self._h, int(block), level, None, 0, C.byref(nf), C.byref(nc)))
+        agg = np.empty(nf.value, np.int32)
+        self._ck(self._lib.alfd_get_aggregates_block(self._h, int(block), level, agg.ctypes.data, agg.size, C.byref(nf),
+                                                     C.byref(nc)))
+        return agg, int(nc.value)
+
+    def clear_hierarchy(self, block=0):
+        """Forget the aggregates / prolongators of a block (alfd_clear_hierarchy); the next setup runs without."""
+        self._ck(self._lib.alfd_clear_hierarchy(self._h, int(block)))
+
+    def inner_iterations(self):
+        """Inner CG iterations of the last solve by inner operator: {"aug", "a22", "aug2"} (alfd_get_inner_iterations)."""
+        counts = np.zeros(3, np.int64)
+        self._ck(self._lib.alfd_get_inner_iterations(self._h, counts.ctypes.data))
+        return dict(aug=int(counts[0]), a22=int(counts[1]), aug2=int(counts[2]))
 
     def build_aggregates(self, block_size=1, threshold=0.02, max_aggregate_nodes=8, min_coarse=600, max_levels=7):
         """Algebraic aggregation from the uploaded A alone (alfd_build_aggregates); returns
@@ -247,17 +279,22 @@ class Context:
 
     def build_smoothed_aggregation(self, block_size=1, threshold=0.02, max_aggregate_nodes=8, damping=4.0 / 3.0,
                                    min_coarse=600, max_levels=7, return_omega=False, drop_tolerance=0.0,
-                                   max_row_entries=0):
+                                   max_row_entries=0, block=0):
         """Smoothed aggregation from the uploaded operators (alfd_build_smoothed_aggregation): every level's
         prolongator P = P_tent - omega D^-1 Aug P_tent, built on the device.  Upload A (and C / Ct / W^-1 and
         configure an AL variant for the penalty term) first.  drop_tolerance / max_row_entries other than 0 truncate
         every row on the device (alfd_build_smoothed_aggregation_truncated: entries below drop_tolerance * the row
         maximum go, at most max_row_entries stay, the dropped mass is lumped per component).  Returns
         [(Csr P, n_coarse), ...] -- the list upload_problem and the oracle take; with return_omega also the damping
-        omega of every level."""
+        omega of every level.  block = 1: the hierarchy of the immersed block, built from (A2, M, W^-1, gamma2)
+        (alfd_build_smoothed_aggregation_block); it stays in the context for the next setup."""
         nlev = C.c_int32(0)
         omega = np.zeros(max(max_levels, 8), np.float64)   # ALFD_MAX_LEVELS - 1 entries when max_levels is out of range
-        if drop_tolerance == 0.0 and max_row_entries == 0:
+        if block != 0:
+            self._ck(self._lib.alfd_build_smoothed_aggregation_block(
+                self._h, int(block), block_size, threshold, max_aggregate_nodes, damping, drop_tolerance,
+                max_row_entries, min_coarse, max_levels, C.byref(nlev), omega.ctypes.data))
+        elif drop_tolerance == 0.0 and max_row_entries == 0:
             self._ck(self._lib.alfd_build_smoothed_aggregation(self._h, block_size, threshold, max_aggregate_nodes,
                                                                damping, min_coarse, max_levels, C.byref(nlev),
                                                                omega.ctypes.data))
@@ -267,22 +304,22 @@ class Context:
                 min_coarse, max_levels, C.byref(nlev), omega.ctypes.data))
         out = []
         for level in range(nlev.value):
-            P = self.prolongator(level)
+            P = self.prolongator(level, block)
             out.append((P, int(P.ncols)))
         return (out, omega[:nlev.value].copy()) if return_omega else out
 
-    def prolongator(self, level):
-        """The CSR prolongator of a level as a problems.Csr (alfd_get_prolongator): built by
+    def prolongator(self, level, block=0):
+        """The CSR prolongator of a level as a problems.Csr (alfd_get_prolongator_block): built by
         build_smoothed_aggregation or set by set_prolongator."""
         from .problems import Csr
         nf, nc, nnz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
-        self._ck(self._lib.alfd_get_prolongator(self._h, level, None, None, None, 0, C.byref(nf), C.byref(nc),
-                                                C.byref(nnz)))
+        self._ck(self._lib.alfd_get_prolongator_block(self._h, int(block), level, None, None, None, 0, C.byref(nf),
+                                                      C.byref(nc), C.byref(nnz)))
         rp = np.empty(nf.value + 1, np.int64)
         col = np.empty(nnz.value, np.int32)
         val = np.empty(nnz.value, np.float64)
-        self._ck(self._lib.alfd_get_prolongator(self._h, level, rp.ctypes.data, col.ctypes.data, val.ctypes.data,
-                                                col.size, C.byref(nf), C.byref(nc), C.byref(nnz)))
+        self._ck(self._lib.alfd_get_prolongator_block(self._h, int(block), level, rp.ctypes.data, col.ctypes.data,
+                                                      val.ctypes.data, col.size, C.byref(nf), C.byref(nc), C.byref(nnz)))
         return Csr(int(nf.value), int(nc.value), rp, col, val)
 
     def set_aggregate_partition(self, level, coarse_offsets):
@@ -746,16 +783,20 @@ def host_stream_plan(m, row_block=96, blocks=None):
     return {k: getattr(info, k) for k, _ in info._fields_}
 
 
-def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_blocks=None) -> Context:
+def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_blocks=None, immersed_levels=None) -> Context:
     """Upload a problems.SyntheticProblem (whole, or this rank's rows) with the
     reference's diagonal choices: W^-1 = 1/M_ii^2 (stokes...:976-978), lumped
     pressure mass (stokes...:946-954).  aggregates: [(agg, n_coarse), ...] for
     ALFD_PREC_MULTILEVEL (problems.geometric_aggregates), or [(Csr P, n_coarse), ...]
     (problems.tensor_prolongators), or a zero-argument callable returning either (evaluated on a helper
     thread while the operators are uploaded).  row_blocks: (block_ptr, rows)
-    for the SpMV on A (Context.set_row_blocks, e.g. problems.brick_row_blocks)."""
+    for the SpMV on A (Context.set_row_blocks, e.g. problems.brick_row_blocks).  immersed_levels:
+    [(Csr P, n_coarse), ...] of the immersed block of an elliptic-interface problem (block 1:
+    problems.immersed_tensor_prolongators); None leaves whatever the context holds for that block."""
     if row_blocks is not None:
         ctx.set_row_blocks(_abi.A, *row_blocks)
+    for level, entry in enumerate(immersed_levels or []):
+        ctx.set_prolongator(level, entry[0], block=1)
 
     def set_hierarchy(levels):
         for level, entry in enumerate(levels or []):
@@ -829,8 +870,9 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
     return ctx
 
 
-def context_from_problem(pb, cfg: _abi.Config, device_id=0, aggregates=None, row_blocks=None) -> Context:
-    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks)
+def context_from_problem(pb, cfg: _abi.Config, device_id=0, aggregates=None, row_blocks=None,
+                         immersed_levels=None) -> Context:
+    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks, immersed_levels)
 
 
 # ---------------------------------------------------------------------------

@@ -117,8 +117,12 @@ enum alfd_inner_prec {
   ALFD_PREC_CHEBYSHEV = 2,
   /* Aggregation multigrid V-cycle with Chebyshev smoothing on every level (the
    * GPU counterpart of the ML smoothed-aggregation AMG the reference initialises
-   * in utilities.h:304-317).  Needs alfd_set_aggregates(); applies to the
-   * augmented (1,1) block, other inner operators fall back to CHEBYSHEV. */
+   * in utilities.h:304-317).  Needs alfd_set_aggregates() / alfd_set_prolongator() for the augmented
+   * (1,1) block.  The elliptic-interface variants take a second hierarchy, for the immersed block
+   * A22 = A2 + gamma2 M invW M (alfd_set_prolongator_block(ctx, 1, ..), amg_prec_A22 of
+   * elliptic_interface.cc:824-851): with it the A22 solve of AL_ELL_MODIFIED runs its own V-cycle and the
+   * 2-block CG of AL_ELL_IDEAL the block diagonal of the two (elliptic_interface.cc:930-942); without it
+   * A22 keeps the CHEBYSHEV sweep and AL_ELL_IDEAL answers ALFD_E_UNSUPPORTED at alfd_setup. */
   ALFD_PREC_MULTILEVEL = 3
 };
 
@@ -389,6 +393,31 @@ int alfd_build_smoothed_aggregation_truncated(alfd_ctx_t ctx, int32_t block_size
  * without a CSR prolongator. */
 int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
                          int64_t *n_fine, int64_t *n_coarse, int64_t *nnz);
+/* alfd_set_prolongator, alfd_build_smoothed_aggregation_truncated and alfd_get_prolongator for one of the two
+ * hierarchies.  block 0: the augmented (1,1) block, exactly those calls.
+ * block 1: the immersed space of the elliptic-interface variants, whose operator is A22 = A2 + gamma2 M invW M -- the
+ * roles of (A, C, Ct, gamma) are taken by (A2, M, M, gamma2), n_fine of level 0 is the row count of slot A2, and
+ * alfd_setup forms A2_{l+1} = P^T (A2_l P), M_{l+1} = M_l P with the same products, diagonals, power iterations and
+ * (alfd_config::ml_coarse_direct) explicit coarsest inverse; the ml_* settings are shared by both hierarchies.  The
+ * builder runs the smoothed aggregation above on (A2, M, invW, gamma2), so the immersed hierarchy needs no geometry
+ * either (amg_prec_A22.initialize(matrix), elliptic_interface.cc:841-851); drop_tolerance = 0 and max_row_entries = 0
+ * truncate nothing.  Block 1 takes CSR prolongators only (there is no alfd_set_aggregates for it), has no interface patch (M touches
+ * every row) and is single-rank: ALFD_E_UNSUPPORTED on a partitioned context, ALFD_E_INVALID for another block, for
+ * the builder without slot A2, and at alfd_setup for a block-1 hierarchy on a variant without A2 or with sizes that
+ * do not match.  alfd_clear_hierarchy forgets what was set or built for a block (the next alfd_setup runs without). */
+int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_fine, int64_t n_coarse,
+                               const int64_t *row_ptr, const int32_t *col, const double *val);
+int alfd_build_smoothed_aggregation_block(alfd_ctx_t ctx, int block, int32_t block_size, double threshold,
+                                          int32_t max_aggregate_nodes, double damping, double drop_tolerance,
+                                          int32_t max_row_entries, int64_t min_coarse, int32_t max_levels,
+                                          int32_t *levels_out, double *omega_out);
+int alfd_get_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t *row_ptr, int32_t *col, double *val,
+                               int64_t capacity, int64_t *n_fine, int64_t *n_coarse, int64_t *nnz);
+/* The aggregates the builder formed for a level of a block (agg[n_fine], -1: empty row), as alfd_get_aggregates does
+ * for block 0; NULL agg queries the sizes.  ALFD_E_INVALID for a level the builder did not form. */
+int alfd_get_aggregates_block(alfd_ctx_t ctx, int block, int level, int32_t *agg, int64_t capacity, int64_t *n_fine,
+                              int64_t *n_coarse);
+int alfd_clear_hierarchy(alfd_ctx_t ctx, int block);
 /* Host-only (no device, no context): ONE level's smoothed prolongator with the arithmetic of
  * alfd_build_smoothed_aggregation, from the square CSR A (nrows), optionally Ct (nrows x n_mult, ct_row_ptr == NULL:
  * no penalty term) with the W^-1 diagonal w_inv[n_mult] and gamma, the aggregates agg[nrows] (-1: empty row),
@@ -443,6 +472,10 @@ int alfd_solve(alfd_ctx_t ctx, const double *const *rhs_blocks, double *const *x
 int alfd_upload_rhs(alfd_ctx_t ctx, const double *const *rhs_blocks, const double *const *x0_blocks);
 int alfd_solve_resident(alfd_ctx_t ctx, alfd_result *res);
 int alfd_download_solution(alfd_ctx_t ctx, double *const *x_blocks);
+/* Inner CG iterations of the last solve (or alfd_precond_apply) by inner operator, counts[alfd_inner_op]: the
+ * augmented (1,1) block, A22, the 2-block operator.  alfd_result::inner_iterations is their sum (plus the K solves of
+ * the rational variant). */
+int alfd_get_inner_iterations(alfd_ctx_t ctx, int64_t counts[3]);
 /* Residual history of the last solve: out[k] = residual checked at step k. */
 int alfd_get_history(alfd_ctx_t ctx, double *out, int32_t capacity, int32_t *count);
 
@@ -464,10 +497,12 @@ int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double
  * Chebyshev sweep, the multilevel cycle incl. patch and coarsest inverse), after alfd_setup.  Unlike
  * alfd_precond_apply with one fixed CG step, which returns alpha(r) M^-1 r, this keeps the scale, so linearity,
  * symmetry and the operator itself can be compared with an independent reference.  `op` selects the inner operator:
- *   ALFD_INNER_OP_AUG   the augmented (1,1) block: AL2, AL_STOKES, AL_STOKES_DIAG, AL_ELL_MODIFIED (the only one
- *                       ALFD_PREC_MULTILEVEL applies to); r, z have the length of block 0
+ *   ALFD_INNER_OP_AUG   the augmented (1,1) block: AL2, AL_STOKES, AL_STOKES_DIAG, AL_ELL_MODIFIED; r, z have the
+ *                       length of block 0
  *   ALFD_INNER_OP_A22   the second block A22_aug of AL_ELL_MODIFIED; r, z have the length of block 1
+ *                       (ALFD_PREC_MULTILEVEL: the V-cycle of the block-1 hierarchy when one is set, else the sweep)
  *   ALFD_INNER_OP_AUG2  the coupled 2-block operator of AL_ELL_IDEAL; r, z hold block 0 followed by block 1
+ *                       (ALFD_PREC_MULTILEVEL: the block diagonal of the two hierarchies, patch included on block 0)
  * An op the configured variant does not solve with: ALFD_E_INVALID; before alfd_setup: ALFD_E_NOT_SETUP.  Stages
  * through the buffers of the depth-1 calls (a resident right-hand side stays intact).  On a partitioned context the
  * call is collective like alfd_spmv: r, z hold this rank's rows. */
@@ -647,6 +682,13 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  launch (aug_tail_kernel); 0: separate launches.  Same bits either way; takes effect at the next
  *                  apply.  Operators whose Ct is not in the plain row-per-lane-group form, partitioned contexts,
  *                  grad_div_in_A = 0, w_inverse != diagonal and aug_assembled always use the separate launches.
+ *   "ml_tail_rows" (>= 0, default 0 = off): the levels l >= 1 of the block-1 (immersed) hierarchy from the first one
+ *                  with at most this many unknowns down to the coarsest run their part of the V-cycle in ONE launch
+ *                  (ml_tail_kernel: one workgroup, a barrier where the launches were) instead of 15-21 launches per
+ *                  level.  Same bits either way; takes effect at the next apply.  Used only when every operator of
+ *                  those levels is stored as plain CSR rows, on one rank, with the diagonal W^-1 and the factored
+ *                  operator; otherwise the launches.  Off by default: every level keeps all multiplier rows of M_l,
+ *                  so at sizes where the launches matter one workgroup is slower.
  * Returns ALFD_E_INVALID for an unknown name. */
 int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value);
 /* Kernel-class timing of the last solve, accumulated with HIP events when

@@ -139,12 +139,13 @@ class System {
   }
   bool renumbered() const { return !new_to_old_.empty(); }
 
-  // CSR prolongator of a multigrid level (alfd_set_prolongator), e.g. from MGTransferPrebuilt or
-  // FETools::get_interpolation_matrix; the rows of level 0 follow the block-0 renumbering.
+  // CSR prolongator of a multigrid level (alfd_set_prolongator_block), e.g. from MGTransferPrebuilt or
+  // FETools::get_interpolation_matrix; the rows of level 0 follow the block-0 renumbering.  block = 1: the hierarchy
+  // of the immersed block A22 of elliptic_interface.cc (amg_prec_A22, :841-851); its rows are never renumbered.
   template <class SparseMatrixType>
-  void set_prolongator(int level, const SparseMatrixType &P) {
+  void set_prolongator(int level, const SparseMatrixType &P, int block = 0) {
     const int64_t nrows = (int64_t)P.m();
-    const bool prow = level == 0 && !new_to_old_.empty();
+    const bool prow = block == 0 && level == 0 && !new_to_old_.empty();
     std::vector<int64_t> rp(nrows + 1, 0);
     std::vector<int32_t> col;
     std::vector<double> val;
@@ -160,7 +161,7 @@ class System {
       }
       rp[r + 1] = (int64_t)col.size();
     }
-    check(alfd_set_prolongator(ctx_, level, nrows, (int64_t)P.n(), rp.data(), col.data(), val.data()));
+    check(alfd_set_prolongator_block(ctx_, block, level, nrows, (int64_t)P.n(), rp.data(), col.data(), val.data()));
   }
 
   template <class VectorType>
@@ -201,13 +202,18 @@ class System {
   // Returns the number of levels; omega (optional) receives the damping of every level.  drop_tolerance /
   // max_row_entries other than 0 truncate every row of the prolongators on the device
   // (alfd_build_smoothed_aggregation_truncated: e.g. 0, 4 keeps the iteration counts at about one eighth of the entries).
+  // block = 1: the hierarchy of the immersed block, from (A2, M, W^-1, gamma2) (alfd_build_smoothed_aggregation_block).
   int build_smoothed_aggregation(int32_t block_size = 1, double threshold = 0.02, int32_t max_aggregate_nodes = 8,
                                  double damping = 4.0 / 3.0, int64_t min_coarse = 600, int32_t max_levels = 7,
                                  std::vector<double> *omega = nullptr, double drop_tolerance = 0.0,
-                                 int32_t max_row_entries = 0) {
+                                 int32_t max_row_entries = 0, int block = 0) {
     int32_t levels = 0;
     std::vector<double> w(ALFD_MAX_LEVELS, 0.0);
-    if (drop_tolerance == 0.0 && max_row_entries == 0)
+    if (block != 0)
+      check(alfd_build_smoothed_aggregation_block(ctx_, block, block_size, threshold, max_aggregate_nodes, damping,
+                                                  drop_tolerance, max_row_entries, min_coarse, max_levels, &levels,
+                                                  w.data()));
+    else if (drop_tolerance == 0.0 && max_row_entries == 0)
       check(alfd_build_smoothed_aggregation(ctx_, block_size, threshold, max_aggregate_nodes, damping, min_coarse,
                                             max_levels, &levels, w.data()));
     else
