@@ -275,8 +275,11 @@ struct alfd_ctx {
     DevCsr inv;                                // explicit inverse of the coarsest operator (alfd_config::ml_coarse_direct)
     std::vector<MlLevel> ml;
     TailTable *tail_tab = nullptr;             // level descriptors of ml_tail_kernel (hierarchy 1; setup workspace)
+    bool built_partitioned = false;            // made by alfd_build_smoothed_aggregation on a partitioned context:
+                                               // level 0 = local rows, alfd_setup fetches the whole fine support
     void clear_input() {
       for (int l = 0; l < ALFD_MAX_LEVELS; ++l) agg[l].clear(), wgt[l].clear(), P[l] = HostCsr(), ncoarse[l] = 0;
+      built_partitioned = false;
     }
   } hier[2];
   // interface patch (alfd_config::ml_patch_degree > 0): S = non-empty rows of Ct, vectors of length |S|
@@ -298,6 +301,14 @@ struct alfd_ctx {
     DevCsr Cts_loc, Ctg;
     double *send = nullptr, *stage = nullptr, *lam_send = nullptr, *lam_stage = nullptr, *loc = nullptr;
   } patch;
+  // alfd_build_strength_graph: the node-graph rows of this rank's nodes (neighbours as GLOBAL node ids)
+  struct StrengthGraph {
+    bool have = false, on_device = false;     // on_device: sa_node_graph_kernel formed it (false: the joint host fallback)
+    int64_t n_nodes = 0, node0 = 0;
+    std::vector<int64_t> gp;
+    std::vector<int32_t> gc, fixed;
+    std::vector<double> gw, d;
+  } sg;
   int ml_rep_level = -1;                      // first replicated level (multi-rank), -1: none
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
@@ -4883,48 +4894,62 @@ static int gather_vec(alfd_ctx *ctx, const double *d_local, int64_t n_local, dou
 // free neighbours (at most max_size nodes); (2) leftovers join the founded aggregate they are most
 // strongly tied to; (3) what is still free founds aggregates of its own.  The next level's graph
 // is that of the Galerkin product with the piecewise-constant prolongator.
-static void aggregate_level(const HostCsr &A, int bs, double theta, int max_size, std::vector<int32_t> &agg,
-                            int64_t &n_coarse) {
-  const int64_t n = A.nrows, nn = n / bs;
-  std::vector<double> d(nn, 0.0);
-  std::vector<char> fixed(nn, 1);
-  for (int64_t i = 0; i < n; ++i) {
+// The node graph of one level, in two steps so that a row-partitioned context can form the rows of its own nodes
+// (sa_node_diag_kernel / sa_node_graph_kernel compute the same bits on the device; max and fabs are exact):
+//   node_diag_host:  d_I = max |a_ii| and the fixed flag of the nodes of A's rows.  A holds the rows [row0, row0 +
+//                    A.nrows) of the level's operator with GLOBAL column ids; d / fixed are indexed by local node.
+//   node_graph_host: per local node the strong neighbours J ascending with w_IJ = max |a_ij|; d / fixed of ALL nodes
+//                    (nn of them), neighbours as global node ids.
+static void node_diag_host(const HostCsr &A, int64_t row0, int bs, std::vector<double> &d, std::vector<int32_t> &fixed) {
+  const int64_t nl = A.nrows / bs;
+  d.assign(nl, 0.0);
+  fixed.assign(nl, 1);
+  for (int64_t i = 0; i < nl * bs; ++i) {
     const int64_t I = i / bs;
     for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
-      if (A.col[k] == i) d[I] = std::max(d[I], std::fabs(A.val[k]));
+      if (A.col[k] == row0 + i) d[I] = std::max(d[I], std::fabs(A.val[k]));
       else if (A.val[k] != 0.0) fixed[I] = 0;
     }
   }
-  // node graph (strong edges only), CSR with weights
-  std::vector<int64_t> gp(nn + 1, 0);
-  std::vector<int32_t> gc;
-  std::vector<double> gw;
-  {
-    std::vector<double> w(nn, 0.0);
-    std::vector<int32_t> touched;
-    for (int64_t I = 0; I < nn; ++I) {
-      touched.clear();
-      if (!fixed[I])
-        for (int64_t i = I * bs; i < (I + 1) * bs; ++i)
-          for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
-            const int64_t J = A.col[k] / bs;
-            if (J == I || J >= nn || fixed[J]) continue;
-            const double v = std::fabs(A.val[k]);
-            if (v == 0.0) continue;
-            if (w[J] == 0.0) touched.push_back((int32_t)J);
-            w[J] = std::max(w[J], v);
-          }
-      std::sort(touched.begin(), touched.end());
-      for (int32_t J : touched) {
-        if (w[J] >= theta * std::sqrt(d[I] * d[J])) {
-          gc.push_back(J);
-          gw.push_back(w[J]);
+}
+
+static void node_graph_host(const HostCsr &A, int64_t row0, int bs, double theta, int64_t nn, const double *d,
+                            const int32_t *fixed, std::vector<int64_t> &gp, std::vector<int32_t> &gc,
+                            std::vector<double> &gw) {
+  const int64_t nl = A.nrows / bs, node0 = row0 / bs;
+  gp.assign(nl + 1, 0);
+  gc.clear();
+  gw.clear();
+  std::vector<double> w(nn, 0.0);
+  std::vector<int32_t> touched;
+  for (int64_t Il = 0; Il < nl; ++Il) {
+    const int64_t I = node0 + Il;
+    touched.clear();
+    if (!fixed[I])
+      for (int64_t i = Il * bs; i < (Il + 1) * bs; ++i)
+        for (int64_t k = A.rp[i]; k < A.rp[i + 1]; ++k) {
+          const int64_t J = A.col[k] / bs;
+          if (J == I || J >= nn || fixed[J]) continue;
+          const double v = std::fabs(A.val[k]);
+          if (v == 0.0) continue;
+          if (w[J] == 0.0) touched.push_back((int32_t)J);
+          w[J] = std::max(w[J], v);
         }
-        w[J] = 0.0;
+    std::sort(touched.begin(), touched.end());
+    for (int32_t J : touched) {
+      if (w[J] >= theta * std::sqrt(d[I] * d[J])) {
+        gc.push_back(J);
+        gw.push_back(w[J]);
       }
-      gp[I + 1] = (int64_t)gc.size();
+      w[J] = 0.0;
     }
+    gp[Il + 1] = (int64_t)gc.size();
   }
+}
+
+// The three greedy passes over a node graph (nn nodes, strong edges gp / gc / gw, the fixed flags); agg gets n entries.
+static void aggregate_graph(int64_t n, int64_t nn, int bs, int max_size, const int32_t *fixed, const int64_t *gp,
+                            const int32_t *gc, const double *gw, std::vector<int32_t> &agg, int64_t &n_coarse) {
   std::vector<int32_t> na(nn, -1);  // node -> aggregate
   int32_t nagg = 0;
   std::vector<std::pair<double, int32_t>> cand;
@@ -4967,6 +4992,186 @@ static void aggregate_level(const HostCsr &A, int bs, double theta, int max_size
   for (int64_t i = 0; i < nn * bs; ++i)
     if (na[i / bs] >= 0) agg[i] = (int32_t)(na[i / bs] * bs + i % bs);
   n_coarse = (int64_t)nagg * bs;
+}
+
+static void aggregate_level(const HostCsr &A, int bs, double theta, int max_size, std::vector<int32_t> &agg,
+                            int64_t &n_coarse) {
+  const int64_t nn = A.nrows / bs;
+  std::vector<double> d, gw;
+  std::vector<int32_t> fixed, gc;
+  std::vector<int64_t> gp;
+  node_diag_host(A, 0, bs, d, fixed);
+  node_graph_host(A, 0, bs, theta, nn, d.data(), fixed.data(), gp, gc, gw);
+  aggregate_graph(A.nrows, nn, bs, max_size, fixed.data(), gp.data(), gc.data(), gw.data(), agg, n_coarse);
+}
+
+// Every rank contributes the status of its local phase; all return the first non-zero one (rank order), so that no rank
+// runs into the next collective while a peer has left (*any_flag: some rank raised `flag`).
+static int joint_status(alfd_ctx *ctx, int local, int flag, int *any_flag) {
+  if (any_flag) *any_flag = flag;
+  if (ctx->nranks == 1) return local;
+  const int64_t mine[2] = {local, flag};
+  std::vector<char> all;
+  std::vector<size_t> sz;
+  const std::string keep = ctx->err;
+  const int rc = allgather_bytes(ctx, mine, sizeof(mine), all, sz);
+  if (rc != ALFD_OK) return rc;
+  int first = ALFD_OK, who = -1;
+  for (int p = 0; p < ctx->nranks; ++p) {
+    int64_t v[2];
+    std::memcpy(v, all.data() + (size_t)p * sizeof(mine), sizeof(mine));
+    if (first == ALFD_OK && v[0] != ALFD_OK) first = (int)v[0], who = p;
+    if (any_flag && v[1]) *any_flag = 1;
+  }
+  if (first != ALFD_OK && who != ctx->rank) ctx->err = "rank " + std::to_string(who) + " failed in a collective build step";
+  else ctx->err = keep;
+  return first;
+}
+
+// The node graph of slot A's resident rows on the device (sa_node_diag_kernel, sa_node_graph_kernel); collective on a
+// partitioned context: d and the fixed flags of all nodes are all-gathered (one double and one int per node), nothing
+// else moves and A is not downloaded.  A node with more than kNgMaxOut neighbour nodes on ANY rank sends all ranks to
+// node_graph_host on their downloaded rows (same bits).
+static int strength_graph_dev(alfd_ctx *ctx, int bs, double theta) {
+  alfd_ctx::StrengthGraph &G = ctx->sg;
+  G = alfd_ctx::StrengthGraph();
+  const DevCsr &A = ctx->mat[ALFD_A];
+  const int P = ctx->nranks, rk = ctx->rank;
+  const int64_t row0 = P > 1 ? ctx->part[0][rk] : 0, N = P > 1 ? ctx->part[0].back() : A.nrows;
+  const int64_t nl = A.nrows / bs, nn = N / bs, node0 = row0 / bs;
+  const int32_t nlc = P > 1 ? A.n_local_cols : (int32_t)A.ncols;
+  int32_t *d_halo = nullptr, *d_fl = nullptr, *d_fg = nullptr, *d_cnt = nullptr, *d_ovf = nullptr, *d_gc = nullptr;
+  double *d_dl = nullptr, *d_dg = nullptr, *d_gw = nullptr;
+  int64_t *d_gp = nullptr;
+  auto release = [&]() {
+    for (void *p : {(void *)d_halo, (void *)d_fl, (void *)d_fg, (void *)d_cnt, (void *)d_ovf, (void *)d_gc, (void *)d_dl,
+                    (void *)d_dg, (void *)d_gw, (void *)d_gp})
+      if (p) hipFree(p);
+  };
+  auto hip = [&](hipError_t e) -> int {
+    if (e == hipSuccess) return ALFD_OK;
+    ctx->err = std::string("HIP error in the strength graph: ") + hipGetErrorString(e);
+    return (int)ALFD_E_HIP;
+  };
+#define SG(call)                     \
+  do {                               \
+    const int rc__ = hip(call);      \
+    if (rc__ != ALFD_OK) return rc__; \
+  } while (0)
+  std::vector<double> dl(nl);
+  std::vector<int32_t> fl(nl);
+  // ---- phase 1 (local): d and the fixed flags of the own nodes
+  auto phase1 = [&]() -> int {
+    if (!A.halo_globals.empty()) {
+      SG(hipMalloc((void **)&d_halo, A.halo_globals.size() * sizeof(int32_t)));
+      SG(hipMemcpyAsync(d_halo, A.halo_globals.data(), A.halo_globals.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                        ctx->stream));
+    }
+    SG(hipMalloc((void **)&d_dl, std::max<int64_t>(nl, 1) * sizeof(double)));
+    SG(hipMalloc((void **)&d_fl, std::max<int64_t>(nl, 1) * sizeof(int32_t)));
+    if (nl > 0) {
+      hipLaunchKernelGGL(sa_node_diag_kernel, dim3((unsigned)((nl + 255) / 256)), dim3(256), 0, ctx->stream, nl, bs, node0,
+                         A.rp, A.col, A.val, nlc, row0, d_halo, d_dl, d_fl);
+      SG(hipGetLastError());
+      SG(hipMemcpyAsync(dl.data(), d_dl, nl * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+      SG(hipMemcpyAsync(fl.data(), d_fl, nl * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SG(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  int rc = joint_status(ctx, phase1(), 0, nullptr);
+  if (rc != ALFD_OK) return release(), rc;
+  // ---- d / fixed of all nodes
+  std::vector<double> dg;
+  std::vector<int32_t> fg;
+  if (P == 1) {
+    dg = dl;
+    fg = fl;
+  } else {
+    std::vector<char> bd, bf;
+    std::vector<size_t> sz;
+    rc = allgather_bytes(ctx, dl.data(), dl.size() * sizeof(double), bd, sz);
+    if (rc == ALFD_OK) rc = allgather_bytes(ctx, fl.data(), fl.size() * sizeof(int32_t), bf, sz);
+    if (rc != ALFD_OK) return release(), rc;      // a failed transport fails on every rank
+    if ((int64_t)(bd.size() / sizeof(double)) != nn || (int64_t)(bf.size() / sizeof(int32_t)) != nn)
+      return release(), ctx->err = "alfd_build_strength_graph: the ranks' rows of A do not add up to the partition", ALFD_E_COMM;
+    dg.resize(nn);
+    fg.resize(nn);
+    std::memcpy(dg.data(), bd.data(), bd.size());
+    std::memcpy(fg.data(), bf.data(), bf.size());
+  }
+  // ---- phase 2 (local): count the strong neighbours of every own node
+  std::vector<int32_t> hc(nl);
+  int32_t hovf = 0;
+  const unsigned grid = (unsigned)std::max<int64_t>(1, std::min<int64_t>(nl, 256 * 64));
+  auto launch = [&](int pass) {
+    hipLaunchKernelGGL(sa_node_graph_kernel, dim3(grid), dim3(64), 0, ctx->stream, nl, node0, nn, bs, theta, A.rp, A.col,
+                       A.val, nlc, row0, d_halo, d_dg, d_fg, pass, d_cnt, d_gp, d_gc, d_gw, d_ovf);
+  };
+  auto phase2 = [&]() -> int {
+    SG(hipMalloc((void **)&d_dg, std::max<int64_t>(nn, 1) * sizeof(double)));
+    SG(hipMalloc((void **)&d_fg, std::max<int64_t>(nn, 1) * sizeof(int32_t)));
+    SG(hipMalloc((void **)&d_cnt, std::max<int64_t>(nl, 1) * sizeof(int32_t)));
+    SG(hipMalloc((void **)&d_ovf, sizeof(int32_t)));
+    SG(hipMalloc((void **)&d_gp, (nl + 1) * sizeof(int64_t)));
+    SG(hipMemcpyAsync(d_dg, dg.data(), nn * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    SG(hipMemcpyAsync(d_fg, fg.data(), nn * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
+    SG(hipMemsetAsync(d_ovf, 0, sizeof(int32_t), ctx->stream));
+    if (nl > 0) {
+      launch(0);
+      SG(hipGetLastError());
+      SG(hipMemcpyAsync(hc.data(), d_cnt, nl * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SG(hipMemcpyAsync(&hovf, d_ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+    SG(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  int any_ovf = 0;
+  {
+    const int loc = phase2();
+    rc = joint_status(ctx, loc, hovf, &any_ovf);
+  }
+  if (rc != ALFD_OK) return release(), rc;
+  // ---- phase 3 (local): fill, or all ranks on the host
+  auto phase3 = [&]() -> int {
+    if (any_ovf) {
+      HostCsr h;
+      RC(download_csr(ctx, A, h));
+      for (size_t k = 0; k < h.col.size(); ++k)
+        h.col[k] = (int32_t)(h.col[k] < nlc ? row0 + h.col[k] : A.halo_globals[h.col[k] - nlc]);
+      node_graph_host(h, row0, bs, theta, nn, dg.data(), fg.data(), G.gp, G.gc, G.gw);
+      return ALFD_OK;
+    }
+    G.gp.assign(nl + 1, 0);
+    for (int64_t I = 0; I < nl; ++I) G.gp[I + 1] = G.gp[I] + hc[I];
+    const int64_t nnz = G.gp[nl];
+    G.gc.resize(nnz);
+    G.gw.resize(nnz);
+    SG(hipMalloc((void **)&d_gc, std::max<int64_t>(nnz, 1) * sizeof(int32_t)));
+    SG(hipMalloc((void **)&d_gw, std::max<int64_t>(nnz, 1) * sizeof(double)));
+    SG(hipMemcpyAsync(d_gp, G.gp.data(), (nl + 1) * sizeof(int64_t), hipMemcpyHostToDevice, ctx->stream));
+    if (nl > 0) {
+      launch(1);
+      SG(hipGetLastError());
+    }
+    if (nnz > 0) {
+      SG(hipMemcpyAsync(G.gc.data(), d_gc, nnz * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+      SG(hipMemcpyAsync(G.gw.data(), d_gw, nnz * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SG(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  rc = joint_status(ctx, phase3(), 0, nullptr);
+#undef SG
+  release();
+  if (rc != ALFD_OK) return G = alfd_ctx::StrengthGraph(), rc;
+  G.have = true;
+  G.on_device = !any_ovf;
+  G.n_nodes = nl;
+  G.node0 = node0;
+  G.d = dl;
+  G.fixed = fl;
+  return ALFD_OK;
 }
 
 // Rows of a row-partitioned CSR matrix (this rank holds the global rows [row_off[rank], row_off[rank + 1]) as `loc`,
@@ -5319,14 +5524,21 @@ static int sa_penalty_rows(alfd_ctx *ctx, const SaPenalty &pen, const std::vecto
 // P on the device; *fits = false when a row has more distinct coarse ids than the kernel holds.  tau == 0 and cap == 0:
 // sa_prolongator_kernel; otherwise sa_truncated_prolongator_kernel, whose counts, row pointer and arrays hold the kept
 // entries only (the untruncated P exists nowhere).
-static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector<int32_t> &agg, int64_t nc,
-                              const std::vector<double> &f, const HostCsr &Q, int bs, double tau, int cap, HostCsr &P,
-                              bool *fits) {
+// (the rows of A are device arrays: an uploaded copy, or the global-column view of a partitioned context's resident rows
+// with agg = [agg of the own rows | agg of all unknowns], see sa_global_cols_kernel)
+static int sa_prolongator_dev_raw(alfd_ctx *ctx, int64_t n, const int64_t *arp, const int32_t *acol, const double *aval,
+                                  const std::vector<int32_t> &agg, int64_t nc, const std::vector<double> &f,
+                                  const HostCsr &Q, int bs, double tau, int cap, HostCsr &P, bool *fits) {
   *fits = false;
-  const int64_t n = A.nrows;
   const bool trunc = tau != 0.0 || cap != 0;
-  DevRawCsr dA, dQ, dP;
-  RC(upload_raw(ctx, A, dA));
+  struct {
+    const int64_t *rp;
+    const int32_t *col;
+    const double *val;
+    void release() {}
+  } dA{arp, acol, aval};
+  DevRawCsr dQ, dP;
+  const int64_t n_agg = (int64_t)agg.size();
   const bool pen = !Q.rp.empty();
   if (pen) RC(upload_raw(ctx, Q, dQ));
   int32_t *d_agg = nullptr, *counts = nullptr, *ovf = nullptr;
@@ -5344,12 +5556,12 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
     return ALFD_E_HIP;
   };
   hipError_t e;
-  if ((e = hipMalloc((void **)&d_agg, std::max<int64_t>(n, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
+  if ((e = hipMalloc((void **)&d_agg, std::max<int64_t>(n_agg, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
   if ((e = hipMalloc((void **)&d_f, std::max<int64_t>(n, 1) * sizeof(double))) != hipSuccess) return fail(e);
   if ((e = hipMalloc((void **)&counts, std::max<int64_t>(n, 1) * sizeof(int32_t))) != hipSuccess) return fail(e);
   if ((e = hipMalloc((void **)&ovf, sizeof(int32_t))) != hipSuccess) return fail(e);
   if ((e = hipMalloc((void **)&dP.rp, (n + 1) * sizeof(int64_t))) != hipSuccess) return fail(e);
-  if (n && (e = hipMemcpyAsync(d_agg, agg.data(), n * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
+  if (n_agg && (e = hipMemcpyAsync(d_agg, agg.data(), n_agg * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
     return fail(e);
   if (n && (e = hipMemcpyAsync(d_f, f.data(), n * sizeof(double), hipMemcpyHostToDevice, ctx->stream)) != hipSuccess)
     return fail(e);
@@ -5400,6 +5612,17 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
   release();
   *fits = true;
   return ALFD_OK;
+}
+
+static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector<int32_t> &agg, int64_t nc,
+                              const std::vector<double> &f, const HostCsr &Q, int bs, double tau, int cap, HostCsr &P,
+                              bool *fits) {
+  *fits = false;
+  DevRawCsr dA;
+  RC(upload_raw(ctx, A, dA));
+  const int rc = sa_prolongator_dev_raw(ctx, A.nrows, dA.rp, dA.col, dA.val, agg, nc, f, Q, bs, tau, cap, P, fits);
+  dA.release();
+  return rc;
 }
 
 // The interface patch of a partitioned context: S is split by row ownership, the patch operators are gathered whole on
@@ -5520,6 +5743,152 @@ static int patch_setup_rep(alfd_ctx *ctx) {
   return ALFD_OK;
 }
 
+// The level-0 products of a partitioned hierarchy, replicated: A_1 = P_0^T (A P_0) and C_1 = C P_0 (C1 may be null) whole
+// on every rank, with the bits of the single-rank products; Rg = this rank's rows of P_0^T over GLOBAL fine ids.  P0 =
+// this rank's rows of P_0 (global coarse ids), coff = the ranks' ranges of the coarse ids (the rank that forms a coarse
+// row).  Remote rows of P_0 and A P_0 come from their owners (fetch_rows).  built = false (caller-supplied
+// prolongators): the rows of A's halo, so a coarse unknown's fine support must lie in its rank's rows + halo of A.
+// built = true (alfd_build_smoothed_aggregation on a partitioned context, whose global aggregates do not respect the
+// slabs and whose smoothed columns reach one hop further): also every fine row in the support of an owned coarse
+// unknown that this rank does not own -- known from an all-gather of (forming rank, fine row) pairs, one per remote
+// rank a row of P_0 touches -- so any contiguous split of the coarse ids is valid and the result does not depend on it.
+// Shared by alfd_setup and the builder (which needs A_1 and C_1 for the aggregation of level 1).
+static int rep_level0_products(alfd_ctx *ctx, const HostCsr &P0, const std::vector<int64_t> &coff, bool built, HostCsr &A1,
+                               HostCsr *C1, HostCsr &Rg) {
+  const int P = ctx->nranks, rk = ctx->rank;
+  const std::vector<int64_t> &off0 = ctx->part[0];
+  const int64_t n1 = P0.ncols;
+  DevCsr &dA = ctx->mat[ALFD_A], &dC = ctx->mat[ALFD_C];
+  std::vector<int64_t> extra;   // fine rows beyond A's halo whose prolongator rows reach an owned coarse unknown
+  if (built) {
+    std::vector<int64_t> pairs;   // (forming rank, global fine row), one per remote rank a row touches
+    std::vector<char> hit(P);
+    for (int64_t q = 0; q < P0.nrows; ++q) {
+      std::fill(hit.begin(), hit.end(), 0);
+      for (int64_t k = P0.rp[q]; k < P0.rp[q + 1]; ++k) {
+        const int p = (int)(std::upper_bound(coff.begin(), coff.end(), (int64_t)P0.col[k]) - coff.begin()) - 1;
+        if (p != rk && p >= 0 && p < P && !hit[p]) {
+          hit[p] = 1;
+          pairs.push_back(p);
+          pairs.push_back(off0[rk] + q);
+        }
+      }
+    }
+    std::vector<char> ball;
+    std::vector<size_t> sz;
+    RC(allgather_bytes(ctx, pairs.data(), pairs.size() * sizeof(int64_t), ball, sz));
+    const int64_t *all = reinterpret_cast<const int64_t *>(ball.data());
+    const size_t npairs = ball.size() / (2 * sizeof(int64_t));
+    std::vector<int64_t> halo(dA.halo_globals.begin(), dA.halo_globals.end());   // sorted
+    for (size_t t = 0; t < npairs; ++t)
+      if (all[2 * t] == rk && !std::binary_search(halo.begin(), halo.end(), all[2 * t + 1])) extra.push_back(all[2 * t + 1]);
+    std::sort(extra.begin(), extra.end());
+  }
+  // A's rows in its LOCAL column space [owned | halo]: the prolongator rows in that order
+  auto perm_rows = [&](const DevCsr &m, const std::vector<int64_t> &more, HostCsr &Pperm, std::vector<int64_t> &colg) -> int {
+    std::vector<int64_t> want(m.halo_globals.begin(), m.halo_globals.end());
+    want.insert(want.end(), more.begin(), more.end());
+    HostCsr halo;
+    RC(fetch_rows(ctx, P0, off0.data(), want, halo));
+    Pperm = P0;
+    Pperm.nrows = P0.nrows + halo.nrows;
+    for (int64_t i = 0; i < halo.nrows; ++i) Pperm.rp.push_back(Pperm.rp.back() + (halo.rp[i + 1] - halo.rp[i]));
+    Pperm.col.insert(Pperm.col.end(), halo.col.begin(), halo.col.end());
+    Pperm.val.insert(Pperm.val.end(), halo.val.begin(), halo.val.end());
+    colg.resize(Pperm.nrows);
+    for (int64_t q = 0; q < P0.nrows; ++q) colg[q] = off0[rk] + q;
+    for (size_t q = 0; q < want.size(); ++q) colg[P0.nrows + q] = want[q];
+    return ALFD_OK;
+  };
+  HostCsr PpA, PpC, AP_loc, AP_halo, CP_loc;
+  std::vector<int64_t> colgA, colgC;
+  RC(perm_rows(dA, extra, PpA, colgA));
+  {   // A_r * P on the device, fetched (its rows are served to the neighbours below)
+    DevRawCsr dP, dAP;
+    RC(upload_raw(ctx, PpA, dP));
+    bool fits = false;
+    RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, dP.rp, dP.col, dP.val, n1, dAP, &fits));
+    dP.release();
+    if (!fits) return ctx->err = "partitioned Galerkin product: a row exceeds the device kernel's column set", ALFD_E_UNSUPPORTED;
+    RC(download_raw(ctx, dAP, AP_loc));
+    dAP.release();
+  }
+  {
+    std::vector<int64_t> want(dA.halo_globals.begin(), dA.halo_globals.end());
+    want.insert(want.end(), extra.begin(), extra.end());
+    RC(fetch_rows(ctx, AP_loc, off0.data(), want, AP_halo));
+  }
+  // R_owned: one row per owned coarse unknown, entries over the local fine space [owned | halo] in GLOBAL fine order
+  const int64_t c0 = coff[rk], nc_loc = coff[rk + 1] - c0;
+  HostCsr Rl, APp;
+  {
+    std::vector<int64_t> cnt(nc_loc + 1, 0);
+    for (int64_t q = 0; q < PpA.nrows; ++q)
+      for (int64_t k = PpA.rp[q]; k < PpA.rp[q + 1]; ++k) {
+        const int64_t I = PpA.col[k];
+        if (I >= c0 && I < c0 + nc_loc) cnt[I - c0 + 1]++;
+      }
+    for (int64_t I = 0; I < nc_loc; ++I) cnt[I + 1] += cnt[I];
+    std::vector<std::pair<int64_t, std::pair<int32_t, double>>> ent(cnt[nc_loc]);   // (global fine id, (local index, value))
+    std::vector<int64_t> cur(cnt.begin(), cnt.end() - 1);
+    for (int64_t q = 0; q < PpA.nrows; ++q)
+      for (int64_t k = PpA.rp[q]; k < PpA.rp[q + 1]; ++k) {
+        const int64_t I = PpA.col[k];
+        if (I >= c0 && I < c0 + nc_loc) ent[cur[I - c0]++] = {colgA[q], {(int32_t)q, PpA.val[k]}};
+      }
+    Rl.nrows = nc_loc;
+    Rl.ncols = PpA.nrows;
+    Rl.rp = cnt;
+    Rl.col.resize(ent.size());
+    Rl.val.resize(ent.size());
+    for (int64_t I = 0; I < nc_loc; ++I) {
+      std::sort(ent.begin() + cnt[I], ent.begin() + cnt[I + 1], [](const auto &a, const auto &b) { return a.first < b.first; });
+      for (int64_t k = cnt[I]; k < cnt[I + 1]; ++k) Rl.col[k] = ent[k].second.first, Rl.val[k] = ent[k].second.second;
+    }
+    APp = AP_loc;
+    APp.nrows = AP_loc.nrows + AP_halo.nrows;
+    for (int64_t i = 0; i < AP_halo.nrows; ++i) APp.rp.push_back(APp.rp.back() + (AP_halo.rp[i + 1] - AP_halo.rp[i]));
+    APp.col.insert(APp.col.end(), AP_halo.col.begin(), AP_halo.col.end());
+    APp.val.insert(APp.val.end(), AP_halo.val.begin(), AP_halo.val.end());
+  }
+  {
+    // every prolongator entry must have been seen by the rank that forms its coarse row: the fine rows in the support
+    // of an owned coarse unknown have to lie in this rank's rows or in A's halo (coarse partition aligned with the fine one)
+    int64_t cnt2[2] = {(int64_t)Rl.col.size(), P0.nnz()};
+    std::vector<char> ball;
+    std::vector<size_t> sz;
+    RC(allgather_bytes(ctx, cnt2, sizeof(cnt2), ball, sz));
+    int64_t seen = 0, total = 0;
+    for (int p = 0; p < P; ++p) {
+      int64_t v[2];
+      std::memcpy(v, ball.data() + (size_t)p * sizeof(cnt2), sizeof(cnt2));
+      seen += v[0];
+      total += v[1];
+    }
+    if (seen != total)
+      return ctx->err = "partitioned CSR prolongator: a coarse unknown's fine support leaves its rank's rows + halo of A "
+                        "(alfd_set_aggregate_partition must follow the fine partition)", ALFD_E_INVALID;
+  }
+  HostCsr A1_loc;
+  RC(product(ctx, Rl, APp, A1_loc));
+  RC(gather_csr(ctx, A1_loc, nullptr, n1, A1));
+  // C_1 = C P: rows of the owned multipliers, then gathered
+  if (C1) {
+    RC(perm_rows(dC, {}, PpC, colgC));
+    {
+      HostCsr Cl;
+      RC(download_csr(ctx, dC, Cl));
+      Cl.ncols = PpC.nrows;
+      RC(product(ctx, Cl, PpC, CP_loc));
+    }
+    RC(gather_csr(ctx, CP_loc, nullptr, n1, *C1));
+  }
+  Rg = Rl;
+  Rg.ncols = off0.back();
+  for (size_t k = 0; k < Rg.col.size(); ++k) Rg.col[k] = (int32_t)colgA[Rl.col[k]];
+  return ALFD_OK;
+}
+
 // ALFD_PREC_MULTILEVEL through CSR prolongators on a ROW-PARTITIONED context (round 3): the fine level stays
 // partitioned, every level below it -- and the interface patch -- is REPLICATED on all ranks.  Level 0: this rank holds
 // the prolongator rows of its own fine unknowns (global coarse ids) and alfd_set_aggregate_partition(0, ...) names the
@@ -5556,108 +5925,11 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
   HostCsr A1, C1, Ct1;
   {
     PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
-    // A's rows in its LOCAL column space [owned | halo]: the prolongator rows in that order
-    DevCsr &dA = ctx->mat[ALFD_A], &dC = ctx->mat[ALFD_C];
-    auto perm_rows = [&](const DevCsr &m, HostCsr &Pperm, std::vector<int64_t> &colg) -> int {
-      std::vector<int64_t> want(m.halo_globals.begin(), m.halo_globals.end());
-      HostCsr halo;
-      RC(fetch_rows(ctx, P0, off0.data(), want, halo));
-      Pperm = P0;
-      Pperm.nrows = P0.nrows + halo.nrows;
-      for (int64_t i = 0; i < halo.nrows; ++i) Pperm.rp.push_back(Pperm.rp.back() + (halo.rp[i + 1] - halo.rp[i]));
-      Pperm.col.insert(Pperm.col.end(), halo.col.begin(), halo.col.end());
-      Pperm.val.insert(Pperm.val.end(), halo.val.begin(), halo.val.end());
-      colg.resize(Pperm.nrows);
-      for (int64_t q = 0; q < P0.nrows; ++q) colg[q] = off0[rk] + q;
-      for (size_t q = 0; q < want.size(); ++q) colg[P0.nrows + q] = want[q];
-      return ALFD_OK;
-    };
-    HostCsr PpA, PpC, AP_loc, AP_halo, CP_loc;
-    std::vector<int64_t> colgA, colgC;
-    RC(perm_rows(dA, PpA, colgA));
-    {   // A_r * P on the device, fetched (its rows are served to the neighbours below)
-      DevRawCsr dP, dAP;
-      RC(upload_raw(ctx, PpA, dP));
-      bool fits = false;
-      RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, dP.rp, dP.col, dP.val, n1, dAP, &fits));
-      dP.release();
-      if (!fits) return ctx->err = "partitioned Galerkin product: a row exceeds the device kernel's column set", ALFD_E_UNSUPPORTED;
-      RC(download_raw(ctx, dAP, AP_loc));
-      dAP.release();
-    }
-    {
-      std::vector<int64_t> want(dA.halo_globals.begin(), dA.halo_globals.end());
-      RC(fetch_rows(ctx, AP_loc, off0.data(), want, AP_halo));
-    }
-    // R_owned: one row per owned coarse unknown, entries over the local fine space [owned | halo] in GLOBAL fine order
-    const int64_t c0 = coff[rk], nc_loc = coff[rk + 1] - c0;
-    HostCsr Rl, APp;
-    {
-      std::vector<int64_t> cnt(nc_loc + 1, 0);
-      for (int64_t q = 0; q < PpA.nrows; ++q)
-        for (int64_t k = PpA.rp[q]; k < PpA.rp[q + 1]; ++k) {
-          const int64_t I = PpA.col[k];
-          if (I >= c0 && I < c0 + nc_loc) cnt[I - c0 + 1]++;
-        }
-      for (int64_t I = 0; I < nc_loc; ++I) cnt[I + 1] += cnt[I];
-      std::vector<std::pair<int64_t, std::pair<int32_t, double>>> ent(cnt[nc_loc]);   // (global fine id, (local index, value))
-      std::vector<int64_t> cur(cnt.begin(), cnt.end() - 1);
-      for (int64_t q = 0; q < PpA.nrows; ++q)
-        for (int64_t k = PpA.rp[q]; k < PpA.rp[q + 1]; ++k) {
-          const int64_t I = PpA.col[k];
-          if (I >= c0 && I < c0 + nc_loc) ent[cur[I - c0]++] = {colgA[q], {(int32_t)q, PpA.val[k]}};
-        }
-      Rl.nrows = nc_loc;
-      Rl.ncols = PpA.nrows;
-      Rl.rp = cnt;
-      Rl.col.resize(ent.size());
-      Rl.val.resize(ent.size());
-      for (int64_t I = 0; I < nc_loc; ++I) {
-        std::sort(ent.begin() + cnt[I], ent.begin() + cnt[I + 1], [](const auto &a, const auto &b) { return a.first < b.first; });
-        for (int64_t k = cnt[I]; k < cnt[I + 1]; ++k) Rl.col[k] = ent[k].second.first, Rl.val[k] = ent[k].second.second;
-      }
-      APp = AP_loc;
-      APp.nrows = AP_loc.nrows + AP_halo.nrows;
-      for (int64_t i = 0; i < AP_halo.nrows; ++i) APp.rp.push_back(APp.rp.back() + (AP_halo.rp[i + 1] - AP_halo.rp[i]));
-      APp.col.insert(APp.col.end(), AP_halo.col.begin(), AP_halo.col.end());
-      APp.val.insert(APp.val.end(), AP_halo.val.begin(), AP_halo.val.end());
-    }
-    {
-      // every prolongator entry must have been seen by the rank that forms its coarse row: the fine rows in the support
-      // of an owned coarse unknown have to lie in this rank's rows or in A's halo (coarse partition aligned with the fine one)
-      int64_t cnt2[2] = {(int64_t)Rl.col.size(), P0.nnz()};
-      std::vector<char> ball;
-      std::vector<size_t> sz;
-      RC(allgather_bytes(ctx, cnt2, sizeof(cnt2), ball, sz));
-      int64_t seen = 0, total = 0;
-      for (int p = 0; p < P; ++p) {
-        int64_t v[2];
-        std::memcpy(v, ball.data() + (size_t)p * sizeof(cnt2), sizeof(cnt2));
-        seen += v[0];
-        total += v[1];
-      }
-      if (seen != total)
-        return ctx->err = "partitioned CSR prolongator: a coarse unknown's fine support leaves its rank's rows + halo of A "
-                          "(alfd_set_aggregate_partition must follow the fine partition)", ALFD_E_INVALID;
-    }
-    HostCsr A1_loc;
-    RC(product(ctx, Rl, APp, A1_loc));
-    RC(gather_csr(ctx, A1_loc, nullptr, n1, A1));
-    // C_1 = C P: rows of the owned multipliers, then gathered
-    RC(perm_rows(dC, PpC, colgC));
-    {
-      HostCsr Cl;
-      RC(download_csr(ctx, dC, Cl));
-      Cl.ncols = PpC.nrows;
-      RC(product(ctx, Cl, PpC, CP_loc));
-    }
-    RC(gather_csr(ctx, CP_loc, nullptr, n1, C1));
+    HostCsr Rg;
+    RC(rep_level0_products(ctx, P0, coff, ctx->hier[0].built_partitioned, A1, &C1, Rg));
     transpose_host(C1, Ct1);
     // the partitioned transfer pair of level 0 <-> 1: R rows of the owned coarse unknowns (global fine columns, halo on
     // the fine vector), P rows of the owned fine unknowns addressing the replicated coarse vector
-    HostCsr Rg = Rl;
-    Rg.ncols = off0.back();
-    for (size_t k = 0; k < Rg.col.size(); ++k) Rg.col[k] = (int32_t)colgA[Rl.col[k]];
     MlLevel &N = ctx->hier[0].ml[1];
     PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
     RC(upload_level_part(ctx, N.R, Rg, off0.data(), false));
@@ -6695,6 +6967,7 @@ int alfd_set_aggregates(alfd_ctx_t ctx, int level, int64_t n_fine, const int32_t
     ctx->hier[0].wgt[level].clear();
   ctx->hier[0].ncoarse[level] = n_coarse;
   ctx->hier[0].P[level] = HostCsr();
+  ctx->hier[0].built_partitioned = false;
   for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) ctx->hier[0].agg[l].clear(), ctx->hier[0].wgt[l].clear(), ctx->hier[0].P[l] = HostCsr();
   ctx->is_setup = false;
   return ALFD_OK;
@@ -6734,6 +7007,7 @@ int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_f
   H.agg[level].clear();
   H.wgt[level].clear();
   H.ncoarse[level] = n_coarse;
+  H.built_partitioned = false;   // a caller-supplied level: the halo condition of alfd_set_prolongator holds again
   for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) {   // levels below are redefined by later calls
     H.agg[l].clear();
     H.P[l] = HostCsr();
@@ -6810,6 +7084,102 @@ int alfd_host_aggregate_level(int64_t nrows, const int64_t *rp, const int32_t *c
   return ALFD_OK;
 }
 
+int alfd_host_strength_graph(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int32_t block_size,
+                             double threshold, double *d, int32_t *fixed, int64_t *node_ptr, int32_t *nbr, double *weight,
+                             int64_t capacity, int64_t *nnz) {
+  if (nrows < 1 || !rp || !col || !val || !nnz || block_size < 1 || nrows % block_size || !(threshold >= 0.0) ||
+      rp[0] != 0)
+    return ALFD_E_INVALID;
+  for (int64_t i = 0; i < nrows; ++i)
+    if (rp[i + 1] < rp[i]) return ALFD_E_INVALID;
+  for (int64_t k = 0; k < rp[nrows]; ++k)
+    if (col[k] < 0) return ALFD_E_INVALID;
+  HostCsr A;
+  A.nrows = A.ncols = nrows;
+  A.rp.assign(rp, rp + nrows + 1);
+  A.col.assign(col, col + rp[nrows]);
+  A.val.assign(val, val + rp[nrows]);
+  const int64_t nn = nrows / block_size;
+  std::vector<double> dd, gw;
+  std::vector<int32_t> fx, gc;
+  std::vector<int64_t> gp;
+  node_diag_host(A, 0, block_size, dd, fx);
+  node_graph_host(A, 0, block_size, threshold, nn, dd.data(), fx.data(), gp, gc, gw);
+  *nnz = gp[nn];
+  if (d) std::copy(dd.begin(), dd.end(), d);
+  if (fixed) std::copy(fx.begin(), fx.end(), fixed);
+  if (node_ptr) std::copy(gp.begin(), gp.end(), node_ptr);
+  if (nbr || weight) {
+    if (capacity < gp[nn]) return ALFD_E_INVALID;
+    if (nbr) std::copy(gc.begin(), gc.end(), nbr);
+    if (weight) std::copy(gw.begin(), gw.end(), weight);
+  }
+  return ALFD_OK;
+}
+
+int alfd_host_aggregate_graph(int64_t n_nodes, const int32_t *fixed, const int64_t *node_ptr, const int32_t *nbr,
+                              const double *weight, int32_t block_size, int32_t max_aggregate_nodes, int32_t *agg,
+                              int64_t *n_coarse) {
+  if (n_nodes < 1 || !fixed || !node_ptr || !agg || !n_coarse || block_size < 1 || max_aggregate_nodes < 2 ||
+      node_ptr[0] != 0 || n_nodes > INT32_MAX / block_size)
+    return ALFD_E_INVALID;
+  for (int64_t I = 0; I < n_nodes; ++I)
+    if (node_ptr[I + 1] < node_ptr[I]) return ALFD_E_INVALID;
+  if (node_ptr[n_nodes] > 0 && (!nbr || !weight)) return ALFD_E_INVALID;
+  for (int64_t k = 0; k < node_ptr[n_nodes]; ++k)
+    if (nbr[k] < 0 || nbr[k] >= n_nodes) return ALFD_E_INVALID;
+  std::vector<int32_t> a;
+  aggregate_graph(n_nodes * block_size, n_nodes, block_size, max_aggregate_nodes, fixed, node_ptr, nbr, weight, a, *n_coarse);
+  std::copy(a.begin(), a.end(), agg);
+  return ALFD_OK;
+}
+
+int alfd_build_strength_graph(alfd_ctx_t ctx, int32_t block_size, double threshold, int64_t *n_nodes, int64_t *nnz) {
+  CHECK_CTX();
+  ctx->sg = alfd_ctx::StrengthGraph();
+  // every check below reads what all ranks hold alike (arguments, the partition) or fails before any collective
+  if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold))
+    return ctx->err = "alfd_build_strength_graph: bad arguments", ALFD_E_INVALID;
+  if (ctx->nranks > 1) {
+    if (ctx->part.empty()) return ctx->err = "alfd_set_partition must precede alfd_build_strength_graph", ALFD_E_INVALID;
+    for (int64_t o : ctx->part[0])
+      if (o % block_size)
+        return ctx->err = "alfd_build_strength_graph: the partition offsets of block 0 must be multiples of block_size",
+               ALFD_E_INVALID;
+  }
+  // rank-local preconditions: agreed on before the first exchange
+  int loc = ALFD_OK;
+  const DevCsr &A = ctx->mat[ALFD_A];
+  const int64_t N = ctx->nranks > 1 ? ctx->part[0].back() : A.nrows;
+  if (!A.present) ctx->err = "upload slot A first", loc = ALFD_E_NOT_SETUP;
+  else if (A.sparse || A.ncols != N || A.nrows % block_size ||
+           (ctx->nranks > 1 && A.nrows != ctx->part[0][ctx->rank + 1] - ctx->part[0][ctx->rank]))
+    ctx->err = "alfd_build_strength_graph: slot A must hold this rank's rows of a square operator, a multiple of block_size",
+    loc = ALFD_E_INVALID;
+  RC(joint_status(ctx, loc, 0, nullptr));
+  RC(strength_graph_dev(ctx, block_size, threshold));
+  if (n_nodes) *n_nodes = ctx->sg.n_nodes;
+  if (nnz) *nnz = ctx->sg.gp.back();
+  return ALFD_OK;
+}
+
+int alfd_get_strength_graph(alfd_ctx_t ctx, double *d, int32_t *fixed, int64_t *node_ptr, int32_t *nbr, double *weight,
+                            int64_t capacity, int32_t *on_device) {
+  CHECK_CTX();
+  const alfd_ctx::StrengthGraph &G = ctx->sg;
+  if (!G.have) return ctx->err = "alfd_build_strength_graph first", ALFD_E_NOT_SETUP;
+  if (d) std::copy(G.d.begin(), G.d.end(), d);
+  if (fixed) std::copy(G.fixed.begin(), G.fixed.end(), fixed);
+  if (node_ptr) std::copy(G.gp.begin(), G.gp.end(), node_ptr);
+  if (nbr || weight) {
+    if (capacity < G.gp.back()) return ALFD_E_INVALID;
+    if (nbr) std::copy(G.gc.begin(), G.gc.end(), nbr);
+    if (weight) std::copy(G.gw.begin(), G.gw.end(), weight);
+  }
+  if (on_device) *on_device = G.on_device ? 1 : 0;
+  return ALFD_OK;
+}
+
 int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacity, int64_t *n_fine, int64_t *n_coarse) {
   return alfd_get_aggregates_block(ctx, 0, level, agg, capacity, n_fine, n_coarse);
 }
@@ -6828,57 +7198,24 @@ int alfd_get_aggregates_block(alfd_ctx_t ctx, int block, int level, int32_t *agg
   return ALFD_OK;
 }
 
-// alfd_build_smoothed_aggregation (tau = 0, cap = 0: nothing is truncated) and alfd_build_smoothed_aggregation_truncated
-// on (A, Ct, invW, gamma) for block 0, on (A2, M, invW, gamma2) for block 1 (alfd_build_smoothed_aggregation_block)
-static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_size, double threshold,
-                                      int32_t max_aggregate_nodes, double damping, double tau, int32_t cap, int64_t min_coarse,
-                                      int32_t max_levels, int32_t *levels_out, double *omega_out) {
-  CHECK_CTX();
-  if (ctx->nranks > 1) return ctx->err = "alfd_build_smoothed_aggregation is single-rank", ALFD_E_UNSUPPORTED;
-  RC(check_block(ctx, block));
-  alfd_ctx::Hierarchy &H = ctx->hier[block];
-  const int slotA = block == 0 ? ALFD_A : ALFD_A2, slotCt = block == 0 ? ALFD_CT : ALFD_M;
-  if (block == 1 && !ctx->mat[slotA].present)
-    return ctx->err = "a block-1 hierarchy needs slot A2 (the elliptic-interface variants)", ALFD_E_INVALID;
-  if (ctx->configured && gd_nested(ctx))
-    return ctx->err = "alfd_build_smoothed_aggregation: grad_div_in_A = 0 has no multilevel inner preconditioner", ALFD_E_UNSUPPORTED;
-  if (!ctx->mat[slotA].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
-  if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
-      !(damping > 0.0) || !std::isfinite(damping))
-    return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
-  if (!(tau >= 0.0) || !(tau < 1.0) || cap < 0) {
-    H.clear_input();
-    ctx->is_setup = false;
-    return ctx->err = "alfd_build_smoothed_aggregation_truncated: drop_tolerance must be in [0, 1), max_row_entries >= 0",
-           ALFD_E_INVALID;
-  }
-  if (ctx->mat[slotA].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
-  if (ctx->mat[slotA].nrows != ctx->mat[slotA].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
-  if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
-  const int its = ctx->configured ? ctx->cfg.cheb_power_its : 20;
-  if (its < 1) return ctx->err = "cheb_power_its must be >= 1", ALFD_E_INVALID;
-  // the penalty term: an AL variant with a diagonal W^-1, a non-zero gamma, A not already augmented, Ct and W^-1 present
-  const alfd_config &c = ctx->cfg;
-  const double gamma = block == 0 ? c.gamma : c.gamma2;
-  const bool use_pen = ctx->configured && c.variant != ALFD_RATIONAL && c.w_inverse == ALFD_W_DIAGONAL &&
-                       !c.aug_assembled && gamma != 0.0 && ctx->mat[slotCt].present && ctx->diag[ALFD_INVW] &&
-                       (block == 0 || is_elliptic(c.variant));
-  HostCsr A, An, C, Ct, Cn, Q, P, R, AP;
-  std::vector<double> w;
-  RC(download_csr(ctx, ctx->mat[slotA], A));
-  if (use_pen) {
-    RC(download_csr(ctx, ctx->mat[slotCt], Ct));
-    if (Ct.nrows != A.nrows || ctx->diag_n[ALFD_INVW] != Ct.ncols)
-      return ctx->err = "alfd_build_smoothed_aggregation: Ct / W^-1 do not match A", ALFD_E_INVALID;
-    w.resize(Ct.ncols);
-    if (!w.empty())
-      HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
-    HIPC(hipStreamSynchronize(ctx->stream));
-    transpose_host(Ct, C);
-  }
-  H.clear_input();
-  ctx->is_setup = false;
-  int nlev = 0;
+struct SaParams {
+  int32_t block_size, max_aggregate_nodes, cap, max_levels, its;
+  double threshold, damping, tau, gamma;
+  int64_t min_coarse;
+  bool use_pen;
+};
+
+// The levels nlev, nlev + 1, ... of a smoothed-aggregation hierarchy from the operators (A, C, Ct = C^T, w) of level
+// nlev, whole on this rank: the single-rank build from level 0, the replicated levels >= 1 of a partitioned one.
+static int sa_build_levels(alfd_ctx *ctx, alfd_ctx::Hierarchy &H, const SaParams &sp, HostCsr &A, HostCsr &C, HostCsr &Ct,
+                           const std::vector<double> &w, int &nlev, double *omega_out) {
+  const int32_t block_size = sp.block_size, max_aggregate_nodes = sp.max_aggregate_nodes, cap = sp.cap,
+                max_levels = sp.max_levels;
+  const int its = sp.its;
+  const double threshold = sp.threshold, damping = sp.damping, tau = sp.tau, gamma = sp.gamma;
+  const int64_t min_coarse = sp.min_coarse;
+  const bool use_pen = sp.use_pen;
+  HostCsr An, Cn, Q, P, R, AP;
   std::vector<double> d, f;
   while (nlev < max_levels) {
     std::vector<int32_t> agg;
@@ -6926,6 +7263,338 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_s
       transpose_host(C, Ct);
     }
   }
+  return ALFD_OK;
+}
+
+// alfd_build_smoothed_aggregation[_truncated] on a ROW-PARTITIONED context (block 0): the single-rank hierarchy bit for bit,
+// whatever the partition.  Level 0 is built from the resident rows (A is not downloaded; the few rows of Ct and C are):
+//   graph     sa_node_graph_kernel on the own nodes, d / fixed all-gathered; the graph rows are all-gathered and the three
+//             greedy passes run redundantly on every rank (aggregates do not respect the slabs);
+//   order     the resident rows already are in global CSR order, sa_global_cols_kernel renames their columns;
+//   d, lambda sa_diag_rows_kernel, then its steps of sa_power_t_kernel / sa_power_rows_kernel on the replicated v with an
+//             all-gather of y per step; both norms are the one sequential fma sum of sa_lambda over the whole vector, on
+//             every rank's host;
+//   penalty   gamma Ct W^-1 (C P_tent) by the generic product from the gathered C and the own rows of Ct;
+//   P_0       sa_prolongator_kernel / sa_truncated_prolongator_kernel, unchanged, on the view (own rows of P_0).
+// Levels >= 1: A_1, C_1 replicated by rep_level0_products, then sa_build_levels redundantly on every rank.  After every
+// rank-local phase the ranks exchange a status word (joint_status): a failure is returned by all, and a row with more
+// candidates than the kernel holds sends all ranks to the host routines together.
+static int build_sa_partitioned(alfd_ctx *ctx, SaParams sp, int32_t *levels_out, double *omega_out, bool *touched) {
+  alfd_ctx::Hierarchy &H = ctx->hier[0];
+  const alfd_config &c = ctx->cfg;
+  const int P = ctx->nranks, rk = ctx->rank, last = ctx->nblocks - 1, bs = sp.block_size;
+  for (int64_t o : ctx->part[0])   // (the caller has checked that there is a partition)
+    if (o % bs)
+      return ctx->err = "alfd_build_smoothed_aggregation: the partition offsets of block 0 must be multiples of block_size",
+             ALFD_E_INVALID;
+  DevCsr &dA = ctx->mat[ALFD_A], &dCt = ctx->mat[ALFD_CT], &dC = ctx->mat[ALFD_C];
+  const int64_t row0 = ctx->part[0][rk], n = ctx->part[0][rk + 1] - row0, N = ctx->part[0].back();
+  const int64_t lam0 = ctx->part[last][rk], M = ctx->part[last].back();
+  int loc = ALFD_OK;
+  if (!dA.present) ctx->err = "upload slot A first", loc = ALFD_E_NOT_SETUP;
+  else if (dA.sparse || dA.nrows != n || dA.ncols != N)
+    ctx->err = "alfd_build_smoothed_aggregation: slot A must hold this rank's rows of the square operator", loc = ALFD_E_INVALID;
+  RC(joint_status(ctx, loc, 0, nullptr));
+  // the penalty term: the single-rank rule; the pieces must be there on every rank or on none
+  const bool pen_cfg = ctx->configured && c.variant != ALFD_RATIONAL && c.w_inverse == ALFD_W_DIAGONAL && !c.aug_assembled &&
+                       sp.gamma != 0.0;
+  const bool have = pen_cfg && dCt.present && dC.present && ctx->diag[ALFD_INVW] != nullptr;
+  loc = ALFD_OK;
+  if (have && (dCt.nrows != n || dCt.ncols != M || dC.ncols != N || ctx->diag_n[ALFD_INVW] != dC.nrows))
+    ctx->err = "alfd_build_smoothed_aggregation: Ct / C / W^-1 do not match A and the partition", loc = ALFD_E_INVALID;
+  int any_have = 0, any_not = 0;
+  RC(joint_status(ctx, loc, have ? 1 : 0, &any_have));
+  RC(joint_status(ctx, ALFD_OK, have ? 0 : 1, &any_not));
+  if (any_have && any_not)
+    return ctx->err = "alfd_build_smoothed_aggregation: Ct, C and W^-1 must be uploaded on every rank or on none", ALFD_E_INVALID;
+  sp.use_pen = have;
+  H.clear_input();
+  ctx->is_setup = false;
+  *touched = true;
+  // ---- aggregates: device graph rows, gathered; greedy passes on every rank
+  RC(strength_graph_dev(ctx, bs, sp.threshold));
+  const int64_t nn = N / bs;
+  std::vector<int32_t> agg;
+  int64_t nc = 0;
+  {
+    const alfd_ctx::StrengthGraph &G = ctx->sg;
+    std::vector<int32_t> len(G.n_nodes);
+    for (int64_t I = 0; I < G.n_nodes; ++I) len[I] = (int32_t)(G.gp[I + 1] - G.gp[I]);
+    std::vector<char> bl, bc, bw, bf;
+    std::vector<size_t> sz;
+    RC(allgather_bytes(ctx, len.data(), len.size() * 4, bl, sz));
+    RC(allgather_bytes(ctx, G.gc.data(), G.gc.size() * 4, bc, sz));
+    RC(allgather_bytes(ctx, G.gw.data(), G.gw.size() * 8, bw, sz));
+    RC(allgather_bytes(ctx, G.fixed.data(), G.fixed.size() * 4, bf, sz));
+    if ((int64_t)(bl.size() / 4) != nn || (int64_t)(bf.size() / 4) != nn || bc.size() / 4 != bw.size() / 8)
+      return ctx->err = "alfd_build_smoothed_aggregation: inconsistent graph pieces", ALFD_E_COMM;
+    std::vector<int64_t> gp(nn + 1, 0);
+    const int32_t *gl = reinterpret_cast<const int32_t *>(bl.data());
+    for (int64_t I = 0; I < nn; ++I) gp[I + 1] = gp[I] + gl[I];
+    if (gp[nn] != (int64_t)(bc.size() / 4)) return ctx->err = "alfd_build_smoothed_aggregation: inconsistent graph pieces", ALFD_E_COMM;
+    aggregate_graph(N, nn, bs, sp.max_aggregate_nodes, reinterpret_cast<const int32_t *>(bf.data()), gp.data(),
+                    reinterpret_cast<const int32_t *>(bc.data()), reinterpret_cast<const double *>(bw.data()), agg, nc);
+  }
+  if (nc < 1 || nc >= N) return ctx->err = "algebraic aggregation found nothing to coarsen", ALFD_E_INVALID;
+  // ---- the build-time views: A's rows with columns n + global id (device), Ct / C rows with global ids (host)
+  const int64_t shift = n;
+  int32_t *d_haloA = nullptr, *d_vcol = nullptr;
+  double *d_w = nullptr, *d_d = nullptr, *d_v = nullptr, *d_t = nullptr, *d_y = nullptr;
+  DevRawCsr dCtl, dCg;
+  auto release = [&]() {
+    for (void *q : {(void *)d_haloA, (void *)d_vcol, (void *)d_w, (void *)d_d, (void *)d_v, (void *)d_t, (void *)d_y})
+      if (q) hipFree(q);
+    dCtl.release();
+    dCg.release();
+  };
+  auto hip = [&](hipError_t e) -> int {
+    if (e == hipSuccess) return ALFD_OK;
+    ctx->err = std::string("HIP error in the partitioned smoothed-aggregation build: ") + hipGetErrorString(e);
+    return (int)ALFD_E_HIP;
+  };
+#define SB(call)                      \
+  do {                                \
+    const int rc__ = hip(call);       \
+    if (rc__ != ALFD_OK) return rc__; \
+  } while (0)
+  HostCsr Ctl, Cl, Cg;
+  std::vector<double> w_loc, w_g;
+  auto to_global = [](HostCsr &h, const DevCsr &m, int64_t c0, int64_t ncols_global) {
+    for (size_t k = 0; k < h.col.size(); ++k)
+      h.col[k] = (int32_t)(h.col[k] < m.n_local_cols ? c0 + h.col[k] : m.halo_globals[h.col[k] - m.n_local_cols]);
+    h.ncols = ncols_global;
+  };
+  auto views = [&]() -> int {
+    if (!dA.halo_globals.empty()) {
+      SB(hipMalloc((void **)&d_haloA, dA.halo_globals.size() * sizeof(int32_t)));
+      SB(hipMemcpyAsync(d_haloA, dA.halo_globals.data(), dA.halo_globals.size() * sizeof(int32_t), hipMemcpyHostToDevice,
+                        ctx->stream));
+    }
+    SB(hipMalloc((void **)&d_vcol, std::max<int64_t>(dA.nnz, 1) * sizeof(int32_t)));
+    if (dA.nnz > 0) {
+      hipLaunchKernelGGL(sa_global_cols_kernel, dim3((unsigned)((dA.nnz + 255) / 256)), dim3(256), 0, ctx->stream, dA.nnz,
+                         dA.col, dA.n_local_cols, row0, d_haloA, shift, d_vcol);
+      SB(hipGetLastError());
+    }
+    if (sp.use_pen) {
+      RC(download_csr(ctx, dCt, Ctl));
+      to_global(Ctl, dCt, lam0, M);
+      RC(download_csr(ctx, dC, Cl));
+      to_global(Cl, dC, row0, N);
+      w_loc.resize(ctx->diag_n[ALFD_INVW]);
+      if (!w_loc.empty())
+        SB(hipMemcpyAsync(w_loc.data(), ctx->diag[ALFD_INVW], w_loc.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SB(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  int rc = joint_status(ctx, views(), 0, nullptr);
+  if (rc != ALFD_OK) return release(), rc;
+  if (sp.use_pen) {
+    rc = gather_csr(ctx, Cl, nullptr, N, Cg);
+    std::vector<char> bw;
+    std::vector<size_t> sz;
+    if (rc == ALFD_OK) rc = allgather_bytes(ctx, w_loc.data(), w_loc.size() * 8, bw, sz);
+    if (rc == ALFD_OK && ((int64_t)(bw.size() / 8) != M || Cg.nrows != M))
+      ctx->err = "alfd_build_smoothed_aggregation: the ranks' rows of C / W^-1 do not add up to the partition", rc = ALFD_E_COMM;
+    if (rc != ALFD_OK) return release(), rc;
+    w_g.resize(M);
+    std::memcpy(w_g.data(), bw.data(), bw.size());
+  }
+  // ---- d and lambda_max(D^-1 Aug)
+  std::vector<double> d_loc(n), y_loc(n), v(N), y(N);
+  const unsigned gn = (unsigned)std::max<int64_t>(1, (n + 255) / 256), gm = (unsigned)std::max<int64_t>(1, (M + 255) / 256);
+  auto diag = [&]() -> int {
+    if (sp.use_pen) {
+      RC(upload_raw(ctx, Ctl, dCtl));
+      RC(upload_raw(ctx, Cg, dCg));
+      SB(hipMalloc((void **)&d_w, std::max<int64_t>(M, 1) * sizeof(double)));
+      SB(hipMalloc((void **)&d_t, std::max<int64_t>(M, 1) * sizeof(double)));
+      if (M > 0) SB(hipMemcpyAsync(d_w, w_g.data(), M * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    }
+    SB(hipMalloc((void **)&d_d, std::max<int64_t>(n, 1) * sizeof(double)));
+    SB(hipMalloc((void **)&d_y, std::max<int64_t>(n, 1) * sizeof(double)));
+    SB(hipMalloc((void **)&d_v, std::max<int64_t>(N, 1) * sizeof(double)));
+    if (n > 0) {
+      hipLaunchKernelGGL(sa_diag_rows_kernel, dim3(gn), dim3(256), 0, ctx->stream, n, row0, shift, dA.rp, d_vcol, dA.val,
+                         sp.use_pen ? dCtl.rp : nullptr, dCtl.col, dCtl.val, d_w, sp.gamma, d_d);
+      SB(hipGetLastError());
+      SB(hipMemcpyAsync(d_loc.data(), d_d, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SB(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  rc = joint_status(ctx, diag(), 0, nullptr);
+  if (rc != ALFD_OK) return release(), rc;
+  for (int64_t i = 0; i < N; ++i) v[i] = 1.0 + (double)(((uint64_t)i * 2654435761ull) & 1023ull) * (1.0 / 1024.0);
+  double lam = 0.0;
+  int bad = ALFD_OK;   // a rank-local failure inside the loop: the rank keeps taking part, the status goes round afterwards
+  auto step = [&]() -> int {
+    SB(hipMemcpyAsync(d_v, v.data(), N * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    if (sp.use_pen && M > 0)
+      hipLaunchKernelGGL(sa_power_t_kernel, dim3(gm), dim3(256), 0, ctx->stream, M, dCg.rp, dCg.col, dCg.val, d_w, d_v, d_t);
+    if (n > 0) {
+      hipLaunchKernelGGL(sa_power_rows_kernel, dim3(gn), dim3(256), 0, ctx->stream, n, shift, dA.rp, d_vcol, dA.val,
+                         sp.use_pen ? dCtl.rp : nullptr, dCtl.col, dCtl.val, d_t, sp.gamma, d_v, d_d, d_y);
+      SB(hipGetLastError());
+      SB(hipMemcpyAsync(y_loc.data(), d_y, n * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    }
+    SB(hipStreamSynchronize(ctx->stream));
+    return ALFD_OK;
+  };
+  for (int it = 0; it < sp.its; ++it) {
+    double nv = 0.0;
+    for (int64_t i = 0; i < N; ++i) nv = std::fma(v[i], v[i], nv);
+    const double sc = 1.0 / std::sqrt(nv);
+    for (int64_t i = 0; i < N; ++i) v[i] = v[i] * sc;
+    if (bad == ALFD_OK) bad = step();
+    std::vector<char> by;
+    std::vector<size_t> sz;
+    rc = allgather_bytes(ctx, y_loc.data(), y_loc.size() * 8, by, sz);
+    if (rc == ALFD_OK && (int64_t)(by.size() / 8) != N) ctx->err = "alfd_build_smoothed_aggregation: inconsistent vector pieces", rc = ALFD_E_COMM;
+    if (rc != ALFD_OK) return release(), rc;
+    std::memcpy(y.data(), by.data(), by.size());
+    double ny = 0.0;
+    for (int64_t i = 0; i < N; ++i) ny = std::fma(y[i], y[i], ny);
+    lam = std::sqrt(ny);
+    std::swap(v, y);
+  }
+  rc = joint_status(ctx, bad, 0, nullptr);
+  if (rc != ALFD_OK) return release(), rc;
+  if (!(lam > 0.0) || !std::isfinite(lam))
+    return release(), ctx->err = "alfd_build_smoothed_aggregation: lambda_max(D^-1 Aug) of level 0 is not positive and finite "
+                                 "(zero diagonal?)", ALFD_E_INVALID;
+  const double omega = sp.damping / lam;
+  // ---- the own rows of P_0
+  std::vector<int32_t> agg_ext(agg.begin() + row0, agg.begin() + row0 + n);   // [agg of the own rows | agg of all unknowns]
+  agg_ext.insert(agg_ext.end(), agg.begin(), agg.end());
+  std::vector<double> f(n, 0.0);
+  for (int64_t i = 0; i < n; ++i)
+    if (agg_ext[i] >= 0) f[i] = -omega / d_loc[i];
+  HostCsr Q, Pl;
+  bool fits = false;
+  auto rows = [&]() -> int {
+    if (sp.use_pen) {
+      HostCsr Pt, Tm;
+      sa_tentative(agg, nc, Pt);
+      RC(product(ctx, Cg, Pt, Tm));
+      sa_scale_rows(Tm, w_g.data(), sp.gamma);
+      RC(product(ctx, Ctl, Tm, Q));
+    }
+    return sa_prolongator_dev_raw(ctx, n, dA.rp, d_vcol, dA.val, agg_ext, nc, f, Q, bs, sp.tau, sp.cap, Pl, &fits);
+  };
+  int any_nofit = 0;
+  {
+    const int l = rows();
+    rc = joint_status(ctx, l, fits ? 0 : 1, &any_nofit);
+  }
+  if (rc != ALFD_OK) return release(), rc;
+  if (any_nofit) {   // a row beyond the kernel's candidate set on some rank: every rank takes the host routines (same bits)
+    auto host_rows = [&]() -> int {
+      HostCsr h;
+      RC(download_csr(ctx, dA, h));
+      for (size_t k = 0; k < h.col.size(); ++k)
+        h.col[k] = (int32_t)(shift + (h.col[k] < dA.n_local_cols ? row0 + h.col[k] : dA.halo_globals[h.col[k] - dA.n_local_cols]));
+      sa_rows_host(h, agg_ext, nc, f, sp.use_pen ? &Q : nullptr, Pl);
+      if (sp.tau != 0.0 || sp.cap != 0) {
+        HostCsr T;
+        sa_truncate_host(Pl, agg_ext, bs, sp.tau, sp.cap, T);
+        std::swap(Pl, T);
+      }
+      return ALFD_OK;
+    };
+    rc = joint_status(ctx, host_rows(), 0, nullptr);
+    if (rc != ALFD_OK) return release(), rc;
+  }
+  release();
+#undef SB
+  H.agg[0].assign(agg_ext.begin(), agg_ext.begin() + n);
+  H.P[0] = Pl;
+  H.ncoarse[0] = nc;
+  H.built_partitioned = true;
+  std::vector<int64_t> &coff = ctx->ml_coff[0];   // any contiguous split is valid: whole nodes, evenly
+  coff.assign(P + 1, 0);
+  for (int p = 0; p <= P; ++p) coff[p] = (nc / bs) * p / P * bs;
+  if (omega_out) omega_out[0] = omega;
+  int nlev = 1;
+  if (!(nc <= sp.min_coarse || nlev >= sp.max_levels)) {
+    // ---- levels >= 1: the replicated Galerkin products of alfd_setup, then the single-rank loop on every rank
+    HostCsr A1, C1, Ct1, Rg;
+    RC(rep_level0_products(ctx, Pl, coff, true, A1, sp.use_pen ? &C1 : nullptr, Rg));
+    if (sp.use_pen) transpose_host(C1, Ct1);
+    const int l = sa_build_levels(ctx, H, sp, A1, C1, Ct1, w_g, nlev, omega_out);
+    RC(joint_status(ctx, l, 0, nullptr));
+  }
+  if (levels_out) *levels_out = nlev;
+  return ALFD_OK;
+}
+
+// alfd_build_smoothed_aggregation (tau = 0, cap = 0: nothing is truncated) and alfd_build_smoothed_aggregation_truncated
+// on (A, Ct, invW, gamma) for block 0, on (A2, M, invW, gamma2) for block 1 (alfd_build_smoothed_aggregation_block)
+static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_size, double threshold,
+                                      int32_t max_aggregate_nodes, double damping, double tau, int32_t cap, int64_t min_coarse,
+                                      int32_t max_levels, int32_t *levels_out, double *omega_out) {
+  CHECK_CTX();
+  RC(check_block(ctx, block));
+  const bool part = ctx->nranks > 1;   // block 0 on a partitioned context: collective, the rank-local checks are joint
+  // a rank group that has no row partition yet has nothing the collective build could work on, and the single-rank
+  // build is not defined on it: the answer such a context always got (the same on every rank, before any exchange)
+  if (part && ctx->part.empty())
+    return ctx->err = "alfd_build_smoothed_aggregation on a rank group needs alfd_set_partition (the single-rank build "
+                      "does not run there)", ALFD_E_UNSUPPORTED;
+  alfd_ctx::Hierarchy &H = ctx->hier[block];
+  const int slotA = block == 0 ? ALFD_A : ALFD_A2, slotCt = block == 0 ? ALFD_CT : ALFD_M;
+  if (block == 1 && !ctx->mat[slotA].present)
+    return ctx->err = "a block-1 hierarchy needs slot A2 (the elliptic-interface variants)", ALFD_E_INVALID;
+  if (ctx->configured && gd_nested(ctx))
+    return ctx->err = "alfd_build_smoothed_aggregation: grad_div_in_A = 0 has no multilevel inner preconditioner", ALFD_E_UNSUPPORTED;
+  if (!part && !ctx->mat[slotA].present) return ctx->err = "upload slot A first", ALFD_E_NOT_SETUP;
+  if (block_size < 1 || !(threshold >= 0.0) || !std::isfinite(threshold) || max_aggregate_nodes < 2 || min_coarse < 1 ||
+      !(damping > 0.0) || !std::isfinite(damping))
+    return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
+  if (!(tau >= 0.0) || !(tau < 1.0) || cap < 0) {
+    H.clear_input();
+    ctx->is_setup = false;
+    return ctx->err = "alfd_build_smoothed_aggregation_truncated: drop_tolerance must be in [0, 1), max_row_entries >= 0",
+           ALFD_E_INVALID;
+  }
+  if (!part && ctx->mat[slotA].nrows % block_size) return ctx->err = "rows of A are not a multiple of block_size", ALFD_E_INVALID;
+  if (!part && ctx->mat[slotA].nrows != ctx->mat[slotA].ncols) return ctx->err = "A is not square", ALFD_E_INVALID;
+  if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
+  const int its = ctx->configured ? ctx->cfg.cheb_power_its : 20;
+  if (its < 1) return ctx->err = "cheb_power_its must be >= 1", ALFD_E_INVALID;
+  if (part) {
+    const SaParams sp{block_size, max_aggregate_nodes, cap, max_levels, its, threshold, damping, tau, ctx->cfg.gamma,
+                      min_coarse, false};
+    bool touched = false;   // a failure after the old hierarchy went leaves none behind
+    const int rc = build_sa_partitioned(ctx, sp, levels_out, omega_out, &touched);
+    if (rc != ALFD_OK && touched) H.clear_input();
+    return rc;
+  }
+  // the penalty term: an AL variant with a diagonal W^-1, a non-zero gamma, A not already augmented, Ct and W^-1 present
+  const alfd_config &c = ctx->cfg;
+  const double gamma = block == 0 ? c.gamma : c.gamma2;
+  const bool use_pen = ctx->configured && c.variant != ALFD_RATIONAL && c.w_inverse == ALFD_W_DIAGONAL &&
+                       !c.aug_assembled && gamma != 0.0 && ctx->mat[slotCt].present && ctx->diag[ALFD_INVW] &&
+                       (block == 0 || is_elliptic(c.variant));
+  HostCsr A, C, Ct;
+  std::vector<double> w;
+  RC(download_csr(ctx, ctx->mat[slotA], A));
+  if (use_pen) {
+    RC(download_csr(ctx, ctx->mat[slotCt], Ct));
+    if (Ct.nrows != A.nrows || ctx->diag_n[ALFD_INVW] != Ct.ncols)
+      return ctx->err = "alfd_build_smoothed_aggregation: Ct / W^-1 do not match A", ALFD_E_INVALID;
+    w.resize(Ct.ncols);
+    if (!w.empty())
+      HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+    transpose_host(Ct, C);
+  }
+  H.clear_input();
+  ctx->is_setup = false;
+  int nlev = 0;
+  const SaParams sp{block_size, max_aggregate_nodes, cap, max_levels, its, threshold, damping, tau, gamma, min_coarse, use_pen};
+  RC(sa_build_levels(ctx, H, sp, A, C, Ct, w, nlev, omega_out));
   if (nlev == 0) return ctx->err = "algebraic aggregation found nothing to coarsen", ALFD_E_INVALID;
   if (levels_out) *levels_out = nlev;
   return ALFD_OK;

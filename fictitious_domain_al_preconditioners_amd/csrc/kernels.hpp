@@ -1838,6 +1838,215 @@ __global__ __launch_bounds__(64) void spgemm_rows_kernel(int64_t nrows, const in
 }
 
 // ---------------------------------------------------------------------------------------------------
+// The node graph of the algebraic aggregation (alfd_build_strength_graph) from the RESIDENT rows of A, so that a
+// row-partitioned context forms the graph rows of its own nodes without downloading A.  The rows are the local ones
+// (n_nodes * bs of them, the first is global row node0 * bs); a column c is local: owned (c < nlc, global id c0 + c)
+// or a halo column (global id halo_g[c - nlc]); on one rank nlc = ncols, c0 = 0 and halo_g is never read.
+//   sa_node_diag_kernel (one thread per node): d_I = max |a_ii| over the node's rows, fixed_I = 1 when the node's
+//   rows hold nothing but their diagonals (explicit zeros do not count) -- node_diag_host.
+//   sa_node_graph_kernel (one 64-lane workgroup per node, two passes as sa_prolongator_kernel): the neighbour nodes
+//   J != I, not fixed, with w_IJ = max |a_ij| > 0 go into an LDS hash set whose value is the running maximum (the
+//   bit pattern of a positive double orders like the double, so the maximum is an integer atomicMax); J is strong
+//   when w_IJ >= theta * sqrt(d_I d_J) with d / fixed of ALL nn nodes (all-gathered).  Pass 0 counts the strong
+//   neighbours, pass 1 sorts them ascending and writes (J, w_IJ).  max, fabs, one product, one correctly rounded
+//   sqrt and one comparison: the bits of node_graph_host.  More than kNgMaxOut distinct neighbour nodes:
+//   overflow[0] is set and the host forms the graph.  LDS: 26 KiB per workgroup.
+constexpr int kNgTable = 2048;
+constexpr int kNgMaxOut = 512;
+__global__ __launch_bounds__(256) void sa_node_diag_kernel(
+    int64_t n_nodes, int bs, int64_t node0, const int64_t *__restrict__ arp, const int32_t *__restrict__ acol,
+    const double *__restrict__ aval, int32_t nlc, int64_t c0, const int32_t *__restrict__ halo_g,
+    double *__restrict__ d, int32_t *__restrict__ fixed) {
+  const int64_t I = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (I >= n_nodes) return;
+  double dm = 0.0;
+  int32_t fx = 1;
+  for (int64_t i = I * bs; i < (I + 1) * bs; ++i) {
+    const int64_t gi = node0 * bs + i;
+    for (int64_t k = arp[i]; k < arp[i + 1]; ++k) {
+      const int32_t c = acol[k];
+      const int64_t g = c < nlc ? c0 + c : (int64_t)halo_g[c - nlc];
+      if (g == gi) dm = fmax(dm, fabs(aval[k]));
+      else if (aval[k] != 0.0) fx = 0;
+    }
+  }
+  d[I] = dm;
+  fixed[I] = fx;
+}
+
+__global__ __launch_bounds__(64) void sa_node_graph_kernel(
+    int64_t n_nodes, int64_t node0, int64_t nn, int bs, double theta, const int64_t *__restrict__ arp,
+    const int32_t *__restrict__ acol, const double *__restrict__ aval, int32_t nlc, int64_t c0,
+    const int32_t *__restrict__ halo_g, const double *__restrict__ d, const int32_t *__restrict__ fixed, int pass,
+    int32_t *__restrict__ counts, const int64_t *__restrict__ gp, int32_t *__restrict__ gc, double *__restrict__ gw,
+    int32_t *__restrict__ overflow) {
+  __shared__ int32_t table[kNgTable];
+  __shared__ unsigned long long tw[kNgTable];
+  __shared__ int32_t keys[kNgMaxOut];
+  __shared__ int32_t cnt;
+  const int lane = threadIdx.x;
+  for (int64_t Il = blockIdx.x; Il < n_nodes; Il += gridDim.x) {
+    const int64_t I = node0 + Il;
+    if (fixed[I]) {
+      if (pass == 0 && lane == 0) counts[Il] = 0;
+      continue;
+    }
+    for (int s = lane; s < kNgTable; s += 64) {
+      table[s] = -1;
+      tw[s] = 0ull;
+    }
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    const int64_t k0 = arp[Il * bs], k1 = arp[(Il + 1) * bs];   // the node's rows are consecutive
+    for (int64_t k = k0 + lane; k < k1; k += 64) {
+      const int32_t c = acol[k];
+      const int64_t g = c < nlc ? c0 + c : (int64_t)halo_g[c - nlc];
+      const int64_t Jl = g / bs;
+      if (Jl == I || Jl >= nn || fixed[Jl]) continue;
+      const double v = fabs(aval[k]);
+      if (v == 0.0) continue;
+      const int32_t J = (int32_t)Jl;
+      const unsigned long long bits = (unsigned long long)__double_as_longlong(v);
+      uint32_t h = ((uint32_t)J * 2654435761u) >> 21;   // 11 bits
+      for (;;) {
+        if (*(volatile int32_t *)&cnt > kNgMaxOut) break;   // overflowing node: stop inserting (reported below)
+        const int32_t old = atomicCAS(&table[h], -1, J);
+        if (old == -1) atomicAdd(&cnt, 1);
+        if (old == -1 || old == J) {
+          atomicMax(&tw[h], bits);
+          break;
+        }
+        h = (h + 1) & (kNgTable - 1);
+      }
+    }
+    __syncthreads();
+    const int nd = cnt;
+    __syncthreads();
+    if (nd > kNgMaxOut) {
+      if (lane == 0) overflow[0] = 1;
+      if (pass == 0 && lane == 0) counts[Il] = 0;
+      continue;
+    }
+    // the strong ones among the nd distinct neighbours
+    if (lane == 0) cnt = 0;
+    __syncthreads();
+    const double dI = d[I];
+    for (int s = lane; s < kNgTable; s += 64) {
+      const int32_t J = table[s];
+      if (J == -1) continue;
+      const double w = __longlong_as_double((long long)tw[s]);
+      if (w >= theta * sqrt(dI * d[J])) {
+        const int at = atomicAdd(&cnt, 1);
+        if (pass == 1) keys[at] = J;
+      }
+    }
+    __syncthreads();
+    const int n = cnt;
+    if (pass == 0) {
+      if (lane == 0) counts[Il] = n;
+      __syncthreads();
+      continue;
+    }
+    // pad to a power of two with INT_MAX, bitonic sort (n2 <= kNgMaxOut)
+    int n2 = 64;
+    while (n2 < n) n2 <<= 1;
+    for (int s = n + lane; s < n2; s += 64) keys[s] = 0x7fffffff;
+    __syncthreads();
+    for (int size = 2; size <= n2; size <<= 1)
+      for (int stride = size >> 1; stride > 0; stride >>= 1) {
+        for (int t = lane; t < n2 / 2; t += 64) {
+          const int lo = 2 * t - (t & (stride - 1));
+          const int hi = lo + stride;
+          const bool up = (lo & size) == 0;
+          const int32_t a = keys[lo], b = keys[hi];
+          if ((a > b) == up) {
+            keys[lo] = b;
+            keys[hi] = a;
+          }
+        }
+        __syncthreads();
+      }
+    const int64_t e0 = gp[Il];
+    for (int t = lane; t < n; t += 64) {
+      const int32_t J = keys[t];
+      uint32_t h = ((uint32_t)J * 2654435761u) >> 21;
+      while (table[h] != J) h = (h + 1) & (kNgTable - 1);   // J is in the table
+      gc[e0 + t] = J;
+      gw[e0 + t] = __longlong_as_double((long long)tw[h]);
+    }
+    __syncthreads();
+  }
+}
+
+// ---------------------------------------------------------------------------------------------------
+// The build-time kernels of alfd_build_smoothed_aggregation on a row-partitioned context.  A partitioned matrix keeps
+// every row in the order it was uploaded in (ascending GLOBAL columns) and only renames the columns to local ids
+// [owned | halo]; the chains of the builder run in global CSR order, so a view of the resident rows needs new column
+// ids and nothing else.
+//   sa_global_cols_kernel: out[k] = shift + the global id of col[k].  With shift = the number of local rows and the
+//     aggregate array laid out as [agg of the own rows | agg of all unknowns], sa_prolongator_kernel and
+//     sa_truncated_prolongator_kernel run unchanged on the view (agg[i] is the row's own id, agg[col] a column's).
+//   sa_diag_rows_kernel (one thread per row): d_i = fma(gamma, s_i, a_ii), s_i the sequential fma of (w_k c_ik) c_ik
+//     over row i of Ct (global multiplier ids; ctrp == nullptr: a_ii alone) -- the bits of sa_diag.
+//   sa_power_t_kernel (one thread per row of the REPLICATED C): t_k = w_k * (sequential fma of c_kj v_j over row k).
+//   sa_power_rows_kernel (one thread per row): y_i = (A v + gamma Ct t)_i / d_i, each product one sequential fma chain
+//     from 0.0 in CSR order -- the per-row chains of sa_spmv_host, which the 64-lane partial sums of the SpMV kernels
+//     are not.  v is the whole (replicated) vector, cols carry `shift`.
+__global__ __launch_bounds__(256) void sa_global_cols_kernel(int64_t nnz, const int32_t *__restrict__ col, int32_t nlc,
+                                                             int64_t c0, const int32_t *__restrict__ halo_g, int64_t shift,
+                                                             int32_t *__restrict__ out) {
+  const int64_t k = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (k >= nnz) return;
+  const int32_t c = col[k];
+  out[k] = (int32_t)(shift + (c < nlc ? c0 + c : (int64_t)halo_g[c - nlc]));
+}
+
+__global__ __launch_bounds__(256) void sa_diag_rows_kernel(
+    int64_t nrows, int64_t row0, int64_t shift, const int64_t *__restrict__ arp, const int32_t *__restrict__ acol,
+    const double *__restrict__ aval, const int64_t *__restrict__ ctrp, const int32_t *__restrict__ ctcol,
+    const double *__restrict__ ctval, const double *__restrict__ w, double gamma, double *__restrict__ d) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrows) return;
+  double di = 0.0;
+  for (int64_t k = arp[i]; k < arp[i + 1]; ++k)
+    if ((int64_t)acol[k] - shift == row0 + i) di = aval[k];
+  if (ctrp) {
+    double s = 0.0;
+    for (int64_t k = ctrp[i]; k < ctrp[i + 1]; ++k) s = fma(w[ctcol[k]] * ctval[k], ctval[k], s);
+    di = fma(gamma, s, di);
+  }
+  d[i] = di;
+}
+
+__global__ __launch_bounds__(256) void sa_power_t_kernel(int64_t m, const int64_t *__restrict__ crp,
+                                                         const int32_t *__restrict__ ccol, const double *__restrict__ cval,
+                                                         const double *__restrict__ w, const double *__restrict__ v,
+                                                         double *__restrict__ t) {
+  const int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (r >= m) return;
+  double s = 0.0;
+  for (int64_t k = crp[r]; k < crp[r + 1]; ++k) s = fma(cval[k], v[ccol[k]], s);
+  t[r] = w[r] * s;
+}
+
+__global__ __launch_bounds__(256) void sa_power_rows_kernel(
+    int64_t nrows, int64_t shift, const int64_t *__restrict__ arp, const int32_t *__restrict__ acol,
+    const double *__restrict__ aval, const int64_t *__restrict__ ctrp, const int32_t *__restrict__ ctcol,
+    const double *__restrict__ ctval, const double *__restrict__ t, double gamma, const double *__restrict__ v,
+    const double *__restrict__ d, double *__restrict__ y) {
+  const int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x;
+  if (i >= nrows) return;
+  double s = 0.0;
+  for (int64_t k = arp[i]; k < arp[i + 1]; ++k) s = fma(aval[k], v[(int64_t)acol[k] - shift], s);
+  if (ctrp) {
+    double u = 0.0;
+    for (int64_t k = ctrp[i]; k < ctrp[i + 1]; ++k) u = fma(ctval[k], t[ctcol[k]], u);
+    s = fma(gamma, u, s);
+  }
+  y[i] = s / d[i];
+}
+
+// ---------------------------------------------------------------------------------------------------
 // Smoothed-aggregation prolongator P = P_tent - omega D^-1 (A P_tent + pen), one 64-lane workgroup per fine row i
 // (alfd_build_smoothed_aggregation).  P_tent is never formed: (P_tent)_{j, agg[j]} = 1, so (A P_tent)_{iJ} is the sum
 // of the entries of row i of A whose column j has agg[j] == J.  pen = gamma Ct diag(w) C P_tent comes in as a CSR matrix

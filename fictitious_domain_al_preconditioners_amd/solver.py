@@ -41,6 +41,7 @@ ABI_SYMBOLS = [
     "alfd_constraint_residual",
     "alfd_set_prolongator_block", "alfd_build_smoothed_aggregation_block", "alfd_get_prolongator_block",
     "alfd_clear_hierarchy", "alfd_get_inner_iterations", "alfd_get_aggregates_block",
+    "alfd_host_strength_graph", "alfd_host_aggregate_graph", "alfd_build_strength_graph", "alfd_get_strength_graph",
 ]
 
 
@@ -145,6 +146,10 @@ def load_library():
         "alfd_clear_hierarchy": (C.c_int, [vp, C.c_int]),
         "alfd_get_aggregates_block": (C.c_int, [vp, C.c_int, C.c_int, vp, i64, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_get_inner_iterations": (C.c_int, [vp, vp]),
+        "alfd_host_strength_graph": (C.c_int, [i64, vp, vp, vp, i32, dbl, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]),
+        "alfd_host_aggregate_graph": (C.c_int, [i64, vp, vp, vp, vp, i32, i32, vp, C.POINTER(i64)]),
+        "alfd_build_strength_graph": (C.c_int, [vp, i32, dbl, C.POINTER(i64), C.POINTER(i64)]),
+        "alfd_get_strength_graph": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i32)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -287,7 +292,11 @@ class Context:
         maximum go, at most max_row_entries stay, the dropped mass is lumped per component).  Returns
         [(Csr P, n_coarse), ...] -- the list upload_problem and the oracle take; with return_omega also the damping
         omega of every level.  block = 1: the hierarchy of the immersed block, built from (A2, M, W^-1, gamma2)
-        (alfd_build_smoothed_aggregation_block); it stays in the context for the next setup."""
+        (alfd_build_smoothed_aggregation_block); it stays in the context for the next setup.
+        On a row-partitioned context (block 0) the call is collective and builds the single-rank hierarchy bit for bit:
+        the level-0 entry holds this rank's rows of P_0 (global coarse ids), the levels below are whole on every rank,
+        omega is the same on all ranks; setup() then uses the hierarchy as it stands (do not hand it back through
+        set_prolongator: caller-supplied level-0 prolongators must keep their support inside the rank's rows + halo)."""
         nlev = C.c_int32(0)
         omega = np.zeros(max(max_levels, 8), np.float64)   # ALFD_MAX_LEVELS - 1 entries when max_levels is out of range
         if block != 0:
@@ -307,6 +316,23 @@ class Context:
             P = self.prolongator(level, block)
             out.append((P, int(P.ncols)))
         return (out, omega[:nlev.value].copy()) if return_omega else out
+
+    def build_strength_graph(self, block_size=1, threshold=0.02):
+        """The node graph of the algebraic aggregation from the resident rows of slot A, on the device
+        (alfd_build_strength_graph; collective on a partitioned context, where it holds the rows of this rank's nodes
+        with global neighbour ids).  Returns the dict of solver.host_strength_graph plus on_device (False: a node
+        had too many neighbours for the kernel and every rank used the host routine)."""
+        nn, nnz, dev = C.c_int64(0), C.c_int64(0), C.c_int32(0)
+        self._ck(self._lib.alfd_build_strength_graph(self._h, int(block_size), float(threshold), C.byref(nn),
+                                                     C.byref(nnz)))
+        d = np.empty(nn.value, np.float64)
+        fixed = np.empty(nn.value, np.int32)
+        ptr = np.empty(nn.value + 1, np.int64)
+        nbr = np.empty(nnz.value, np.int32)
+        w = np.empty(nnz.value, np.float64)
+        self._ck(self._lib.alfd_get_strength_graph(self._h, d.ctypes.data, fixed.ctypes.data, ptr.ctypes.data,
+                                                   nbr.ctypes.data, w.ctypes.data, nbr.size, C.byref(dev)))
+        return dict(d=d, fixed=fixed, node_ptr=ptr, nbr=nbr, weight=w, on_device=bool(dev.value))
 
     def prolongator(self, level, block=0):
         """The CSR prolongator of a level as a problems.Csr (alfd_get_prolongator_block): built by
@@ -601,6 +627,55 @@ def host_aggregate_level(m, block_size=1, threshold=0.02, max_aggregate_nodes=8)
                                        threshold, max_aggregate_nodes, agg.ctypes.data, C.byref(nc))
     if rc != _abi.OK:
         raise AlfdError(rc, "alfd_host_aggregate_level failed")
+    return agg, int(nc.value)
+
+
+def host_strength_graph(m, block_size=1, threshold=0.02):
+    """Host-only: the node graph of one level of the algebraic aggregation on a problems.Csr
+    (alfd_host_strength_graph): dict with d, fixed (per node), node_ptr, nbr, weight (strong neighbours ascending)."""
+    lib = load_library()
+    rp = np.ascontiguousarray(m.row_ptr, np.int64)
+    col = np.ascontiguousarray(m.col, np.int32)
+    val = np.ascontiguousarray(m.val, np.float64)
+    if block_size < 1 or m.nrows % block_size:
+        raise ValueError("rows must be a multiple of block_size")
+    nn = m.nrows // block_size
+    d = np.empty(nn, np.float64)
+    fixed = np.empty(nn, np.int32)
+    ptr = np.empty(nn + 1, np.int64)
+    nnz = C.c_int64(0)
+
+    def call(nb, w, cap):
+        return lib.alfd_host_strength_graph(m.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, int(block_size),
+                                            float(threshold), d.ctypes.data, fixed.ctypes.data, ptr.ctypes.data, nb, w,
+                                            cap, C.byref(nnz))
+    rc = call(None, None, 0)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_strength_graph failed")
+    nbr = np.empty(nnz.value, np.int32)
+    w = np.empty(nnz.value, np.float64)
+    rc = call(nbr.ctypes.data, w.ctypes.data, nbr.size)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_strength_graph failed")
+    return dict(d=d, fixed=fixed, node_ptr=ptr, nbr=nbr, weight=w)
+
+
+def host_aggregate_graph(graph, block_size=1, max_aggregate_nodes=8):
+    """Host-only: the greedy passes of the algebraic aggregation on a node graph (host_strength_graph, or the rows of
+    Context.build_strength_graph gathered in rank order); (agg, n_coarse) as host_aggregate_level."""
+    lib = load_library()
+    fixed = np.ascontiguousarray(graph["fixed"], np.int32)
+    ptr = np.ascontiguousarray(graph["node_ptr"], np.int64)
+    nbr = np.ascontiguousarray(graph["nbr"], np.int32)
+    w = np.ascontiguousarray(graph["weight"], np.float64)
+    if ptr.size != fixed.size + 1 or nbr.size != w.size or nbr.size < ptr[-1]:
+        raise ValueError("inconsistent node graph")
+    agg = np.empty(fixed.size * block_size, np.int32)
+    nc = C.c_int64(0)
+    rc = lib.alfd_host_aggregate_graph(fixed.size, fixed.ctypes.data, ptr.ctypes.data, nbr.ctypes.data, w.ctypes.data,
+                                       int(block_size), int(max_aggregate_nodes), agg.ctypes.data, C.byref(nc))
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_aggregate_graph failed")
     return agg, int(nc.value)
 
 

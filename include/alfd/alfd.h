@@ -350,6 +350,36 @@ int alfd_get_aggregates(alfd_ctx_t ctx, int level, int32_t *agg, int64_t capacit
 int alfd_host_aggregate_level(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
                               int32_t block_size, double threshold, int32_t max_aggregate_nodes, int32_t *agg,
                               int64_t *n_coarse);
+/* The two halves of alfd_host_aggregate_level, host-only (no device, no context); both calls together give its bits.
+ * alfd_host_strength_graph: the node graph of one level.  Nodes are block_size consecutive rows; d[n_nodes] = max |a_ii|
+ * over the node's rows, fixed[n_nodes] = 1 when the node's rows hold nothing but their diagonals (explicit zeros do not
+ * count); node I lists, ascending, the nodes J != I that are not fixed, with weight w_IJ = max |a_ij| > 0 over the
+ * bs x bs block and w_IJ >= threshold * sqrt(d_I d_J) (fixed nodes list nothing).  Two-call sizing: with nbr and
+ * weight NULL the call returns *nnz (d, fixed, node_ptr[n_nodes + 1] may be NULL too), then capacity >= *nnz.
+ * alfd_host_aggregate_graph: the three greedy passes in natural order on such a graph; agg[n_nodes * block_size]. */
+int alfd_host_strength_graph(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                             int32_t block_size, double threshold, double *d, int32_t *fixed, int64_t *node_ptr,
+                             int32_t *nbr, double *weight, int64_t capacity, int64_t *nnz);
+int alfd_host_aggregate_graph(int64_t n_nodes, const int32_t *fixed, const int64_t *node_ptr, const int32_t *nbr,
+                              const double *weight, int32_t block_size, int32_t max_aggregate_nodes, int32_t *agg,
+                              int64_t *n_coarse);
+/* The same node graph from the RESIDENT rows of slot A, formed on the device (max, fabs, one product, one square root
+ * and one comparison per edge: the bits of alfd_host_strength_graph), on single-rank and on row-partitioned contexts.
+ * Partitioned contexts: collective, every rank calls with the same arguments; a rank forms the graph rows of its own
+ * nodes from its rows of A (halo columns included), neighbours are GLOBAL node ids, and the only traffic is one
+ * all-gather of d and of the fixed flags (12 bytes per node) plus one status word per phase -- A is not downloaded.
+ * The offsets of block 0 in alfd_set_partition must be multiples of block_size (ALFD_E_INVALID on every rank
+ * otherwise; the context stays usable).  A failure on one rank is returned by all of them: the ranks exchange a
+ * status word after every local phase, so none is left waiting in a collective.  A node with more than 512 neighbour
+ * nodes on any rank sends all ranks to the host routine on their own rows (same bits, *on_device = 0).
+ * alfd_build_strength_graph keeps the rows of this rank's nodes (*n_nodes of them, *nnz edges) until the next call;
+ * alfd_get_strength_graph copies them out: d / fixed [n_nodes], node_ptr [n_nodes + 1], nbr / weight [capacity >= nnz]
+ * (any may be NULL).  Gathering the rows of all ranks in rank order and running alfd_host_aggregate_graph on them
+ * gives the aggregates of the single-rank alfd_build_aggregates, whatever the partition: the first step of the
+ * smoothed-aggregation builders below on a partitioned context.  (alfd_build_aggregates itself stays single-rank.) */
+int alfd_build_strength_graph(alfd_ctx_t ctx, int32_t block_size, double threshold, int64_t *n_nodes, int64_t *nnz);
+int alfd_get_strength_graph(alfd_ctx_t ctx, double *d, int32_t *fixed, int64_t *node_ptr, int32_t *nbr, double *weight,
+                            int64_t capacity, int32_t *on_device);
 /* Smoothed aggregation (the algorithm of ML in the reference, utilities.h:304-317) from the uploaded operators alone.
  * Per level l, from A_0 = A (slot A) and C_0 = Ct^T (slot CT):
  *   agg_l   = the aggregation of alfd_build_aggregates on A_l (block_size, threshold, max_aggregate_nodes);
@@ -365,8 +395,29 @@ int alfd_host_aggregate_level(int64_t nrows, const int64_t *row_ptr, const int32
  * would store them (alfd_setup forms the Galerkin products again), the aggregates as alfd_set_aggregates
  * (alfd_get_aggregates returns them); earlier aggregates / prolongators are cleared.  omega_out (may be NULL) receives
  * omega_l for every built level (room for max_levels entries, ALFD_MAX_LEVELS - 1 when max_levels is out of range).
- * Deterministic, bit for bit.  Single rank: ALFD_E_UNSUPPORTED on a partitioned context, ALFD_E_NOT_SETUP without
- * slot A, ALFD_E_INVALID on bad arguments (damping <= 0 or not finite, ...).  Canonical order: DESIGN.md section 4. */
+ * Deterministic, bit for bit.  ALFD_E_NOT_SETUP without slot A, ALFD_E_INVALID on bad arguments (damping <= 0 or not
+ * finite, ...).  Canonical order: DESIGN.md section 4.
+ * Row-partitioned contexts (alfd_comm_init*, alfd_set_partition; block 0): the call is COLLECTIVE -- every rank calls it
+ * with the same arguments -- and builds the single-rank hierarchy of the same global operators bit for bit, whatever
+ * the partition: aggregates, omega_l and every P_l.  Slot A holds this rank's rows (slots C / CT and W^-1 its rows of
+ * C, Ct and W^-1 when the penalty term applies: on every rank or on none).
+ *   partitioned: level 0.  alfd_get_prolongator(0) returns this rank's rows of P_0 with GLOBAL coarse ids,
+ *     alfd_get_aggregates(0) this rank's slice; aggregates may hold nodes of several ranks.
+ *   replicated: levels >= 1, stored whole on every rank; omega_out is the same on all ranks.
+ *   chosen by the library: the coarse offsets of alfd_set_aggregate_partition(0, ...), the rank that forms each row of
+ *     A_1: (n_coarse / block_size) * p / nranks * block_size for rank p.  Any contiguous split gives the same bits.
+ *   over the wire per build: d and the fixed flags of the nodes and the rows of the node graph (alfd_build_strength_graph),
+ *     the rows of C and W^-1, cheb_power_its all-gathers of one velocity vector (the norms of the power iteration are
+ *     the one sequential sum over the whole vector on every rank), the remote rows of P_0 and A P_0 in the support of a
+ *     rank's coarse unknowns, the rows of A_1 and C_1, and one status word after every rank-local phase.  A is not
+ *     downloaded.  Levels >= 1 are built redundantly on every rank.
+ * alfd_setup then runs the replicated path of alfd_set_prolongator (interface patch included); for a hierarchy built
+ * here it fetches the whole fine support of a rank's coarse unknowns, so the halo condition of caller-supplied
+ * prolongators does not apply (it still does once alfd_set_prolongator / alfd_set_aggregates replace a level).
+ * A rank group without alfd_set_partition has no rows to build from: ALFD_E_UNSUPPORTED, as before.
+ * The offsets of block 0 must be multiples of block_size: ALFD_E_INVALID on every rank otherwise.  A failure on one
+ * rank is returned by all of them, and a row with more than 512 candidates on any rank sends all ranks to the host
+ * routines (same bits).  The context stays usable after an error. */
 int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
                                     double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
                                     double *omega_out);
@@ -402,7 +453,8 @@ int alfd_get_prolongator(alfd_ctx_t ctx, int level, int64_t *row_ptr, int32_t *c
  * builder runs the smoothed aggregation above on (A2, M, invW, gamma2), so the immersed hierarchy needs no geometry
  * either (amg_prec_A22.initialize(matrix), elliptic_interface.cc:841-851); drop_tolerance = 0 and max_row_entries = 0
  * truncate nothing.  Block 1 takes CSR prolongators only (there is no alfd_set_aggregates for it), has no interface patch (M touches
- * every row) and is single-rank: ALFD_E_UNSUPPORTED on a partitioned context, ALFD_E_INVALID for another block, for
+ * every row) and is single-rank: ALFD_E_UNSUPPORTED on a partitioned context (block 0 of the builder is collective there,
+ * see alfd_build_smoothed_aggregation), ALFD_E_INVALID for another block, for
  * the builder without slot A2, and at alfd_setup for a block-1 hierarchy on a variant without A2 or with sizes that
  * do not match.  alfd_clear_hierarchy forgets what was set or built for a block (the next alfd_setup runs without). */
 int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_fine, int64_t n_coarse,
