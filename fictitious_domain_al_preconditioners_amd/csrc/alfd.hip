@@ -150,23 +150,30 @@ struct HostCsr {
 
 constexpr int kScratchSlot = ALFD_NSLOTS;  // internal upload target (level matrices, batched systems)
 
-// One level of the aggregation multigrid hierarchy (level 0 = the augmented block itself).
-struct MlLevel {
+// The operators and vectors of one multigrid level in ONE index space.  P / R connect the record to the record of the
+// next finer level that the V-cycle pairs it with: loc to loc, rep to rep, and the loc pair of the first replicated level
+// to the finer level's loc (MlLevel).
+struct LevelStore {
   DevCsr A, C, Ct;   // operator pieces of this level (levels >= 1; level 0 uses the slots)
-  DevCsr P, R;       // prolongation to this level from the next coarser one, and R = P^T
+  DevCsr P, R;       // prolongation from this level to the next finer one, and R = P^T
   int64_t n = 0, npad = 0;
-  double *dinv = nullptr;
+  double *dinv = nullptr, *r = nullptr, *z = nullptr, *t = nullptr, *cd = nullptr, *cres = nullptr, *ctmp = nullptr;
+};
+
+// One level of the aggregation multigrid hierarchy (level 0 = the augmented block itself).  loc holds this rank's rows.
+// Multi-rank: levels from alfd_ctx::ml_rep_level on are REPLICATED on every rank (global operators and vectors, no halo
+// exchanges) and run on rep, the whole level; rep.P / rep.R connect two replicated levels, loc.P / loc.R above stay
+// rank-local.  A replicated level of the aggregate path keeps loc as well: its dinv and the restricted residual are
+// gathered from there.
+struct MlLevel {
+  LevelStore loc, rep;
   double lmax = 0;
-  double *r = nullptr, *z = nullptr, *t = nullptr, *cd = nullptr, *cres = nullptr, *ctmp = nullptr;
-  uint8_t *tail_mask = nullptr;   // npad bytes, 1 = row listed in Ct (aug_tail_kernel); null: this level runs unfused
-  // multi-rank: levels from alfd_ctx::ml_rep_level on are REPLICATED on every rank (global operators and
-  // vectors, no halo exchanges); gP / gR connect two replicated levels, P / R above stay rank-local
-  DevCsr gA, gC, gCt, gP, gR;
-  bool P_global_cols = false;   // P of this level addresses the replicated coarse vector by GLOBAL ids (CSR prolongators)
-  int64_t gn = 0, gnpad = 0, g_maxpiece = 0;
-  std::vector<int64_t> g_offs;  // rank offsets of this level's unknowns (size nranks + 1)
-  double *gdinv = nullptr, *gr = nullptr, *gz = nullptr, *gt = nullptr, *gcd = nullptr, *gcres = nullptr,
-         *gctmp = nullptr, *g_send = nullptr, *g_stage = nullptr;
+  uint8_t *tail_mask = nullptr;   // loc.npad bytes, 1 = row listed in Ct (aug_tail_kernel); null: this level runs unfused
+  bool P_global_cols = false;     // loc.P addresses the replicated coarse vector by GLOBAL ids (CSR prolongators)
+  // the all-gather of the restricted residual from loc.r into rep.r (first replicated level)
+  std::vector<int64_t> offs;      // rank offsets of this level's unknowns (size nranks + 1)
+  int64_t maxpiece = 0;
+  double *send = nullptr, *stage = nullptr;
 };
 
 enum State { ITERATE = 0, SUCCESS = 1, FAILURE = 2 };
@@ -3544,7 +3551,8 @@ static int power_iteration(alfd_ctx *ctx, int op) {
 static void free_levels(alfd_ctx *ctx) {
   for (alfd_ctx::Hierarchy &H : ctx->hier) {
     for (MlLevel &L : H.ml)
-      for (DevCsr *m : {&L.A, &L.C, &L.Ct, &L.P, &L.R, &L.gA, &L.gC, &L.gCt, &L.gP, &L.gR}) csr_free(*m);
+      for (LevelStore *S : {&L.loc, &L.rep})
+        for (DevCsr *m : {&S->A, &S->C, &S->Ct, &S->P, &S->R}) csr_free(*m);
     H.ml.clear();
     H.tail_tab = nullptr;   // setup workspace
     csr_free(H.inv);
@@ -3594,8 +3602,24 @@ static int ensure_window_plans(alfd_ctx *ctx) {
   for (DevCsr &m : ctx->mat) RC(ensure_window_plan(ctx, m));
   for (alfd_ctx::Hierarchy &H : ctx->hier)
     for (MlLevel &L : H.ml)
-      for (DevCsr *m : {&L.A, &L.gA}) RC(ensure_window_plan(ctx, *m));
+      for (LevelStore *S : {&L.loc, &L.rep}) RC(ensure_window_plan(ctx, S->A));
   return ALFD_OK;
+}
+
+// GLOBAL ids of the local column space [owned | halo] of an uploaded matrix; c0 = global id of its first owned column
+static std::vector<int32_t> global_cols(const DevCsr &m, int64_t c0) {
+  std::vector<int32_t> ids((size_t)m.n_local_cols + m.halo_globals.size());
+  for (int32_t j = 0; j < m.n_local_cols; ++j) ids[j] = (int32_t)(c0 + j);
+  std::copy(m.halo_globals.begin(), m.halo_globals.end(), ids.begin() + m.n_local_cols);
+  return ids;
+}
+
+// the rows of b below those of a
+static void append_rows(HostCsr &a, const HostCsr &b) {
+  a.nrows += b.nrows;
+  for (int64_t i = 0; i < b.nrows; ++i) a.rp.push_back(a.rp.back() + (b.rp[i + 1] - b.rp[i]));
+  a.col.insert(a.col.end(), b.col.begin(), b.col.end());
+  a.val.insert(a.val.end(), b.val.begin(), b.val.end());
 }
 
 static void transpose_host(const HostCsr &a, HostCsr &t) {
@@ -3730,26 +3754,28 @@ struct LevelView {
 // keeps the rank-local pair: ml_cycle gathers the restricted residual there.
 static LevelView level_view(alfd_ctx *ctx, int h, int l) {
   MlLevel &L = ctx->hier[h].ml[l];
-  const bool rep = h == 0 && ctx->ml_rep_level >= 0 && l >= ctx->ml_rep_level;
+  const bool rep = h == 0 && ctx->ml_rep_level >= 0 && l >= ctx->ml_rep_level;   // never level 0
+  LevelStore &S = rep ? L.rep : L.loc;
   LevelView V;
   AugOp &F = V.op;
-  F.A = rep ? &L.gA : l > 0 ? &L.A : &ctx->mat[h == 0 ? ALFD_A : ALFD_A2];
-  F.C = rep ? &L.gC : l > 0 ? &L.C : &ctx->mat[h == 0 ? ALFD_C : ALFD_M];
-  F.Ct = rep ? &L.gCt : l > 0 ? &L.Ct : &ctx->mat[h == 0 ? ALFD_CT : ALFD_M];
+  F.A = l > 0 ? &S.A : &ctx->mat[h == 0 ? ALFD_A : ALFD_A2];
+  F.C = l > 0 ? &S.C : &ctx->mat[h == 0 ? ALFD_C : ALFD_M];
+  F.Ct = l > 0 ? &S.Ct : &ctx->mat[h == 0 ? ALFD_CT : ALFD_M];
   F.clsA = l == 0 && h == 0 ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
   F.w = rep ? ctx->g_w : ctx->diag[ALFD_INVW];
   F.gamma = h == 0 ? ctx->cfg.gamma : ctx->cfg.gamma2;
   F.tlam = rep ? ctx->g_tlam : ctx->t_lam;
   F.mask = L.tail_mask;
-  F.npad = rep ? L.gnpad : L.npad;
-  F.dinv = rep ? L.gdinv : L.dinv;
-  F.cd = rep ? L.gcd : L.cd, F.cres = rep ? L.gcres : L.cres, F.ctmp = rep ? L.gctmp : L.ctmp;
+  F.npad = S.npad;
+  F.dinv = S.dinv;
+  F.cd = S.cd, F.cres = S.cres, F.ctmp = S.ctmp;
   F.lmax = L.lmax;
-  V.r = rep ? L.gr : L.r, V.z = rep ? L.gz : L.z, V.t = rep ? L.gt : L.t;
+  V.r = S.r, V.z = S.z, V.t = S.t;
   if (l + 1 < (int)ctx->hier[h].ml.size()) {
-    MlLevel &N = ctx->hier[h].ml[l + 1];
-    V.R = rep ? &N.gR : &N.R, V.P = rep ? &N.gP : &N.P;
-    V.rc = rep ? N.gr : N.r, V.zc = rep ? N.gz : N.z;
+    MlLevel &M = ctx->hier[h].ml[l + 1];
+    LevelStore &N = rep ? M.rep : M.loc;
+    V.R = &N.R, V.P = &N.P;
+    V.rc = N.r, V.zc = N.z;
   }
   return V;
 }
@@ -3781,6 +3807,19 @@ static int aug_apply(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) 
   if (ctx->cfg.aug_assembled) return spmv_m(ctx, *F.A, F.clsA, x, y, 0);   // operator form: A already holds the AL term
   RC(fused_AC(ctx, F, x, y));
   return spmv_m(ctx, *F.Ct, ALFD_T_SPMV_OTHER, F.tlam, y, 1, F.gamma);
+}
+
+// *lmax = cheb_safety * lambda_max(D^-1 Aug) of the factored operator F (its dinv, its npad) by power iteration from the
+// integer-hash vector: entry i < n from global index goff + i.  v and wv, npad zeros on entry, are zero again on return.
+static int aug_lambda_max(alfd_ctx *ctx, const AugOp &F, int64_t n, int64_t goff, double *v, double *wv, double *lmax) {
+  if (n > 0)
+    hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, goff, v);
+  double lam = 0;
+  RC(power_lambda(ctx, F.npad, F.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
+  *lmax = lam * ctx->cfg.cheb_safety;
+  HIPC(hipMemsetAsync(v, 0, F.npad * sizeof(double), ctx->stream));
+  HIPC(hipMemsetAsync(wv, 0, F.npad * sizeof(double), ctx->stream));
+  return ALFD_OK;
 }
 
 // ---- fused smoother steps ("ml_fuse").  One application of a factored operator inside a Chebyshev
@@ -3947,17 +3986,31 @@ static bool tail_ok(alfd_ctx *ctx, int l, const double *r, const double *z) {
   const alfd_config &c = ctx->cfg;
   alfd_ctx::Hierarchy &H = ctx->hier[1];
   const int last = (int)H.ml.size() - 1;
-  if (!H.tail_tab || l < 1 || H.ml[l].n > ctx->ml_tail_rows || r != H.ml[l].r || z != H.ml[l].z) return false;
+  if (!H.tail_tab || l < 1 || H.ml[l].loc.n > ctx->ml_tail_rows || r != H.ml[l].loc.r || z != H.ml[l].loc.z) return false;
   if (ctx->nranks != 1 || c.aug_assembled || c.w_inverse != ALFD_W_DIAGONAL) return false;
   const int sdeg = c.ml_smooth_degree_coarse > 0 ? c.ml_smooth_degree_coarse : c.ml_smooth_degree;
   if (sdeg - 1 > kTailMaxDegree || (!H.inv.present && c.ml_coarse_degree - 1 > kTailMaxDegree)) return false;
   if (H.inv.present && !tail_form(H.inv)) return false;
   for (int j = l; j <= last; ++j) {
-    const MlLevel &L = H.ml[j];
+    const LevelStore &L = H.ml[j].loc;
     if (!tail_form(L.A) || !tail_form(L.C) || !tail_form(L.Ct)) return false;
     if (j > l && (!tail_form(L.R) || !tail_form(L.P))) return false;
   }
   return true;
+}
+
+// device vector pieces (offs[p+1] - offs[p] doubles on rank p) -> the whole vector on every rank
+static int allgather_pieces(alfd_ctx *ctx, const double *mine, const std::vector<int64_t> &offs, int64_t piece, double *send,
+                            double *stage, double *whole) {
+  const int64_t n_me = offs[ctx->rank + 1] - offs[ctx->rank];
+  if (n_me > 0) HIPC(hipMemcpyAsync(send, mine, n_me * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  RC(comm_allgather(ctx, send, stage, (size_t)piece * sizeof(double)));
+  for (int p = 0; p < ctx->nranks; ++p) {
+    const int64_t np = offs[p + 1] - offs[p];
+    if (np > 0)
+      HIPC(hipMemcpyAsync(whole + offs[p], stage + (int64_t)p * piece, np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
+  }
+  return ALFD_OK;
 }
 
 // z = V-cycle(r) on level l of hierarchy h
@@ -3991,17 +4044,10 @@ static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
   if (h == 0 && l + 1 == ctx->ml_rep_level) {
     // the restricted residual is gathered once; everything below runs replicated, without exchanges
     MlLevel &N = H.ml[l + 1];
-    HIPC(hipMemcpyAsync(N.g_send, N.r, N.n * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-    RC(comm_allgather(ctx, N.g_send, N.g_stage, (size_t)N.g_maxpiece * sizeof(double)));
-    for (int p = 0; p < ctx->nranks; ++p) {
-      const int64_t np = N.g_offs[p + 1] - N.g_offs[p];
-      if (np > 0)
-        HIPC(hipMemcpyAsync(N.gr + N.g_offs[p], N.g_stage + (int64_t)p * N.g_maxpiece, np * sizeof(double),
-                            hipMemcpyDeviceToDevice, ctx->stream));
-    }
-    RC(ml_cycle(ctx, h, l + 1, N.gr, N.gz));
+    RC(allgather_pieces(ctx, N.loc.r, N.offs, N.maxpiece, N.send, N.stage, N.rep.r));
+    RC(ml_cycle(ctx, h, l + 1, N.rep.r, N.rep.z));
     // z += P e_c: aggregates -> my slice of e_c; CSR prolongators address the replicated vector by global ids
-    RC(spmv_m(ctx, N.P, ALFD_T_SPMV_OTHER, N.P_global_cols ? N.gz : N.gz + N.g_offs[ctx->rank], z, 1, 1.0));
+    RC(spmv_m(ctx, N.loc.P, ALFD_T_SPMV_OTHER, N.P_global_cols ? N.rep.z : N.rep.z + N.offs[ctx->rank], z, 1, 1.0));
   } else {
     RC(ml_cycle(ctx, h, l + 1, L.rc, L.zc));
     RC(spmv_m(ctx, *L.P, ALFD_T_SPMV_OTHER, L.zc, z, 1, 1.0));               // z += P e_c
@@ -4021,20 +4067,6 @@ static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
 
 // The multilevel inner preconditioner: the V-cycle, wrapped (ml_patch_degree > 0) into two corrections on the
 // interface patch:  z1 = E q E^T r;  z2 = z1 + V(r - Aug z1);  z = z2 + E q E^T (r - Aug z2)  -- symmetric.
-// device vector pieces (offs[p+1] - offs[p] doubles on rank p) -> the whole vector on every rank
-static int allgather_pieces(alfd_ctx *ctx, const double *mine, const std::vector<int64_t> &offs, int64_t piece, double *send,
-                            double *stage, double *whole) {
-  const int64_t n_me = offs[ctx->rank + 1] - offs[ctx->rank];
-  if (n_me > 0) HIPC(hipMemcpyAsync(send, mine, n_me * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  RC(comm_allgather(ctx, send, stage, (size_t)piece * sizeof(double)));
-  for (int p = 0; p < ctx->nranks; ++p) {
-    const int64_t np = offs[p + 1] - offs[p];
-    if (np > 0)
-      HIPC(hipMemcpyAsync(whole + offs[p], stage + (int64_t)p * piece, np * sizeof(double), hipMemcpyDeviceToDevice, ctx->stream));
-  }
-  return ALFD_OK;
-}
-
 // ml_apply on a partitioned context: same arithmetic, the patch polynomial runs redundantly on every rank
 static int ml_apply_rep(alfd_ctx *ctx, const double *r, double *z) {
   alfd_ctx::Patch &Q = ctx->patch;
@@ -4374,14 +4406,7 @@ static int patch_setup(alfd_ctx *ctx, const HostCsr *A_full, const HostCsr &C, c
   const unsigned gm = (unsigned)((m + 255) / 256);
   hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, m, Q.S, ctx->dinv_aug, Q.dinv);
   // lambda_max(D^-1 Aug_SS): power iteration from the integer-hash vector (patch-compact index)
-  double *v = Q.rS, *wv = Q.zS;
-  hipLaunchKernelGGL(hash_vector_kernel, dim3(gm), dim3(256), 0, ctx->stream, m, (int64_t)0, v);
-  double lam = 0;
-  const AugOp F = patch_aug(ctx);
-  RC(power_lambda(ctx, Q.mpad, Q.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
-  Q.lmax = lam * c.cheb_safety;
-  HIPC(hipMemsetAsync(Q.rS, 0, Q.mpad * sizeof(double), ctx->stream));
-  HIPC(hipMemsetAsync(Q.zS, 0, Q.mpad * sizeof(double), ctx->stream));
+  RC(aug_lambda_max(ctx, patch_aug(ctx), m, 0, Q.rS, Q.zS, &Q.lmax));
   RC(build_tail_mask(ctx, Q.Cts, Q.mpad, &Q.tail_mask));
   HIPC(hipStreamSynchronize(ctx->stream));
   Q.on = true;
@@ -5629,7 +5654,6 @@ static int sa_prolongator_dev(alfd_ctx *ctx, const HostCsr &A, const std::vector
 // every rank (they are small), the polynomial runs redundantly; see ml_apply_rep.
 static int patch_setup_rep(alfd_ctx *ctx) {
   alfd_ctx::Patch &Q = ctx->patch;
-  const alfd_config &c = ctx->cfg;
   const int P = ctx->nranks, rk = ctx->rank, last = ctx->nblocks - 1;
   const std::vector<int64_t> &off0 = ctx->part[0], &offl = ctx->part[last];
   DevCsr &dA = ctx->mat[ALFD_A], &dC = ctx->mat[ALFD_C], &dCt = ctx->mat[ALFD_CT];
@@ -5677,9 +5701,7 @@ static int patch_setup_rep(alfd_ctx *ctx) {
   RC(gather_csr(ctx, h, nullptr, m, g));
   RC(upload_level_part(ctx, Q.Cs, g, nullptr, true));
   // Ct rows over GLOBAL multiplier ids
-  std::vector<int32_t> lamg((size_t)dCt.n_local_cols + dCt.halo_globals.size());
-  for (int32_t j = 0; j < dCt.n_local_cols; ++j) lamg[j] = (int32_t)(offl[rk] + j);
-  for (size_t j = 0; j < dCt.halo_globals.size(); ++j) lamg[dCt.n_local_cols + j] = dCt.halo_globals[j];
+  const std::vector<int32_t> lamg = global_cols(dCt, offl[rk]);
   HostCsr Ctg = Ct;
   Ctg.ncols = offl.back();
   for (int64_t i = 0; i < Ctg.nrows; ++i) {   // rows re-sorted by the global id (the local order puts halo ids last)
@@ -5698,8 +5720,8 @@ static int patch_setup_rep(alfd_ctx *ctx) {
   extract_host(A_patch, Trows, posA.data(), m, true, h);
   RC(upload_level_part(ctx, Q.Ats, h, nullptr, true));
   extract_host(A_patch, S, nullptr, A_patch.ncols, false, h);
-  for (size_t k = 0; k < h.col.size(); ++k)
-    h.col[k] = (int32_t)(h.col[k] < dA.n_local_cols ? off0[rk] + h.col[k] : dA.halo_globals[h.col[k] - dA.n_local_cols]);
+  const std::vector<int32_t> fineg = global_cols(dA, off0[rk]);
+  for (int32_t &col : h.col) col = fineg[col];
   h.ncols = off0.back();
   RC(upload_level_part(ctx, Q.As, h, off0.data(), false));
   Q.m = m;
@@ -5727,17 +5749,10 @@ static int patch_setup_rep(alfd_ctx *ctx) {
   if (Q.m_loc) hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m_loc, Q.S, ctx->dinv_aug, Q.loc);
   RC(allgather_pieces(ctx, Q.loc, Q.soff, Q.piece, Q.send, Q.stage, Q.dinv));
   // lambda_max(D^-1 Aug_SS) on the replicated patch: plain reductions, the same on every rank
-  double *v = Q.rS, *wv = Q.zS;
-  hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((m + 255) / 256)), dim3(256), 0, ctx->stream, m, (int64_t)0, v);
-  double lam = 0;
   {
     ReplicatedDots rd(ctx);
-    const AugOp F = patch_aug(ctx);
-    RC(power_lambda(ctx, Q.mpad, Q.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
+    RC(aug_lambda_max(ctx, patch_aug(ctx), m, 0, Q.rS, Q.zS, &Q.lmax));
   }
-  Q.lmax = lam * c.cheb_safety;
-  HIPC(hipMemsetAsync(Q.rS, 0, Q.mpad * sizeof(double), ctx->stream));
-  HIPC(hipMemsetAsync(Q.zS, 0, Q.mpad * sizeof(double), ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   Q.on = true;
   return ALFD_OK;
@@ -5791,10 +5806,7 @@ static int rep_level0_products(alfd_ctx *ctx, const HostCsr &P0, const std::vect
     HostCsr halo;
     RC(fetch_rows(ctx, P0, off0.data(), want, halo));
     Pperm = P0;
-    Pperm.nrows = P0.nrows + halo.nrows;
-    for (int64_t i = 0; i < halo.nrows; ++i) Pperm.rp.push_back(Pperm.rp.back() + (halo.rp[i + 1] - halo.rp[i]));
-    Pperm.col.insert(Pperm.col.end(), halo.col.begin(), halo.col.end());
-    Pperm.val.insert(Pperm.val.end(), halo.val.begin(), halo.val.end());
+    append_rows(Pperm, halo);
     colg.resize(Pperm.nrows);
     for (int64_t q = 0; q < P0.nrows; ++q) colg[q] = off0[rk] + q;
     for (size_t q = 0; q < want.size(); ++q) colg[P0.nrows + q] = want[q];
@@ -5846,10 +5858,7 @@ static int rep_level0_products(alfd_ctx *ctx, const HostCsr &P0, const std::vect
       for (int64_t k = cnt[I]; k < cnt[I + 1]; ++k) Rl.col[k] = ent[k].second.first, Rl.val[k] = ent[k].second.second;
     }
     APp = AP_loc;
-    APp.nrows = AP_loc.nrows + AP_halo.nrows;
-    for (int64_t i = 0; i < AP_halo.nrows; ++i) APp.rp.push_back(APp.rp.back() + (AP_halo.rp[i + 1] - AP_halo.rp[i]));
-    APp.col.insert(APp.col.end(), AP_halo.col.begin(), AP_halo.col.end());
-    APp.val.insert(APp.val.end(), AP_halo.val.begin(), AP_halo.val.end());
+    append_rows(APp, AP_halo);
   }
   {
     // every prolongator entry must have been seen by the rank that forms its coarse row: the fine rows in the support
@@ -5889,6 +5898,40 @@ static int rep_level0_products(alfd_ctx *ctx, const HostCsr &P0, const std::vect
   return ALFD_OK;
 }
 
+// The zeroed work vectors of a record, npad entries each (the caller has set n and npad): r and z, which the transfers
+// read and write; with `sweep` also those of a Chebyshev sweep and a residual on the level.  dinv is the caller's.
+static int store_vectors(alfd_ctx *ctx, LevelStore &S, bool sweep) {
+  for (double **v : {&S.r, &S.z}) RC(ws_alloc_zero(ctx, v, S.npad));
+  if (sweep)
+    for (double **v : {&S.t, &S.cd, &S.cres, &S.ctmp}) RC(ws_alloc_zero(ctx, v, S.npad));
+  return ALFD_OK;
+}
+
+// Level l of hierarchy 0 becomes a REPLICATED level: A, C, Ct (whole) on every rank and the vectors of the record, dinv
+// zero.  offs = the ranks' ranges of the level's unknowns; `first`: the level the restricted residual is gathered into,
+// which holds the buffers of that all-gather.  The caller fills dinv and uploads the transfer pair rep.P / rep.R.
+static int replicate_level(alfd_ctx *ctx, int l, const HostCsr &A, const HostCsr &C, const HostCsr &Ct,
+                           const std::vector<int64_t> &offs, bool first) {
+  MlLevel &L = ctx->hier[0].ml[l];
+  LevelStore &S = L.rep;
+  L.offs = offs;
+  S.n = A.nrows;
+  S.npad = pad_chunk(S.n);
+  RC(upload_level_part(ctx, S.A, A, nullptr, true));
+  RC(upload_level_part(ctx, S.C, C, nullptr, true));
+  RC(upload_level_part(ctx, S.Ct, Ct, nullptr, true));
+  S.A.rep = S.C.rep = S.Ct.rep = true;
+  RC(ws_alloc_zero(ctx, &S.dinv, S.npad));
+  RC(store_vectors(ctx, S, true));
+  if (first) {
+    for (int p = 0; p < ctx->nranks; ++p) L.maxpiece = std::max(L.maxpiece, offs[p + 1] - offs[p]);
+    L.maxpiece = std::max<int64_t>(L.maxpiece, 1);
+    RC(ws_alloc_zero(ctx, &L.send, L.maxpiece));
+    RC(ws_alloc_zero(ctx, &L.stage, L.maxpiece * ctx->nranks));
+  }
+  return ALFD_OK;
+}
+
 // ALFD_PREC_MULTILEVEL through CSR prolongators on a ROW-PARTITIONED context (round 3): the fine level stays
 // partitioned, every level below it -- and the interface patch -- is REPLICATED on all ranks.  Level 0: this rank holds
 // the prolongator rows of its own fine unknowns (global coarse ids) and alfd_set_aggregate_partition(0, ...) names the
@@ -5916,10 +5959,10 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
   // ---- level 0 (partitioned): vectors only, operators are the slots
   {
     MlLevel &L = ctx->hier[0].ml[0];
-    L.n = n_loc;
-    L.npad = pad_chunk(n_loc);
-    for (double **v : {&L.r, &L.z, &L.t, &L.cd, &L.cres, &L.ctmp}) RC(ws_alloc_zero(ctx, v, L.npad));
-    L.dinv = ctx->dinv_aug;
+    L.loc.n = n_loc;
+    L.loc.npad = pad_chunk(n_loc);
+    RC(store_vectors(ctx, L.loc, true));
+    L.loc.dinv = ctx->dinv_aug;
     L.lmax = ctx->lam_max[OP_AUG];
   }
   HostCsr A1, C1, Ct1;
@@ -5932,8 +5975,8 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
     // the fine vector), P rows of the owned fine unknowns addressing the replicated coarse vector
     MlLevel &N = ctx->hier[0].ml[1];
     PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
-    RC(upload_level_part(ctx, N.R, Rg, off0.data(), false));
-    RC(upload_level_part(ctx, N.P, P0, nullptr, true));
+    RC(upload_level_part(ctx, N.loc.R, Rg, off0.data(), false));
+    RC(upload_level_part(ctx, N.loc.P, P0, nullptr, true));
     N.P_global_cols = true;
   }
   // ---- replicated levels 1 .. nlev
@@ -5945,45 +5988,26 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
   HostCsr A = std::move(A1), C = std::move(C1), Ct = std::move(Ct1), An, Cn, Ctn, R;
   for (int l = 1; l <= nlev; ++l) {
     MlLevel &L = ctx->hier[0].ml[l];
-    L.gn = A.nrows;
-    L.gnpad = pad_chunk(L.gn);
-    L.g_offs.assign(P + 1, 0);
-    if (l == 1) L.g_offs = coff;
-    else for (int p = 0; p <= P; ++p) L.g_offs[p] = L.gn * p / P;      // no partitioned piece below level 1
-    L.n = l == 1 ? coff[rk + 1] - coff[rk] : 0;
-    L.npad = pad_chunk(std::max<int64_t>(L.n, 1));
-    for (double **v : {&L.r, &L.z}) RC(ws_alloc_zero(ctx, v, L.npad));
+    std::vector<int64_t> offs(P + 1, 0);
+    if (l == 1) offs = coff;
+    else for (int p = 0; p <= P; ++p) offs[p] = A.nrows * p / P;      // no partitioned piece below level 1
+    L.loc.n = l == 1 ? coff[rk + 1] - coff[rk] : 0;
+    L.loc.npad = pad_chunk(std::max<int64_t>(L.loc.n, 1));
+    RC(store_vectors(ctx, L.loc, false));
     {
       PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
-      RC(upload_level_part(ctx, L.gA, A, nullptr, true));
-      RC(upload_level_part(ctx, L.gC, C, nullptr, true));
-      RC(upload_level_part(ctx, L.gCt, Ct, nullptr, true));
-      L.gA.rep = L.gC.rep = L.gCt.rep = true;
+      RC(replicate_level(ctx, l, A, C, Ct, offs, l == 1));
     }
-    for (double **v : {&L.gdinv, &L.gr, &L.gz, &L.gt, &L.gcd, &L.gcres, &L.gctmp}) RC(ws_alloc_zero(ctx, v, L.gnpad));
     {
       // diagonal and lambda_max on the replicated operator: plain (single-rank) reductions, the same on every rank
       PhaseClock pl(ctx, ALFD_SETUP_ML_LAMBDA);
       ReplicatedDots rd(ctx);
       double *w_save = ctx->diag[ALFD_INVW];
       ctx->diag[ALFD_INVW] = ctx->g_w;        // diag_plus_m reads the weight through the slot
-      const int rc = diag_plus_m(ctx, L.gA, L.gCt, c.aug_assembled ? 0.0 : c.gamma, L.gn, L.gdinv);
+      const int rc = diag_plus_m(ctx, L.rep.A, L.rep.Ct, c.aug_assembled ? 0.0 : c.gamma, L.rep.n, L.rep.dinv);
       ctx->diag[ALFD_INVW] = w_save;
       if (rc != ALFD_OK) return rc;
-      double *v = L.gt, *wv = L.gr;
-      hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((L.gn + 255) / 256)), dim3(256), 0, ctx->stream, L.gn, (int64_t)0, v);
-      double lam = 0;
-      const AugOp F = level_view(ctx, 0, l).op;
-      RC(power_lambda(ctx, L.gnpad, L.gdinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
-      L.lmax = lam * c.cheb_safety;
-      HIPC(hipMemsetAsync(L.gt, 0, L.gnpad * sizeof(double), ctx->stream));
-      HIPC(hipMemsetAsync(L.gr, 0, L.gnpad * sizeof(double), ctx->stream));
-    }
-    if (l == 1) {
-      for (int p = 0; p < P; ++p) L.g_maxpiece = std::max(L.g_maxpiece, coff[p + 1] - coff[p]);
-      L.g_maxpiece = std::max<int64_t>(L.g_maxpiece, 1);
-      RC(ws_alloc_zero(ctx, &L.g_send, L.g_maxpiece));
-      RC(ws_alloc_zero(ctx, &L.g_stage, L.g_maxpiece * P));
+      RC(aug_lambda_max(ctx, level_view(ctx, 0, l).op, L.rep.n, 0, L.rep.t, L.rep.r, &L.lmax));
     }
     if (l == nlev) break;
     const HostCsr &Pm = ctx->hier[0].P[l];
@@ -5998,14 +6022,14 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
     }
     MlLevel &N = ctx->hier[0].ml[l + 1];
     PhaseClock pu(ctx, ALFD_SETUP_ML_UPLOAD);
-    RC(upload_level_part(ctx, N.gP, Pm, nullptr, true));
-    RC(upload_level_part(ctx, N.gR, R, nullptr, true));
-    N.gP.rep = N.gR.rep = true;
+    RC(upload_level_part(ctx, N.rep.P, Pm, nullptr, true));
+    RC(upload_level_part(ctx, N.rep.R, R, nullptr, true));
+    N.rep.P.rep = N.rep.R.rep = true;
     A = std::move(An);
     C = std::move(Cn);
     Ct = std::move(Ctn);
   }
-  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].gn > 0 && ctx->hier[0].ml[nlev].gn <= c.ml_coarse_direct) {
+  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].rep.n > 0 && ctx->hier[0].ml[nlev].rep.n <= c.ml_coarse_direct) {
     PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
     std::vector<double> w(lam_global);
     HIPC(hipMemcpyAsync(w.data(), ctx->g_w, w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -6026,32 +6050,20 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
 static int level_init(alfd_ctx *ctx, int h, int l, int64_t n, int64_t goff) {
   const alfd_config &c = ctx->cfg;
   MlLevel &L = ctx->hier[h].ml[l];
-  L.n = n;
-  L.npad = pad_chunk(n);
-  RC(ws_alloc_zero(ctx, &L.r, L.npad));
-  RC(ws_alloc_zero(ctx, &L.z, L.npad));
-  RC(ws_alloc_zero(ctx, &L.t, L.npad));
-  RC(ws_alloc_zero(ctx, &L.cd, L.npad));
-  RC(ws_alloc_zero(ctx, &L.cres, L.npad));
-  RC(ws_alloc_zero(ctx, &L.ctmp, L.npad));
+  LevelStore &S = L.loc;
+  S.n = n;
+  S.npad = pad_chunk(n);
+  RC(store_vectors(ctx, S, true));
   if (l == 0) {
-    L.dinv = h == 0 ? ctx->dinv_aug : ctx->dinv_a22;
+    S.dinv = h == 0 ? ctx->dinv_aug : ctx->dinv_a22;
     L.lmax = ctx->lam_max[h == 0 ? OP_AUG : OP_A22];
     return ALFD_OK;
   }
   PhaseClock pc(ctx, ALFD_SETUP_ML_LAMBDA);
-  RC(ws_alloc_zero(ctx, &L.dinv, L.npad));
+  RC(ws_alloc_zero(ctx, &S.dinv, S.npad));
   const AugOp F = level_view(ctx, h, l).op;
-  RC(diag_plus_m(ctx, L.A, L.Ct, c.aug_assembled ? 0.0 : F.gamma, n, L.dinv));
-  double *v = L.t, *wv = L.r;
-  if (n > 0)
-    hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, goff, v);
-  double lam = 0;
-  RC(power_lambda(ctx, L.npad, L.dinv, v, wv, [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); }, &lam));
-  L.lmax = lam * c.cheb_safety;
-  HIPC(hipMemsetAsync(L.t, 0, L.npad * sizeof(double), ctx->stream));
-  HIPC(hipMemsetAsync(L.r, 0, L.npad * sizeof(double), ctx->stream));
-  return ALFD_OK;
+  RC(diag_plus_m(ctx, S.A, S.Ct, c.aug_assembled ? 0.0 : F.gamma, n, S.dinv));
+  return aug_lambda_max(ctx, F, n, goff, S.t, S.r, &L.lmax);
 }
 
 // The next level Nx through a general CSR prolongator Pm (single rank): A_c = P^T (A P), C_c = C P, Ct_c = C_c^T from the
@@ -6059,7 +6071,7 @@ static int level_init(alfd_ctx *ctx, int h, int l, int64_t n, int64_t goff) {
 // planner) when gpu_products allows and they fit, else on the host from hA / hC (null: fetched from the device here).
 // An, Cn, Ctn return the host copies of the new level.
 static int csr_level(alfd_ctx *ctx, const HostCsr &Pm, DevCsr &dA, DevCsr &dC, bool gpu_products, const HostCsr *hA,
-                     const HostCsr *hC, MlLevel &Nx, HostCsr &An, HostCsr &Cn, HostCsr &Ctn) {
+                     const HostCsr *hC, LevelStore &Nx, HostCsr &An, HostCsr &Cn, HostCsr &Ctn) {
   HostCsr R;
   {
     PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
@@ -6187,14 +6199,14 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(patch_setup(ctx, have_host_A ? &A : nullptr, C, Ct));
   }
   for (int l = 0; l <= nlev; ++l) {
-    MlLevel &L = ctx->hier[0].ml[l];
+    LevelStore &L = ctx->hier[0].ml[l].loc;
     const int64_t n = off[l][rk + 1] - off[l][rk];
     RC(level_init(ctx, 0, l, n, off[l][rk]));
     if (l == nlev) break;
     if (!ctx->hier[0].P[l].rp.empty()) {
       // ---- next level through a general CSR prolongator (single rank)
       RC(csr_level(ctx, ctx->hier[0].P[l], l == 0 ? ctx->mat[ALFD_A] : L.A, l == 0 ? ctx->mat[ALFD_C] : L.C, gpu_products,
-                   have_host_A ? &A : nullptr, &C, ctx->hier[0].ml[l + 1], An, Cn, Ctn));
+                   have_host_A ? &A : nullptr, &C, ctx->hier[0].ml[l + 1].loc, An, Cn, Ctn));
       if (l + 1 < nlev) {
         A = std::move(An);      // host copies of the new level: the next level's fallback product, aggregation levels
         have_host_A = true;
@@ -6225,9 +6237,7 @@ static int ml_setup(alfd_ctx *ctx) {
     galerkin(A, agg_rows.data(), w, nc_loc, aggA.data(), w, nc_glob, An);
     galerkin(C, nullptr, nullptr, C.nrows, aggC.data(), w, nc_glob, Cn);
     // Ct_{l+1} = P^T Ct_l: rows grouped by aggregate, multiplier columns back to GLOBAL ids
-    std::vector<int32_t> lam_ids((size_t)dCt.n_local_cols + dCt.halo_globals.size());
-    for (int32_t j = 0; j < dCt.n_local_cols; ++j) lam_ids[j] = (int32_t)(lam0 + j);
-    for (size_t j = 0; j < dCt.halo_globals.size(); ++j) lam_ids[dCt.n_local_cols + j] = dCt.halo_globals[j];
+    const std::vector<int32_t> lam_ids = global_cols(dCt, lam0);
     galerkin(Ct, agg_rows.data(), w, nc_loc, lam_ids.data(), nullptr, lam_global, Ctn);
     // transfers are rank-local: P (n x nc_loc, one entry per represented row), R = P^T
     P.nrows = n;
@@ -6244,7 +6254,7 @@ static int ml_setup(alfd_ctx *ctx) {
     }
     transpose_host(P, R);
     ctx->setup_s[ALFD_SETUP_ML_GALERKIN] += std::chrono::duration<double>(std::chrono::steady_clock::now() - tg0).count();
-    MlLevel &Nx = ctx->hier[0].ml[l + 1];
+    LevelStore &Nx = ctx->hier[0].ml[l + 1].loc;
     PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
     RC(upload_level_part(ctx, Nx.A, An, off[l + 1].data(), false));
     RC(upload_level_part(ctx, Nx.C, Cn, off[l + 1].data(), false));
@@ -6265,7 +6275,7 @@ static int ml_setup(alfd_ctx *ctx) {
       RC(download_csr(ctx, Nx.Ct, Ct));
     }
   }
-  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].n > 0 && ctx->hier[0].ml[nlev].n <= c.ml_coarse_direct) {
+  if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].loc.n > 0 && ctx->hier[0].ml[nlev].loc.n <= c.ml_coarse_direct) {
     // An / Cn / Ctn still hold the coarsest level (global = local column ids on one rank)
     std::vector<double> w(ctx->n[last]);
     HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
@@ -6281,37 +6291,25 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(gather_vec(ctx, ctx->diag[ALFD_INVW], ctx->n[last], ctx->g_w));
     for (int l = rep_from; l <= nlev; ++l) {
       MlLevel &L = ctx->hier[0].ml[l];
-      L.g_offs = off[l];
-      L.gn = off[l].back();
-      L.gnpad = pad_chunk(L.gn);
-      HostCsr g;
-      RC(gather_csr(ctx, stash[l].A, nullptr, L.gn, g));
-      RC(upload_level_part(ctx, L.gA, g, nullptr, true));
-      RC(gather_csr(ctx, stash[l].C, nullptr, L.gn, g));
-      RC(upload_level_part(ctx, L.gC, g, nullptr, true));
-      RC(gather_csr(ctx, stash[l].Ct, nullptr, lam_global, g));
-      RC(upload_level_part(ctx, L.gCt, g, nullptr, true));
-      L.gA.rep = L.gC.rep = L.gCt.rep = true;
+      const int64_t n_all = off[l].back();
+      HostCsr wholeA, wholeC, wholeCt, g;
+      RC(gather_csr(ctx, stash[l].A, nullptr, n_all, wholeA));
+      RC(gather_csr(ctx, stash[l].C, nullptr, n_all, wholeC));
+      RC(gather_csr(ctx, stash[l].Ct, nullptr, lam_global, wholeCt));
+      RC(replicate_level(ctx, l, wholeA, wholeC, wholeCt, off[l], l == rep_from));
       if (l > rep_from) {
-        RC(gather_csr(ctx, stash[l].P, off[l].data(), L.gn, g));        // n_{l-1} x n_l
-        RC(upload_level_part(ctx, L.gP, g, nullptr, true));
+        RC(gather_csr(ctx, stash[l].P, off[l].data(), n_all, g));        // n_{l-1} x n_l
+        RC(upload_level_part(ctx, L.rep.P, g, nullptr, true));
         RC(gather_csr(ctx, stash[l].R, off[l - 1].data(), off[l - 1].back(), g));  // n_l x n_{l-1}
-        RC(upload_level_part(ctx, L.gR, g, nullptr, true));
-        L.gP.rep = L.gR.rep = true;
+        RC(upload_level_part(ctx, L.rep.R, g, nullptr, true));
+        L.rep.P.rep = L.rep.R.rep = true;
       }
-      for (double **v : {&L.gdinv, &L.gr, &L.gz, &L.gt, &L.gcd, &L.gcres, &L.gctmp}) RC(ws_alloc_zero(ctx, v, L.gnpad));
-      RC(gather_vec(ctx, L.dinv, L.n, L.gdinv));
-      if (l == rep_from) {
-        for (int p = 0; p < ctx->nranks; ++p) L.g_maxpiece = std::max(L.g_maxpiece, off[l][p + 1] - off[l][p]);
-        L.g_maxpiece = std::max<int64_t>(L.g_maxpiece, 1);
-        RC(ws_alloc_zero(ctx, &L.g_send, L.g_maxpiece));
-        RC(ws_alloc_zero(ctx, &L.g_stage, L.g_maxpiece * ctx->nranks));
-      }
+      RC(gather_vec(ctx, L.loc.dinv, L.loc.n, L.rep.dinv));
     }
     ctx->ml_rep_level = rep_from;
   }
   for (int l = 0; l <= nlev; ++l)
-    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].Ct, ctx->hier[0].ml[l].npad, &ctx->hier[0].ml[l].tail_mask));
+    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].loc.Ct, ctx->hier[0].ml[l].loc.npad, &ctx->hier[0].ml[l].tail_mask));
   return ALFD_OK;
 }
 
@@ -6337,17 +6335,17 @@ static int ml_setup_immersed(alfd_ctx *ctx) {
   const bool gpu_products = ctx->ml_gpu_galerkin != 0;
   HostCsr An, Cn, Ctn, A, C;
   for (int l = 0; l <= nlev; ++l) {
-    MlLevel &L = H.ml[l];
+    LevelStore &L = H.ml[l].loc;
     RC(level_init(ctx, 1, l, l == 0 ? ctx->n[1] : H.ncoarse[l - 1], 0));
     if (l == nlev) break;
     RC(csr_level(ctx, H.P[l], l == 0 ? ctx->mat[ALFD_A2] : L.A, l == 0 ? ctx->mat[ALFD_M] : L.C, gpu_products,
-                 l == 0 ? nullptr : &A, l == 0 ? nullptr : &C, H.ml[l + 1], An, Cn, Ctn));
+                 l == 0 ? nullptr : &A, l == 0 ? nullptr : &C, H.ml[l + 1].loc, An, Cn, Ctn));
     if (l + 1 < nlev) {
       A = std::move(An);
       C = std::move(Cn);
     }
   }
-  if (c.ml_coarse_direct > 0 && H.ml[nlev].n <= c.ml_coarse_direct) {
+  if (c.ml_coarse_direct > 0 && H.ml[nlev].loc.n <= c.ml_coarse_direct) {
     std::vector<double> w(ctx->n[2]);
     HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
@@ -6355,7 +6353,7 @@ static int ml_setup_immersed(alfd_ctx *ctx) {
     RC(coarse_inverse(ctx, An, Cn, Ctn, w, c.gamma2, H.inv));
   }
   for (int l = 0; l <= nlev; ++l)
-    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].Ct, H.ml[l].npad, &H.ml[l].tail_mask));
+    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].loc.Ct, H.ml[l].loc.npad, &H.ml[l].tail_mask));
   return build_tail_table(ctx);
 }
 
@@ -7360,8 +7358,8 @@ static int build_sa_partitioned(alfd_ctx *ctx, SaParams sp, int32_t *levels_out,
   HostCsr Ctl, Cl, Cg;
   std::vector<double> w_loc, w_g;
   auto to_global = [](HostCsr &h, const DevCsr &m, int64_t c0, int64_t ncols_global) {
-    for (size_t k = 0; k < h.col.size(); ++k)
-      h.col[k] = (int32_t)(h.col[k] < m.n_local_cols ? c0 + h.col[k] : m.halo_globals[h.col[k] - m.n_local_cols]);
+    const std::vector<int32_t> ids = global_cols(m, c0);
+    for (int32_t &col : h.col) col = ids[col];
     h.ncols = ncols_global;
   };
   auto views = [&]() -> int {
@@ -7493,8 +7491,8 @@ static int build_sa_partitioned(alfd_ctx *ctx, SaParams sp, int32_t *levels_out,
     auto host_rows = [&]() -> int {
       HostCsr h;
       RC(download_csr(ctx, dA, h));
-      for (size_t k = 0; k < h.col.size(); ++k)
-        h.col[k] = (int32_t)(shift + (h.col[k] < dA.n_local_cols ? row0 + h.col[k] : dA.halo_globals[h.col[k] - dA.n_local_cols]));
+      const std::vector<int32_t> ids = global_cols(dA, row0);
+      for (int32_t &col : h.col) col = (int32_t)(shift + ids[col]);
       sa_rows_host(h, agg_ext, nc, f, sp.use_pen ? &Q : nullptr, Pl);
       if (sp.tau != 0.0 || sp.cap != 0) {
         HostCsr T;
