@@ -319,7 +319,7 @@ struct alfd_ctx {
   int ml_rep_level = -1;                      // first replicated level (multi-rank), -1: none
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
-  int ml_fuse = 1;                            // fused smoother steps: aug_tail_kernel ("ml_fuse", ALFD_ML_FUSE)
+  int ml_fuse = 2;                            // fused smoother steps: aug_tail_kernel, pair launches ("ml_fuse", ALFD_ML_FUSE)
   int ml_tail_rows = 0;                       // "ml_tail_rows": levels >= 1 of hierarchy 1 with at most this many unknowns
                                               // run in one launch (ml_tail_kernel); 0 = off (the measured default)
   int ml_gpu_galerkin = 1;                    // Galerkin products of CSR-prolongator levels on the device (ALFD_ML_GPU_GALERKIN)
@@ -611,7 +611,7 @@ static void launch_stream(alfd_ctx *ctx, const DevCsr &m, const double *x, doubl
   const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
 #define ALFD_STREAM(EPI)                                                                              \
   hipLaunchKernelGGL((spmv_stream_kernel<R, U, EPI, NT>), dim3(grid), dim3(kBlock), 0, ctx->stream,   \
-                     m.nrows, m.rp, m.col, m.val, x, m.halo, m.n_local_cols, y, alpha, d, y2)
+                     m.nrows, m.rp, m.col, m.val, x, m.halo, m.n_local_cols, y, alpha, d, y2, NoPair())
   if (epi == 0) ALFD_STREAM(0);
   else if (epi == 1) ALFD_STREAM(1);
   else if (epi == 2) ALFD_STREAM(2);
@@ -772,10 +772,9 @@ static void launch_vss(alfd_ctx *ctx, const DevCsr &m, const double *x, double *
 #undef ALFD_VSS
 }
 
-static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
-                      const double *d, double *y2, int64_t first_block = 0, int64_t n_blocks = -1) {
-  const DevCsr::Vs &v = m.vs;
-  if (ctx->vs_lds_base_ok < 0) {   // first batch-major launch of this context: does dynamic LDS start at offset 0?
+// does dynamic LDS start at offset 0 (vs_lds_base_probe_kernel)?  Asked once per context, at its first batch-major launch
+static bool vs_lds_base_ok(alfd_ctx *ctx) {
+  if (ctx->vs_lds_base_ok < 0) {   // not asked yet
     uint32_t *probe = nullptr, base = 1;
     if (hipMalloc((void **)&probe, sizeof(uint32_t)) == hipSuccess) {
       hipLaunchKernelGGL(vs_lds_base_probe_kernel, dim3(1), dim3(64), 4096, ctx->stream, probe);
@@ -787,7 +786,13 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
     if (!ctx->vs_lds_base_ok)
       std::fprintf(stderr, "[alfd] dynamic LDS does not start at offset 0 (%u): batch-major SpMV formats disabled\n", base);
   }
-  if (!ctx->vs_lds_base_ok) return false;
+  return ctx->vs_lds_base_ok != 0;
+}
+
+static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
+                      const double *d, double *y2, int64_t first_block = 0, int64_t n_blocks = -1) {
+  const DevCsr::Vs &v = m.vs;
+  if (!vs_lds_base_ok(ctx)) return false;
   if (v.L == 32) return launch_vss<32>(ctx, m, x, y, epi, alpha, d, y2), true;
   if (v.L == 16) return launch_vss<16>(ctx, m, x, y, epi, alpha, d, y2), true;
   if (v.L == 8) return launch_vss<8>(ctx, m, x, y, epi, alpha, d, y2), true;
@@ -798,7 +803,7 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
   const unsigned grid = (unsigned)n_blocks;
   const int32_t base = (int32_t)first_block;
 #define ALFD_VS_ARGS \
-  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->vs_xcd, base
+  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->vs_xcd, base, NoPair()
 #define ALFD_VS(EPI, NWV)                                                                                        \
   do {                                                                                                           \
     if (v.wide) /* 10-bit codes: one instantiation per epilogue (4 waves) */                                    \
@@ -946,6 +951,77 @@ static int spmv(alfd_ctx *ctx, int slot, const double *x, double *y, int epi, do
   return spmv_m(ctx, m, slot == ALFD_A ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER, x, y, epi, alpha, d, y2);
 }
 
+// ml_tail_kernel and the second party of a pair launch walk the CSR arrays of m: everything spmv_launch_local runs on spmv_kernel or, for 64-lane rows, on
+// the streaming kernel (which reads the same arrays and forms the canonical sums)
+static bool tail_form(const DevCsr &m) { return m.present && !m.vs.on && !m.win; }
+
+// ---- pair launch ("ml_fuse" >= 2): y = A x and t = w .* (C x) of a factored operator read the same x and
+// write different vectors, and the C product is a latency-bound kernel of a few microseconds.  Where A runs on the
+// long-row batch-major kernel (4 waves, narrow codes) or on spmv_stream_kernel<2, 8>, C rides as extra workgroups of
+// that grid (PairC, kernels.hpp).  Same sums, same bits; one launch, timed as A's.
+
+// which PAIR instantiation spmv_launch_local's choice for A has: 1 batch-major, 2 stream, 0 none
+static int pair_form_A(alfd_ctx *ctx, const DevCsr &A) {
+  if (!A.present || A.sparse || A.n_list == 0) return 0;
+  if (A.vs.on && ctx->vs_enable && !ctx->vi_off)
+    return A.vs.L == 64 && !A.vs.wide && ctx->vs_NW == 4 && A.vs.nb > 0 && vs_lds_base_ok(ctx) ? 1 : 0;
+  if (A.win) return 0;
+  return A.L == 64 && ctx->spmv_stream_R == 2 && ctx->spmv_stream_U == 8 && !ctx->spmv_nt ? 2 : 0;
+}
+
+// Partitioned contexts (halo exchanges, the overlap path of spmv_m), the exact W^-1, the assembled operator and the
+// nested grad-div term keep the two launches
+static inline bool gd_nested(const alfd_ctx *ctx);
+// the PAIR instantiation (pair_form_A) that takes A and C together, 0: none
+static int pair_forms(alfd_ctx *ctx, const DevCsr &A, const DevCsr &C) {
+  const bool ok = ctx->nranks == 1 && ctx->cfg.w_inverse == ALFD_W_DIAGONAL && !ctx->cfg.aug_assembled && !gd_nested(ctx) &&
+                  tail_form(C) && !C.sparse && C.nrows > 0 && (C.L == 16 || C.L == 32 || C.L == 64) && A.ncols == C.ncols;
+  return ok ? pair_form_A(ctx, A) : 0;
+}
+// ... and so does the fine level below ml_fuse 3
+static int pair_ok(alfd_ctx *ctx, const DevCsr &A, const DevCsr &C) {
+  const bool fine = &A == &ctx->mat[ALFD_A] || &A == &ctx->mat[ALFD_A2];
+  return ctx->ml_fuse >= (fine ? 3 : 2) ? pair_forms(ctx, A, C) : 0;
+}
+
+// form: what pair_forms(ctx, A, C) answered, not 0
+static int launch_pair(alfd_ctx *ctx, int form, const DevCsr &A, int clsA, const DevCsr &C, const double *w,
+                       const double *x, double *y, double *t) {
+  const bool vi = !ctx->vi_off, vs = ctx->vs_enable != 0 && !ctx->vi_off;
+  Timer tm(ctx, clsA, A.algorithmic_bytes() + C.algorithmic_bytes(), A.streamed_bytes(vi, vs) + C.streamed_bytes(vi, vs));
+  PairC pc;
+  pc.nrows = C.n_list, pc.rp = C.rp, pc.col = C.col, pc.val = C.val, pc.x_halo = C.halo, pc.d = w, pc.t = t;
+  pc.n_local = C.n_local_cols, pc.L = C.L;
+  pc.nC = (uint32_t)grid_for_rows(C.n_list, C.L);
+  if (form == 1) {
+    const DevCsr::Vs &v = A.vs;
+    const size_t lds = (size_t)VsFmt<0>::kWinOff + (size_t)v.maxW * sizeof(double);
+    pc.nA = (uint32_t)v.nb;
+#define ALFD_VS_PAIR(TAG)                                                                                                  \
+  hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, true>), dim3(pc.nA + pc.nC), dim3(256), lds, ctx->stream, v.stream,    \
+                     v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0,            \
+                     (const double *)nullptr, (double *)nullptr, ctx->vs_xcd, 0, pc)
+    if (A.tag == 0) ALFD_VS_PAIR(0);
+    else ALFD_VS_PAIR(1);
+#undef ALFD_VS_PAIR
+  } else {   // as launch_stream<2, 8, false>
+    const int64_t nbatches = (A.nrows + 1) / 2;
+    pc.nA = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
+    hipLaunchKernelGGL((spmv_stream_kernel<2, 8, 0, false, true>), dim3(pc.nA + pc.nC), dim3(kBlock), 0, ctx->stream,
+                       A.nrows, A.rp, A.col, A.val, x, A.halo, A.n_local_cols, y, 0.0, (const double *)nullptr,
+                       (double *)nullptr, pc);
+  }
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+
+// y = A x and t = w .* (C x): the pair launch where it applies, else the two launches
+static int spmv_AC(alfd_ctx *ctx, DevCsr &A, int clsA, DevCsr &C, const double *w, const double *x, double *y, double *t) {
+  if (const int form = pair_ok(ctx, A, C)) return launch_pair(ctx, form, A, clsA, C, w, x, y, t);
+  RC(spmv_m(ctx, A, clsA, x, y, 0));
+  return spmv_m(ctx, C, ALFD_T_SPMV_OTHER, x, t, 2, 0.0, w);
+}
+
 // ------------------------------------------------------------ reductions
 // count dots whose chunk partials sit at partial[j*pstride ..]; results land in
 // sc[out+j] (single rank) with optional PCG post-op.
@@ -1042,13 +1118,14 @@ static int op_apply(alfd_ctx *ctx, int op, const double *x, double *y, bool exac
   const double *w = ctx->diag[ALFD_INVW];
   switch (op) {
     case OP_AUG:
-      RC(spmv(ctx, ALFD_A, x, y, 0));
-      if (ctx->cfg.aug_assembled) return ALFD_OK;  // operator form: A already holds the AL term
+      if (ctx->cfg.aug_assembled) return spmv(ctx, ALFD_A, x, y, 0);  // operator form: A already holds the AL term
       if (exact_w && ctx->cfg.w_inverse != ALFD_W_DIAGONAL) {
+        RC(spmv(ctx, ALFD_A, x, y, 0));
         RC(spmv(ctx, ALFD_C, x, ctx->t_lam, 0));
         RC(winv_scale(ctx, 1.0, ctx->t_lam, ctx->t_lam));
       } else {
-        RC(spmv(ctx, ALFD_C, x, ctx->t_lam, 2, 0.0, w));
+        if (!ctx->mat[ALFD_A].present || !ctx->mat[ALFD_C].present) return ctx->err = "matrix not set", ALFD_E_NOT_SETUP;
+        RC(spmv_AC(ctx, ctx->mat[ALFD_A], ALFD_T_SPMV_A, ctx->mat[ALFD_C], w, x, y, ctx->t_lam));
       }
       RC(spmv(ctx, ALFD_CT, ctx->t_lam, y, 1, ctx->cfg.gamma));
       if (!gd_nested(ctx)) return ALFD_OK;
@@ -3795,10 +3872,9 @@ static AugOp patch_aug(alfd_ctx *ctx) {
   return F;
 }
 
-// y = A x and tlam = invW .* (C x): the first two launches of aug_apply
+// y = A x and tlam = invW .* (C x): the first two launches of aug_apply, or their pair launch
 static int fused_AC(alfd_ctx *ctx, const AugOp &F, const double *x, double *y) {
-  RC(spmv_m(ctx, *F.A, F.clsA, x, y, 0));
-  return spmv_m(ctx, *F.C, ALFD_T_SPMV_OTHER, x, F.tlam, 2, 0.0, F.w);
+  return spmv_AC(ctx, *F.A, F.clsA, *F.C, F.w, x, y, F.tlam);
 }
 
 // y = Aug x.  On level 0 these are the launches of op_apply(OP_AUG) with the diagonal weight: setup() refuses the
@@ -3935,10 +4011,6 @@ static int build_tail_mask(alfd_ctx *ctx, const DevCsr &m, int64_t npad, uint8_t
 
 // ---- the coarse tail of hierarchy 1 in one launch ("ml_tail_rows", ml_tail_kernel)
 static_assert(kTailMaxLevels == ALFD_MAX_LEVELS + 1, "TailTable holds every level of a hierarchy");
-
-// ml_tail_kernel walks the CSR arrays of m: everything spmv_launch_local runs on spmv_kernel or, for 64-lane rows, on
-// the streaming kernel (which reads the same arrays and forms the canonical sums)
-static bool tail_form(const DevCsr &m) { return m.present && !m.vs.on && !m.win; }
 
 static TailCsr tail_csr(const DevCsr &m) {
   TailCsr t;
@@ -4124,15 +4196,12 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   }
   RC(ml_cycle(ctx, 0, 0, Q.rr, z));
   hipLaunchKernelGGL(scatter_add_kernel, dim3(gm), dim3(256), 0, ctx->stream, Q.m, Q.S, Q.zS, z);
-  RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));                           // (Aug z) on S
+  if (pen) RC(spmv_AC(ctx, Q.As, ALFD_T_SPMV_OTHER, ctx->mat[ALFD_C], w, z, Q.uS, ctx->t_lam));   // (Aug z) on S
+  else RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));
   if (fused_ok(ctx, F)) {
-    RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
     RC(fused_correct(ctx, F, pdeg, pratio, Q.rS, Q.uS, Q.eS, nullptr));
   } else {
-    if (pen) {
-      RC(spmv(ctx, ALFD_C, z, ctx->t_lam, 2, 0.0, w));
-      RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
-    }
+    if (pen) RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
     VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);                          // uS = r_S - (Aug z)_S
     RC(aug_cheb(ctx, F, pdeg, pratio, Q.uS, Q.eS));
   }
@@ -6730,7 +6799,7 @@ int alfd_create(alfd_ctx_t *out, int device_id) {
   if (const char *e = std::getenv("ALFD_SPMV_WINDOW_MAXW")) ctx->win_maxW = std::min(16384, std::max(256, std::atoi(e)));
   if (const char *e = std::getenv("ALFD_ML_REPLICATE")) ctx->ml_rep_threshold = std::atoll(e);
   if (const char *e = std::getenv("ALFD_ML_GPU_GALERKIN")) ctx->ml_gpu_galerkin = std::atoi(e);
-  if (const char *e = std::getenv("ALFD_ML_FUSE")) ctx->ml_fuse = std::atoi(e) != 0;
+  if (const char *e = std::getenv("ALFD_ML_FUSE")) ctx->ml_fuse = std::max(0, std::min(3, std::atoi(e)));
   if (const char *e = std::getenv("ALFD_SPMV_VI_LEVELS")) ctx->vi_levels = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR")) ctx->vs_enable = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR_ROWS")) ctx->vs_RB = std::max(4, std::min(kVsMaxRows, std::atoi(e)));
@@ -7909,6 +7978,36 @@ int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d,
   return rc;
 }
 
+int alfd_spmv_pair(alfd_ctx_t ctx, int slot_a, int slot_c, const double *x, const double *d, double *y, double *t) {
+  CHECK_CTX();
+  for (int slot : {slot_a, slot_c})
+    if (slot < 0 || slot >= ALFD_NSLOTS || !ctx->mat[slot].present) return ALFD_E_INVALID;
+  if (!x || !d || !y || !t || t == y) return ALFD_E_INVALID;
+  const DevCsr &A = ctx->mat[slot_a], &Cm = ctx->mat[slot_c];
+  const int form = pair_forms(ctx, A, Cm);
+  if (!form) return ctx->err = "alfd_spmv_pair: the two slots do not qualify for the pair launch", ALFD_E_UNSUPPORTED;
+  double *dx = nullptr, *dd = nullptr, *dy = nullptr, *dt = nullptr;
+  HIPC(hipMalloc((void **)&dx, A.ncols * sizeof(double)));
+  HIPC(hipMalloc((void **)&dd, Cm.nrows * sizeof(double)));
+  HIPC(hipMalloc((void **)&dy, A.nrows * sizeof(double)));
+  HIPC(hipMalloc((void **)&dt, Cm.nrows * sizeof(double)));
+  HIPC(hipMemcpyAsync(dx, x, A.ncols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dd, d, Cm.nrows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dy, y, A.nrows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dt, t, Cm.nrows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  const int rc = launch_pair(ctx, form, A, slot_a == ALFD_A ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER, Cm, dd, dx, dy, dt);
+  if (rc == ALFD_OK) {
+    HIPC(hipMemcpyAsync(y, dy, A.nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipMemcpyAsync(t, dt, Cm.nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+  }
+  hipFree(dx);
+  hipFree(dd);
+  hipFree(dy);
+  hipFree(dt);
+  return rc;
+}
+
 int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z) {
   CHECK_CTX();
   CHECK_SETUP();
@@ -8558,8 +8657,8 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
     ctx->vs_xcd = value != 0;
     return ALFD_OK;
   }
-  if (std::strcmp(name, "ml_fuse") == 0) {   // 0: every smoother step as separate launches (same bits either way)
-    ctx->ml_fuse = value != 0;
+  if (std::strcmp(name, "ml_fuse") == 0) {   // 0: separate launches; 1: aug_tail; 2: + pair launches; 3: + on the fine level
+    ctx->ml_fuse = std::max(0, std::min(3, value));   // as ALFD_ML_FUSE: values outside 0..3 take the nearest level
     return ALFD_OK;
   }
   if (std::strcmp(name, "ml_tail_rows") == 0) {   // 0: off; levels >= 1 of the immersed hierarchy up to this size in one launch

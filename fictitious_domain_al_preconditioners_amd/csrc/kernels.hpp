@@ -16,6 +16,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <type_traits>
 
 namespace alfd {
 
@@ -207,21 +208,19 @@ __device__ __forceinline__ double block_reduce_256(double v, double *lds4) {
 //   EPI 3: y[r]  = s and y2[r] = d[r] * s        (C x kept for the constraint row too)
 // SPARSE: rows[] lists the non-empty rows, rp[] is indexed by list position.
 // Columns >= n_local read the halo buffer (multi-GPU row partition).
+// The body is shared with the second party of a pair launch (pair_rows below): workgroup `block` of `nblocks`.
 template <int L, int EPI, bool SPARSE>
-__global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64_t *__restrict__ rp,
-                                                      const int32_t *__restrict__ col,
-                                                      const double *__restrict__ val,
-                                                      const int32_t *__restrict__ rows,
-                                                      const double *__restrict__ x,
-                                                      const double *__restrict__ x_halo, int32_t n_local,
-                                                      double *__restrict__ y, double alpha,
-                                                      const double *__restrict__ d,
-                                                      double *__restrict__ y2) {
+__device__ __forceinline__ void spmv_rows(int64_t block, int64_t nblocks, int64_t nrows,
+                                          const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
+                                          const double *__restrict__ val, const int32_t *__restrict__ rows,
+                                          const double *__restrict__ x, const double *__restrict__ x_halo,
+                                          int32_t n_local, double *__restrict__ y, double alpha,
+                                          const double *__restrict__ d, double *__restrict__ y2) {
   constexpr int RPB = kBlock / L;
   const int lane = threadIdx.x % L;
   const int sub = threadIdx.x / L;
   const int64_t ngroups = (nrows + RPB - 1) / RPB;
-  for (int64_t g = blockIdx.x; g < ngroups; g += gridDim.x) {
+  for (int64_t g = block; g < ngroups; g += nblocks) {
     const int64_t r = g * RPB + sub;
     if (r < nrows) {  // uniform within the L-lane group
       const int64_t k0 = rp[r], k1 = rp[r + 1];
@@ -249,6 +248,54 @@ __global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64
   }
 }
 
+template <int L, int EPI, bool SPARSE>
+__global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64_t *__restrict__ rp,
+                                                      const int32_t *__restrict__ col,
+                                                      const double *__restrict__ val,
+                                                      const int32_t *__restrict__ rows,
+                                                      const double *__restrict__ x,
+                                                      const double *__restrict__ x_halo, int32_t n_local,
+                                                      double *__restrict__ y, double alpha,
+                                                      const double *__restrict__ d,
+                                                      double *__restrict__ y2) {
+  spmv_rows<L, EPI, SPARSE>(blockIdx.x, gridDim.x, nrows, rp, col, val, rows, x, x_halo, n_local, y, alpha, d, y2);
+}
+
+// --------------------------------------------------------------------------
+// Pair launch: t = d .* (C x) of a factored operator A + gamma Ct W^-1 C as extra workgroups of the grid that computes
+// y = A x (PAIR instantiations of spmv_vs_kernel and spmv_stream_kernel).  Workgroups [0, nA) are the A kernel as it
+// is, with nA where it reads gridDim.x; workgroups [nA, nA + nC) run spmv_rows<L, 2, false> on the CSR arrays of C and
+// return.  The parties share x and nothing else.  For 64-lane rows spmv_rows forms the canonical sums that
+// spmv_stream_kernel reproduces, so the result is that of the separate launch whatever form C runs on alone.
+struct PairC {
+  int64_t nrows;
+  const int64_t *rp;
+  const int32_t *col;
+  const double *val, *x_halo, *d;
+  double *t;
+  int32_t n_local, L;   // lanes per row: 16, 32 or 64
+  uint32_t nA, nC;
+};
+struct NoPair {};
+
+__device__ __forceinline__ uint32_t pair_nA(const NoPair &) { return gridDim.x; }
+__device__ __forceinline__ uint32_t pair_nA(const PairC &c) { return c.nA; }
+
+// the second party, or false: this workgroup belongs to the first
+__device__ __forceinline__ bool pair_rows(const NoPair &, const double *) { return false; }
+__device__ __forceinline__ bool pair_rows(const PairC &c, const double *__restrict__ x) {
+  if (blockIdx.x < c.nA) return false;
+  const int64_t block = blockIdx.x - c.nA;
+  switch (c.L) {   // block-uniform
+    case 16: spmv_rows<16, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+    case 32: spmv_rows<32, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+    default: spmv_rows<64, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+  }
+  return true;
+}
+template <bool PAIR>
+using PairArg = typename std::conditional<PAIR, PairC, NoPair>::type;
+
 // --------------------------------------------------------------------------
 // Streaming CSR SpMV for long rows (canonical L = 64).  One wave owns a batch
 // of R consecutive rows and streams their CONTIGUOUS nnz range with perfectly
@@ -260,16 +307,18 @@ __global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64
 // canonical lane (k advances by 64), so each stream lane's per-row accumulator
 // IS one canonical lane partial, rotated by d_i = (k0_i - k_begin) mod 64.  One
 // ds_bpermute un-rotates before the butterfly.
-template <int R, int U, int EPI, bool NT>
+// PAIR: the grid carries a second party behind its first nA workgroups (pair_rows above).
+template <int R, int U, int EPI, bool NT, bool PAIR = false>
 __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
     int64_t nrows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
     const double *__restrict__ val, const double *__restrict__ x, const double *__restrict__ x_halo,
     int32_t n_local, double *__restrict__ y, double alpha, const double *__restrict__ d,
-    double *__restrict__ y2) {
+    double *__restrict__ y2, PairArg<PAIR> pc) {
+  if (pair_rows(pc, x)) return;
   const int lane = threadIdx.x & 63;
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   const int64_t nbatches = (nrows + R - 1) / R;
-  for (int64_t b = (int64_t)blockIdx.x * 4 + wave; b < nbatches; b += (int64_t)gridDim.x * 4) {
+  for (int64_t b = (int64_t)blockIdx.x * 4 + wave; b < nbatches; b += (int64_t)pair_nA(pc) * 4) {
     const int64_t r0 = b * R;
     int64_t kb[R + 1];
 #pragma unroll

@@ -178,13 +178,17 @@ __device__ __forceinline__ void vs_shared(int32_t rem, const int32_t (&sh)[R], i
   }
 }
 
-template <int EPI, int TAG, int NW, int WD = 0>
+// PAIR (NW = 4 only: the second party is written for 256 threads): the grid carries a second party behind its first nA
+// workgroups, pair_rows in kernels.hpp.  It owns no LDS, so the absolute LDS offsets of the first party stay right.
+template <int EPI, int TAG, int NW, int WD = 0, bool PAIR = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmv_vs_kernel(
     const uint8_t *__restrict__ stream, const uint64_t *__restrict__ tab, int32_t stride,
     const int32_t *__restrict__ hdrb, const int32_t *__restrict__ segx, int32_t seg_stride,
     const double *__restrict__ dict, const double *__restrict__ x, const double *__restrict__ x_halo,
     int32_t n_local, double *__restrict__ y, double alpha, const double *__restrict__ d, double *__restrict__ y2,
-    int xcd_remap, int32_t block_base) {
+    int xcd_remap, int32_t block_base, PairArg<PAIR> pc) {
+  static_assert(!PAIR || NW == 4, "the second party runs on kBlock threads");
+  if (pair_rows(pc, x)) return;
   extern __shared__ double xs[];
   char *sm = (char *)xs;
   double *ds = (double *)(sm + kVsDictOff);
@@ -193,7 +197,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
   int64_t b = blockIdx.x;
   if (xcd_remap) {  // workgroups with equal blockIdx % 8 share an XCD: give each XCD a contiguous run of blocks
-    const int64_t nwg = gridDim.x, q = nwg / 8, rm = nwg % 8, xcd = b % 8, idx = b / 8;
+    const int64_t nwg = pair_nA(pc), q = nwg / 8, rm = nwg % 8, xcd = b % 8, idx = b / 8;
     b = (xcd < rm ? xcd * (q + 1) : rm * (q + 1) + (xcd - rm) * q) + idx;
   }
   b += block_base;   // a launch covers the blocks block_base .. block_base + gridDim.x - 1 (interior / boundary halves)

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
     "alfd_build_smoothed_aggregation_truncated", "alfd_host_truncate_prolongator",
-    "alfd_inner_prec_apply", "alfd_spmv_scaled",
+    "alfd_inner_prec_apply", "alfd_spmv_scaled", "alfd_spmv_pair",
     "alfd_estimate_spectrum", "alfd_get_cg_coefficients", "alfd_host_tridiagonal_extremes",
     "alfd_constraint_residual",
     "alfd_set_prolongator_block", "alfd_build_smoothed_aggregation_block", "alfd_get_prolongator_block",
@@ -93,6 +93,7 @@ def load_library():
         "alfd_get_history": (C.c_int, [vp, vp, i32, C.POINTER(i32)]),
         "alfd_spmv": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, dbl]),
         "alfd_spmv_scaled": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
+        "alfd_spmv_pair": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         "alfd_dot": (C.c_int, [vp, i64, vp, vp, C.POINTER(dbl)]),
         "alfd_inner_prec_apply": (C.c_int, [vp, C.c_int, vp, vp]),
         "alfd_matrix_lanes": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
@@ -453,6 +454,20 @@ class Context:
         y2 = np.ascontiguousarray(y2, np.float64).copy()
         self._ck(self._lib.alfd_spmv_scaled(self._h, slot, x.ctypes.data, d.ctypes.data, y.ctypes.data, y2.ctypes.data))
         return y, y2
+
+    def spmv_pair(self, slot_a, slot_c, x, d, y, t):
+        """The pair launch (alfd_spmv_pair): y = A x for slot_a and t = d .* (C x) for slot_c out of one launch.
+        y and t are uploaded as given before the launch; returns (y, t) as copies.  AlfdError with status
+        E_UNSUPPORTED when the two slots do not qualify."""
+        x = np.ascontiguousarray(x, np.float64)
+        d = np.ascontiguousarray(d, np.float64)
+        y = np.ascontiguousarray(y, np.float64).copy()
+        t = np.ascontiguousarray(t, np.float64).copy()
+        if d.size != t.size:
+            raise ValueError("d and t have the row count of slot_c")
+        self._ck(self._lib.alfd_spmv_pair(self._h, slot_a, slot_c, x.ctypes.data, d.ctypes.data, y.ctypes.data,
+                                          t.ctypes.data))
+        return y, t
 
     def dot(self, x, y):
         x = np.ascontiguousarray(x, np.float64)

@@ -543,6 +543,15 @@ int alfd_spmv(alfd_ctx_t ctx, int slot, const double *x, double *y, int mode, do
  * y and y2 are uploaded as given before the launch.  ALFD_E_INVALID for a null ctx, x, d or y, an unset slot, and
  * y2 == y (the kernels take both as restrict pointers). */
 int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d, double *y, double *y2);
+/* The pair launch of the factored operators (tunable "ml_fuse" >= 2), callable on host data: y = A x for slot_a and
+ * t = d .* (C x) for slot_c out of ONE launch, C as extra workgroups of A's grid.  Same bits as alfd_spmv (mode 0) on
+ * slot_a and alfd_spmv_scaled (y2 == NULL) on slot_c.  x has the common column count, y slot_a's row count, d and t
+ * slot_c's.  ALFD_E_UNSUPPORTED, with y and t untouched, when the pair does not qualify whatever "ml_fuse" says:
+ * slot_a not on the long-row batch-major kernel (4 waves, narrow codes) or the streaming kernel (R = 2, U = 8), slot_c
+ * not resident as plain CSR rows with 16, 32 or 64 lanes per row, different column counts, a partitioned context,
+ * w_inverse != diagonal, aug_assembled, grad_div_in_A = 0.  ALFD_E_INVALID for a null ctx, x, d, y or t, an unset
+ * slot, and t == y. */
+int alfd_spmv_pair(alfd_ctx_t ctx, int slot_a, int slot_c, const double *x, const double *d, double *y, double *t);
 int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double *result);
 /* z = M^-1 r: ONE application of the preconditioner of the inner CG, with no CG around it -- exactly the operator
  * the configured variant's inner solve calls once per iteration (alfd_config::inner_prec: identity, Jacobi, the
@@ -728,11 +737,16 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *   "spectrum_host_stepped" (0/1, default 0): alfd_estimate_spectrum steps its CG on the host (one synchronisation
  *                  per iteration, through the inner CG's own loop) instead of on the device.  Same bits either way.
  *                  "spectrum_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
- *   "ml_fuse"      1 (default; environment ALFD_ML_FUSE, read at alfd_create): inside ALFD_PREC_MULTILEVEL the product
- *                  y += gamma Ct t that ends every factored operator A + gamma Ct invW C and the element-wise kernel
- *                  after it (Chebyshev step, residual, residual + first direction, final z += correction) are one
- *                  launch (aug_tail_kernel); 0: separate launches.  Same bits either way; takes effect at the next
- *                  apply.  Operators whose Ct is not in the plain row-per-lane-group form, partitioned contexts,
+ *   "ml_fuse"      0..3 (default 2; environment ALFD_ML_FUSE, read at alfd_create): how many launches one application
+ *                  of a factored operator A + gamma Ct invW C takes inside ALFD_PREC_MULTILEVEL.  0: separate
+ *                  launches.  1: the product y += gamma Ct t that ends it and the element-wise kernel after it
+ *                  (Chebyshev step, residual, residual + first direction, final z += correction) are one launch
+ *                  (aug_tail_kernel).  2: also t = invW .* (C x) rides as extra workgroups of the launch of y = A x
+ *                  (alfd_spmv_pair above) on the levels l >= 1, on the patch and for A[S,:] / C of the patch
+ *                  correction.  3: also on the fine level, which includes the operator of the inner CG.  Same bits at
+ *                  every value; takes effect at the next apply.  Values outside 0..3 take the nearest level, here
+ *                  and in the environment (before the levels, every non-zero value meant 1).  The first step needs Ct in the plain
+ *                  row-per-lane-group form, the second the forms alfd_spmv_pair names; partitioned contexts,
  *                  grad_div_in_A = 0, w_inverse != diagonal and aug_assembled always use the separate launches.
  *   "ml_tail_rows" (>= 0, default 0 = off): the levels l >= 1 of the block-1 (immersed) hierarchy from the first one
  *                  with at most this many unknowns down to the coarsest run their part of the V-cycle in ONE launch
