@@ -520,7 +520,11 @@ int alfd_solve(alfd_ctx_t ctx, const double *const *rhs_blocks, double *const *x
  * depth-1 calls may be mixed with alfd_solve_resident.) */
 /* Same solve with the vectors already resident in HBM (no PCIe in the timed
  * region): alfd_upload_rhs() then alfd_solve_resident() any number of times,
- * alfd_download_solution() at the end. */
+ * alfd_download_solution() at the end.
+ * alfd_upload_rhs keeps x0_blocks (NULL: zero) as the initial guess next to the right-hand side.  EVERY
+ * alfd_solve_resident starts from that uploaded guess again, not from the previous solution, so repeated calls
+ * repeat the same solve; alfd_download_solution returns the solution of the last one.  An upload without
+ * x0_blocks replaces an earlier guess by zero. */
 int alfd_upload_rhs(alfd_ctx_t ctx, const double *const *rhs_blocks, const double *const *x0_blocks);
 int alfd_solve_resident(alfd_ctx_t ctx, alfd_result *res);
 int alfd_download_solution(alfd_ctx_t ctx, double *const *x_blocks);

@@ -19,7 +19,8 @@ from spmv_reference import Case
 pytestmark = pytest.mark.gpu
 
 
-def _run_ranks(world, n, ref, cfg, levels=None, plan=None):
+def _run_ranks(world, n, ref, cfg, levels=None, plan=None, x0=None):
+    """x0: global start blocks, each rank takes its rows; None starts from zero."""
     plan = plan or partition.slab_partition_stokes3d(n, ref, world)
     group = solver.LocalGroup(world)
     out = [None] * world
@@ -33,7 +34,8 @@ def _run_ranks(world, n, ref, cfg, levels=None, plan=None):
             ctx.set_partition(plan.offsets)
             solver.upload_problem(ctx, pb, cfg, partition.local_aggregates(levels, rank) if levels else None)
             rhs = ctx.augment_rhs(cases.rhs_of(pb))
-            x, res = ctx.solve(rhs)
+            own = None if x0 is None else [v[o[rank]:o[rank + 1]] for v, o in zip(x0, plan.offsets)]
+            x, res = ctx.solve(rhs, x0=own)
             sysx = ctx.system_apply(x)
             out[rank] = dict(x=x, res=res.as_dict(), hist=ctx.history(), rhs=rhs, ax=sysx)
             ctx.close()
