@@ -210,6 +210,7 @@ struct alfd_ctx {
   hipStream_t stream = nullptr;
   hipStream_t xstream = nullptr;                  // halo exchanges that run beside the interior row blocks of an SpMV
   hipEvent_t ev_x = nullptr, ev_halo = nullptr;
+  hipEvent_t ev_in = nullptr;                     // *_device calls: the caller's stream up to the call (made on first use)
   int overlap_halo = -1;                          // ALFD_SPMV_OVERLAP_HALO: 1 on, 0 off, -1 (default): on for the in-process and
                                                   // host transports, off over RCCL until that path has run on hardware once
                                                   // (one communicator driven from two streams)
@@ -6721,6 +6722,95 @@ static int to_host(alfd_ctx *ctx, const double *dev, double *const *blocks) {
   return ALFD_OK;
 }
 
+// ---- caller DEVICE blocks <-> padded device block vector (the *_device entry points)
+static_assert(kMaxBlocks == ALFD_MAX_BLOCKS, "BlockTable size");
+
+// Every non-empty block must be device memory of the context's device; nothing has been launched when this refuses.
+// hipPointerGetAttributes leaves a sticky error for an address the runtime does not know: it is cleared, so that the
+// next HIPC(hipGetLastError()) of the context does not trip over it.
+static int check_device_blocks(alfd_ctx *ctx, const double *const *blocks, const char *what) {
+  for (int b = 0; b < ctx->nblocks; ++b) {
+    if (ctx->n[b] == 0) continue;   // a null pointer is fine there
+    const std::string name = std::string(what) + "[" + std::to_string(b) + "]";
+    if (!blocks[b]) return ctx->err = name + " is a null pointer for a non-empty block", ALFD_E_INVALID;
+    hipPointerAttribute_t at;
+    std::memset(&at, 0, sizeof(at));
+    const hipError_t e = hipPointerGetAttributes(&at, blocks[b]);
+    if (e != hipSuccess) {
+      (void)hipGetLastError();
+      return ctx->err = name + " is not device memory (" + hipGetErrorString(e) + ")", ALFD_E_INVALID;
+    }
+    if (at.type != hipMemoryTypeDevice)
+      return ctx->err = name + " is not device memory (host, managed or unregistered address)", ALFD_E_INVALID;
+    if (at.device != ctx->device)
+      return ctx->err = name + " lives on device " + std::to_string(at.device) + ", the context on device " +
+                        std::to_string(ctx->device), ALFD_E_INVALID;
+    // the block must end inside its allocation (unpack writes n[b] doubles there); where the runtime cannot tell the
+    // extent of an allocation the block is taken as given
+    hipDeviceptr_t base = nullptr;
+    size_t size = 0;
+    if (hipMemGetAddressRange(&base, &size, (hipDeviceptr_t)blocks[b]) != hipSuccess) {
+      (void)hipGetLastError();
+      continue;
+    }
+    const char *end = static_cast<const char *>(base) + size;
+    const char *p = reinterpret_cast<const char *>(blocks[b]);
+    if (p < static_cast<const char *>(base) || (size_t)(end - p) < (size_t)ctx->n[b] * sizeof(double))
+      return ctx->err = name + ": " + std::to_string(ctx->n[b]) + " doubles do not fit the allocation, which ends " +
+                        std::to_string((long long)(end - p)) + " bytes after the pointer", ALFD_E_INVALID;
+  }
+  return ALFD_OK;
+}
+
+// The library's stream waits (on the device) for everything the caller has enqueued on `s` so far.
+static int await_stream(alfd_ctx *ctx, void *s) {
+  hipStream_t caller = static_cast<hipStream_t>(s);
+  if (caller == ctx->stream) return ALFD_OK;
+  if (!ctx->ev_in) HIPC(hipEventCreateWithFlags(&ctx->ev_in, hipEventDisableTiming));
+  HIPC(hipEventRecord(ctx->ev_in, caller));
+  HIPC(hipStreamWaitEvent(ctx->stream, ctx->ev_in, 0));
+  return ALFD_OK;
+}
+
+static BlockTable block_table(alfd_ctx *ctx, const double *const *blocks) {
+  BlockTable t;
+  std::memset(&t, 0, sizeof(t));
+  t.nblocks = ctx->nblocks;
+  for (int b = 0; b < ctx->nblocks; ++b) {
+    t.p[b] = const_cast<double *>(blocks[b]);
+    t.n[b] = ctx->n[b];
+    t.off[b] = ctx->off[b];
+  }
+  for (int b = ctx->nblocks; b <= kMaxBlocks; ++b) t.off[b] = ctx->ntot();
+  return t;
+}
+// at most 2048 workgroups, every one with the same number of chunks (up to one): 2527 chunks -> 1264 x 2
+static unsigned block_grid(int64_t nchunks) {
+  const int64_t per = (nchunks + 2047) / 2048;
+  return (unsigned)((nchunks + per - 1) / per);
+}
+
+// dev (ntot() doubles) <- blocks, padding zeroed; enqueued on ctx->stream, no synchronisation
+static int pack_device(alfd_ctx *ctx, const double *const *blocks, double *dev) {
+  const int64_t nchunks = ctx->ntot() / kChunk;
+  if (nchunks == 0) return ALFD_OK;
+  hipLaunchKernelGGL(pack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                     block_table(ctx, blocks), dev, nchunks);
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+// blocks <- dev, the first n[b] entries of every block; synchronises: on return the blocks are complete
+static int unpack_device(alfd_ctx *ctx, const double *dev, double *const *blocks) {
+  const int64_t nchunks = ctx->ntot() / kChunk;
+  if (nchunks > 0) {
+    hipLaunchKernelGGL(unpack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                       block_table(ctx, blocks), dev, nchunks);
+    HIPC(hipGetLastError());
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
+}
+
 static void reset_stats(alfd_ctx *ctx) {
   ctx->inner_its = ctx->mp_its = 0;
   ctx->inner_its_op[0] = ctx->inner_its_op[1] = ctx->inner_its_op[2] = 0;
@@ -6836,6 +6926,7 @@ int alfd_destroy(alfd_ctx_t ctx) {
   if (ctx->xstream) hipStreamDestroy(ctx->xstream);
   if (ctx->ev_x) hipEventDestroy(ctx->ev_x);
   if (ctx->ev_halo) hipEventDestroy(ctx->ev_halo);
+  if (ctx->ev_in) hipEventDestroy(ctx->ev_in);
   hipStreamDestroy(ctx->stream);
   delete ctx;
   return ALFD_OK;
@@ -7916,6 +8007,95 @@ int alfd_solve(alfd_ctx_t ctx, const double *const *rhs, double *const *x, alfd_
   const int rc = alfd_solve_resident(ctx, res);
   const int rc2 = alfd_download_solution(ctx, x);
   return rc != ALFD_OK ? rc : rc2;
+}
+
+// ---- the same calls on caller DEVICE blocks: validate, await the caller's stream, pack (all inputs before any
+// output is written, so outputs may alias inputs), run the code of the host-pointer call, unpack, synchronise.
+int alfd_upload_rhs_device(alfd_ctx_t ctx, const double *const *rhs, const double *const *x0, void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!rhs) return ALFD_E_INVALID;
+  RC(check_device_blocks(ctx, rhs, "rhs_blocks"));
+  if (x0) RC(check_device_blocks(ctx, x0, "x0_blocks"));
+  RC(await_stream(ctx, stream));
+  RC(pack_device(ctx, rhs, ctx->bb));
+  if (x0)
+    RC(pack_device(ctx, x0, ctx->io));
+  else
+    HIPC(hipMemsetAsync(ctx->io, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
+}
+
+int alfd_download_solution_device(alfd_ctx_t ctx, double *const *x, void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!x) return ALFD_E_INVALID;
+  RC(check_device_blocks(ctx, x, "x_blocks"));
+  RC(await_stream(ctx, stream));   // work the caller has queued on x (readers included) ends before x is written
+  return unpack_device(ctx, ctx->xb, x);
+}
+
+int alfd_solve_device(alfd_ctx_t ctx, const double *const *rhs, double *const *x, alfd_result *res, void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!rhs || !x || !res) return ALFD_E_INVALID;
+  RC(check_device_blocks(ctx, rhs, "rhs_blocks"));
+  RC(check_device_blocks(ctx, x, "x_blocks"));
+  RC(await_stream(ctx, stream));
+  RC(pack_device(ctx, rhs, ctx->bb));
+  RC(pack_device(ctx, x, ctx->io));
+  const int rc = alfd_solve_resident(ctx, res);
+  const int rc2 = unpack_device(ctx, ctx->xb, x);
+  return rc != ALFD_OK ? rc : rc2;
+}
+
+int alfd_precond_apply_device(alfd_ctx_t ctx, const double *const *src, double *const *dst, alfd_result *res,
+                              void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!src || !dst) return ALFD_E_INVALID;
+  RC(check_device_blocks(ctx, src, "src_blocks"));
+  RC(check_device_blocks(ctx, dst, "dst_blocks"));
+  RC(await_stream(ctx, stream));
+  reset_stats(ctx);
+  RC(pack_device(ctx, src, ctx->st_in));
+  HIPC(hipMemsetAsync(ctx->st_out, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  const int rc = precond_apply(ctx, ctx->st_in, ctx->st_out);
+  RC(unpack_device(ctx, ctx->st_out, dst));
+  if (res) {
+    std::memset(res, 0, sizeof(*res));
+    fill_result(ctx, res, rc);
+  }
+  return rc;
+}
+
+int alfd_system_apply_device(alfd_ctx_t ctx, const double *const *src, double *const *dst, void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!src || !dst) return ALFD_E_INVALID;
+  RC(check_device_blocks(ctx, src, "src_blocks"));
+  RC(check_device_blocks(ctx, dst, "dst_blocks"));
+  RC(await_stream(ctx, stream));
+  RC(pack_device(ctx, src, ctx->st_in));
+  HIPC(hipMemsetAsync(ctx->st_out, 0, ctx->ntot() * sizeof(double), ctx->stream));
+  RC(system_apply(ctx, ctx->st_in, ctx->st_out));
+  return unpack_device(ctx, ctx->st_out, dst);
+}
+
+int alfd_augment_rhs_device(alfd_ctx_t ctx, double *const *rhs, void *stream) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (!rhs) return ALFD_E_INVALID;
+  if (!ctx->diag[ALFD_INVW] || ctx->cfg.variant == ALFD_RATIONAL)
+    return ctx->err = "rhs augmentation applies to the AL variants only", ALFD_E_UNSUPPORTED;
+  RC(check_device_blocks(ctx, rhs, "rhs_blocks"));
+  RC(await_stream(ctx, stream));
+  const int last = ctx->nblocks - 1;
+  RC(pack_device(ctx, rhs, ctx->st_in));
+  RC(winv_scale(ctx, 1.0, ctx->st_in + ctx->off[last], ctx->t_lam));
+  RC(spmv(ctx, ALFD_CT, ctx->t_lam, ctx->st_in + ctx->off[0], 1, ctx->cfg.gamma));
+  return unpack_device(ctx, ctx->st_in, rhs);
 }
 
 int alfd_get_history(alfd_ctx_t ctx, double *out, int32_t capacity, int32_t *count) {

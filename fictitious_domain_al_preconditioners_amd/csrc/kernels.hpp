@@ -2747,4 +2747,73 @@ __global__ __launch_bounds__(kBlock) void linf_final_kernel(const double *__rest
   if (threadIdx.x == 0) out[0] = s;
 }
 
+// ---- caller block vectors <-> the padded internal vector (the *_device entry points of the C ABI).
+// The internal vector concatenates the blocks, each padded to a multiple of kChunk (off[b + 1] - off[b]); the padding
+// must be ZERO because the fused dot / update kernels read it.  The table travels by value as a kernel argument.
+// One workgroup moves one 4096-double chunk at a time (grid-stride over the chunks); a chunk lies in exactly one
+// block, and an empty block (off[b] == off[b + 1], null pointer allowed) owns no chunk, so it is never dereferenced.
+// Caller pointers are only 8-byte aligned (a view t[1:]): plain 8-byte accesses there; the internal side is
+// chunk-aligned and moves 16 bytes per lane.  Thread t takes the pairs base + e*512 + 2t, e = 0..7: a wave covers
+// 1 KiB contiguous on both sides.
+static_assert(kChunk == 16 * kBlock, "pack / unpack: 8 passes of 2 doubles per thread cover one chunk");
+constexpr int kMaxBlocks = 3;   // == ALFD_MAX_BLOCKS
+struct BlockTable {
+  double *p[kMaxBlocks];        // caller pointers (read by pack, written by unpack)
+  int64_t n[kMaxBlocks];        // block lengths
+  int64_t off[kMaxBlocks + 1];  // padded offsets into the internal vector
+  int32_t nblocks;
+};
+
+// the block that owns the chunk starting at `base` (base < off[nblocks]): the last b with off[b] <= base
+__device__ __forceinline__ void block_of_chunk(const BlockTable &tab, int64_t base, double *&p, int64_t &m) {
+  p = tab.p[0];
+  int64_t n = tab.n[0], o = tab.off[0];
+#pragma unroll
+  for (int b = 1; b < kMaxBlocks; ++b)
+    if (b < tab.nblocks && base >= tab.off[b]) p = tab.p[b], n = tab.n[b], o = tab.off[b];
+  p += base - o;          // first caller element of this chunk (not dereferenced when m <= 0)
+  m = n - (base - o);     // caller elements from there on; >= kChunk except in the block's last chunk
+}
+
+__global__ __launch_bounds__(kBlock) void pack_blocks_kernel(BlockTable tab, double *__restrict__ dst, int64_t nchunks) {
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t base = c * kChunk;
+    double *p;
+    int64_t m;
+    block_of_chunk(tab, base, p, m);
+    const double *__restrict__ src = p;
+    double2 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = e * 512 + 2 * (int)threadIdx.x;
+      v[e].x = i < m ? src[i] : 0.0;
+      v[e].y = i + 1 < m ? src[i + 1] : 0.0;
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      *reinterpret_cast<double2 *>(dst + base + e * 512 + 2 * (int)threadIdx.x) = v[e];
+  }
+}
+
+__global__ __launch_bounds__(kBlock) void unpack_blocks_kernel(BlockTable tab, const double *__restrict__ src,
+                                                               int64_t nchunks) {
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t base = c * kChunk;
+    double *p;
+    int64_t m;
+    block_of_chunk(tab, base, p, m);
+    double *__restrict__ dst = p;
+    double2 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      v[e] = *reinterpret_cast<const double2 *>(src + base + e * 512 + 2 * (int)threadIdx.x);
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = e * 512 + 2 * (int)threadIdx.x;
+      if (i < m) dst[i] = v[e].x;
+      if (i + 1 < m) dst[i + 1] = v[e].y;
+    }
+  }
+}
+
 }  // namespace alfd

@@ -42,6 +42,8 @@ ABI_SYMBOLS = [
     "alfd_set_prolongator_block", "alfd_build_smoothed_aggregation_block", "alfd_get_prolongator_block",
     "alfd_clear_hierarchy", "alfd_get_inner_iterations", "alfd_get_aggregates_block",
     "alfd_host_strength_graph", "alfd_host_aggregate_graph", "alfd_build_strength_graph", "alfd_get_strength_graph",
+    "alfd_upload_rhs_device", "alfd_download_solution_device", "alfd_solve_device", "alfd_precond_apply_device",
+    "alfd_system_apply_device", "alfd_augment_rhs_device",
 ]
 
 
@@ -151,6 +153,13 @@ def load_library():
         "alfd_host_aggregate_graph": (C.c_int, [i64, vp, vp, vp, vp, i32, i32, vp, C.POINTER(i64)]),
         "alfd_build_strength_graph": (C.c_int, [vp, i32, dbl, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_get_strength_graph": (C.c_int, [vp, vp, vp, vp, vp, vp, i64, C.POINTER(i32)]),
+        # device-resident vectors: block tables of DEVICE pointers, the caller's hipStream_t last
+        "alfd_upload_rhs_device": (C.c_int, [vp, PP, PP, vp]),
+        "alfd_download_solution_device": (C.c_int, [vp, PP, vp]),
+        "alfd_solve_device": (C.c_int, [vp, PP, PP, C.POINTER(_abi.Result), vp]),
+        "alfd_precond_apply_device": (C.c_int, [vp, PP, PP, C.POINTER(_abi.Result), vp]),
+        "alfd_system_apply_device": (C.c_int, [vp, PP, PP, vp]),
+        "alfd_augment_rhs_device": (C.c_int, [vp, PP, vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -158,6 +167,15 @@ def load_library():
         fn.argtypes = args
     _lib = lib
     return lib
+
+
+def _hip_runtimes():
+    """Paths of the HIP runtime libraries mapped into this process (more than one: see Context._ck_dev)."""
+    try:
+        with open("/proc/self/maps") as f:
+            return sorted({line.split()[-1] for line in f if "libamdhip64" in line})
+    except OSError:
+        return []
 
 
 def _blocks(arrs):
@@ -421,6 +439,99 @@ class Context:
         x = [np.zeros(n) for n in self.block_sizes]
         self._ck(self._lib.alfd_download_solution(self._h, _blocks(x)))
         return x
+
+    # -- hot path on caller DEVICE buffers (alfd_*_device): no copy through the host
+    def _dev(self, blocks, what, writable=False):
+        """ctypes pointer table of one device array per block: any object with __cuda_array_interface__ (torch ROCm
+        tensors, cupy arrays), float64, 1-D, contiguous, as long as its block.  The optional "stream" entry of the
+        interface (version 3) is not read: the stream to wait for is the `stream` argument of the call alone, so for
+        arrays that are not torch tensors pass it explicitly (None is the null stream for them)."""
+        blocks = list(blocks)
+        if self.block_sizes is None or len(blocks) != len(self.block_sizes):
+            raise ValueError(f"{what}: {len(blocks)} blocks, the context has {self.block_sizes}")
+        table = (C.c_void_p * len(blocks))()
+        for b, (arr, n) in enumerate(zip(blocks, self.block_sizes)):
+            try:
+                cai = getattr(arr, "__cuda_array_interface__", None)
+            except Exception as e:   # noqa: BLE001  (torch raises RuntimeError for a tensor that requires grad)
+                raise ValueError(f"{what}[{b}] does not export __cuda_array_interface__: {e}") from None
+            if cai is None:
+                raise ValueError(f"{what}[{b}] has no __cuda_array_interface__ (a device array is required; "
+                                 "host arrays go through the calls without _device)")
+            shape, strides = tuple(cai["shape"]), cai.get("strides")
+            if np.dtype(cai["typestr"]) != np.dtype(np.float64):
+                raise ValueError(f"{what}[{b}]: dtype {cai['typestr']}, float64 is required")
+            if len(shape) != 1:
+                raise ValueError(f"{what}[{b}]: shape {shape}, a 1-D array is required")
+            if shape[0] != n:
+                raise ValueError(f"{what}[{b}]: length {shape[0]}, the block has {n}")
+            if strides is not None and shape[0] > 1 and tuple(strides) != (8,):
+                raise ValueError(f"{what}[{b}]: strides {tuple(strides)}, a contiguous array is required")
+            ptr, readonly = cai["data"]
+            if writable and readonly:
+                raise ValueError(f"{what}[{b}] is read-only")
+            table[b] = int(ptr) if n > 0 else None
+        return table
+
+    def _ck_dev(self, rc):
+        """_ck for the *_device calls.  A refused block may be a tensor of ANOTHER HIP runtime: a torch wheel ships its
+        own libamdhip64 and, imported after libalfd.so was loaded, runs on that second copy -- whose allocations the
+        library's runtime does not know.  Say so instead of "not device memory" alone."""
+        if rc == _abi.E_INVALID and len(_hip_runtimes()) > 1:
+            msg = self._lib.alfd_last_error(self._h).decode() or self._lib.alfd_strerror(rc).decode()
+            raise AlfdError(rc, msg + "; this process has loaded more than one HIP runtime (" +
+                            ", ".join(_hip_runtimes()) + "): import torch before the first use of this package, "
+                            "so that the tensors and the library share one")
+        self._ck(rc)
+
+    @staticmethod
+    def _stream(stream, *block_lists):
+        """Raw hipStream_t handle: an integer as given (0: the null stream), an object with .cuda_stream (a
+        torch.cuda.Stream), None: torch's current stream on the tensors' device when torch is already imported and all
+        arguments are torch tensors, else the null stream."""
+        if stream is not None:
+            return C.c_void_p(int(getattr(stream, "cuda_stream", stream)) or None)
+        import sys
+        torch = sys.modules.get("torch")
+        arrs = [a for blocks in block_lists if blocks is not None for a in blocks]
+        if torch is None or not arrs or not all(isinstance(a, torch.Tensor) for a in arrs):
+            return C.c_void_p(None)
+        return C.c_void_p(int(torch.cuda.current_stream(arrs[0].device).cuda_stream) or None)
+
+    def precond_apply_device(self, src, dst, stream=None):
+        """dst = P^-1 src on device arrays (alfd_precond_apply_device); dst may be src.  Returns the result record."""
+        res = _abi.Result()
+        self._ck_dev(self._lib.alfd_precond_apply_device(self._h, self._dev(src, "src"), self._dev(dst, "dst", True),
+                                                     C.byref(res), self._stream(stream, src, dst)))
+        return res
+
+    def system_apply_device(self, src, dst, stream=None):
+        """dst = AA src on device arrays (alfd_system_apply_device); dst may be src."""
+        self._ck_dev(self._lib.alfd_system_apply_device(self._h, self._dev(src, "src"), self._dev(dst, "dst", True),
+                                                    self._stream(stream, src, dst)))
+
+    def augment_rhs_device(self, rhs, stream=None):
+        """rhs[0] += gamma Ct invW rhs[last], in place on device arrays (alfd_augment_rhs_device)."""
+        self._ck_dev(self._lib.alfd_augment_rhs_device(self._h, self._dev(rhs, "rhs", True), self._stream(stream, rhs)))
+
+    def solve_device(self, rhs, x, stream=None, raise_on_failure=True):
+        """Solve on device arrays (alfd_solve_device): x holds the initial guess on entry and the solution on return
+        (also when the solve did not converge); x blocks may alias rhs blocks.  Returns the result record."""
+        res = _abi.Result()
+        rc = self._lib.alfd_solve_device(self._h, self._dev(rhs, "rhs"), self._dev(x, "x", True), C.byref(res),
+                                         self._stream(stream, rhs, x))
+        if rc != _abi.OK and raise_on_failure:
+            self._ck_dev(rc)
+        return res
+
+    def upload_rhs_device(self, rhs, x0=None, stream=None):
+        """alfd_upload_rhs_device: right-hand side and initial guess (None: zero) of solve_resident from device arrays."""
+        x0t = self._dev(x0, "x0") if x0 is not None else None
+        self._ck_dev(self._lib.alfd_upload_rhs_device(self._h, self._dev(rhs, "rhs"), x0t, self._stream(stream, rhs, x0)))
+
+    def download_solution_device(self, x, stream=None):
+        """alfd_download_solution_device: the solution of the last solve_resident into device arrays."""
+        self._ck_dev(self._lib.alfd_download_solution_device(self._h, self._dev(x, "x", True), self._stream(stream, x)))
 
     def history(self):
         cnt = C.c_int32(0)

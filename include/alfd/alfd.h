@@ -14,7 +14,8 @@
  *
  * Conventions: every call returns an int status (never throws across the
  * ABI); all pointers at the ABI are HOST pointers -- device residency is
- * internal; a context is single-threaded (like the reference, which runs
+ * internal -- except the block vectors of the alfd_*_device calls, which are
+ * the caller's DEVICE buffers; a context is single-threaded (like the reference, which runs
  * MPI_InitFinalize(argc, argv, 1)); several contexts may coexist.
  * All floating point data is fp64; column indices are int32, row starts int64
  * (deal.II: unsigned int columns, std::size_t rowstart).
@@ -528,6 +529,66 @@ int alfd_solve(alfd_ctx_t ctx, const double *const *rhs_blocks, double *const *x
 int alfd_upload_rhs(alfd_ctx_t ctx, const double *const *rhs_blocks, const double *const *x0_blocks);
 int alfd_solve_resident(alfd_ctx_t ctx, alfd_result *res);
 int alfd_download_solution(alfd_ctx_t ctx, double *const *x_blocks);
+/* ------------------------------------------------- device-resident vectors
+ * The six vector calls above on the caller's GPU buffers: a right-hand side
+ * assembled on the device, a time-stepping loop, an outer iteration that starts
+ * each solve from the previous solution never cross PCIe.  The block tables
+ * (rhs_blocks, x_blocks, ...) are HOST arrays of one DEVICE pointer per block,
+ * each addressing this rank's rows of the block (n[b] doubles; 8-byte alignment
+ * is enough, views such as t[1:] are fine).  `stream` is the caller's
+ * hipStream_t (NULL: the null stream).
+ *   Same computation.  One kernel launch packs the blocks into the library's
+ *     padded vector, one unpacks them; in between runs
+ *     the code of the host-pointer call, so the results are bit-identical to
+ *     it on the same data.  alfd_solve_device = alfd_upload_rhs_device +
+ *     alfd_solve_resident + alfd_download_solution_device; like alfd_solve it
+ *     writes x also when the solve returns a no-convergence status.
+ *     alfd_precond_apply_device, alfd_system_apply_device and
+ *     alfd_augment_rhs_device use the staging of the depth-1 calls: a resident
+ *     right-hand side / guess stays intact.
+ *   Ordering.  The inputs are awaited ON THE DEVICE: whatever the caller has
+ *     enqueued on `stream` before the call (producers of the inputs, earlier
+ *     readers of the outputs) completes before the library touches a block;
+ *     no host synchronisation is needed before the call.  The call itself is
+ *     host-synchronous (the Krylov loops are stepped by the host): on return
+ *     the outputs are complete and visible to every stream.  Work on OTHER
+ *     streams that touches the blocks is the caller's to order.  The calls
+ *     cannot be captured into a HIP graph.
+ *   Validation, before anything is launched.  Every block with n[b] > 0 is
+ *     looked up with hipPointerGetAttributes and must be device memory
+ *     (hipMemoryTypeDevice) of the context's device: a host pointer, a null
+ *     pointer, managed memory or memory of another device returns
+ *     ALFD_E_INVALID with the block named in alfd_last_error; the runtime's
+ *     error state is cleared and the context stays usable.  So does a block
+ *     whose n[b] doubles do not end inside its allocation
+ *     (hipMemGetAddressRange; where the runtime cannot tell the extent the
+ *     block is taken as given, and inside a pooled allocation the check sees
+ *     the pool).  A null block pointer is accepted for n[b] == 0 only (a rank
+ *     without multiplier rows).  A null ctx, a null block table, a null res of
+ *     alfd_solve_device: ALFD_E_INVALID; before alfd_setup: ALFD_E_NOT_SETUP;
+ *     alfd_augment_rhs_device on ALFD_RATIONAL: ALFD_E_UNSUPPORTED, as the
+ *     host call.
+ *   Aliasing.  All inputs are packed before any output is written: dst may
+ *     equal src, x blocks may alias rhs blocks, and the blocks may be views
+ *     into one allocation.  The OUTPUT blocks of one call must not overlap
+ *     each other.
+ *   Partitioned contexts.  Collective exactly like the host-pointer calls
+ *     (every rank calls, one thread / process each); the pointers address the
+ *     rank's own rows.  A refusal on one rank leaves the others waiting, as
+ *     with any collective whose arguments are wrong on one side.
+ * x0_blocks == NULL: zero guess.  res of alfd_precond_apply_device may be
+ * NULL. */
+int alfd_upload_rhs_device(alfd_ctx_t ctx, const double *const *rhs_blocks, const double *const *x0_blocks,
+                           void *stream);
+int alfd_download_solution_device(alfd_ctx_t ctx, double *const *x_blocks, void *stream);
+/* x_blocks: in = initial guess, out = solution. */
+int alfd_solve_device(alfd_ctx_t ctx, const double *const *rhs_blocks, double *const *x_blocks, alfd_result *res,
+                      void *stream);
+int alfd_precond_apply_device(alfd_ctx_t ctx, const double *const *src_blocks, double *const *dst_blocks,
+                              alfd_result *res, void *stream);
+int alfd_system_apply_device(alfd_ctx_t ctx, const double *const *src_blocks, double *const *dst_blocks, void *stream);
+/* rhs_blocks[0] is updated in place from rhs_blocks[last]. */
+int alfd_augment_rhs_device(alfd_ctx_t ctx, double *const *rhs_blocks, void *stream);
 /* Inner CG iterations of the last solve (or alfd_precond_apply) by inner operator, counts[alfd_inner_op]: the
  * augmented (1,1) block, A22, the 2-block operator.  alfd_result::inner_iterations is their sum (plus the K solves of
  * the rational variant). */
