@@ -104,6 +104,24 @@ class MatrixInfo(C.Structure):
     ]
 
 
+class BatchMajorShape(C.Structure):
+    _fields_ = [
+        ("batch_major", C.c_int32), ("lanes", C.c_int32),
+        ("nrows", C.c_int64), ("nnz", C.c_int64), ("shared_nnz", C.c_int64),
+        ("rows", C.c_int64), ("waves", C.c_int64), ("small", C.c_int64),
+        ("blocks", C.c_int64), ("batches", C.c_int64), ("lds_bytes", C.c_int64), ("compute_units", C.c_int64),
+    ]
+
+    def as_dict(self):
+        """Keys as matrix_info reports them (batch_major_* for what is particular to the batch-major forms)."""
+        plain = ("batch_major", "lanes", "nrows", "nnz", "shared_nnz")
+        return {(k if k in plain else "batch_major_" + k): getattr(self, k) for k, _ in self._fields_}
+
+
+# alfd_operator: the operators the library builds at alfd_setup (alfd_get_operator_info, alfd_bench_operator)
+OPERATOR_LEVEL, OPERATOR_PATCH_SS, OPERATOR_PATCH_S = 0, 1, 2
+
+
 class WindowPlanInfo(C.Structure):
     _fields_ = [
         ("windowed", C.c_int32), ("value_indexed", C.c_int32), ("row_block", C.c_int32), ("max_window", C.c_int32),

@@ -106,6 +106,8 @@ struct DevCsr {
     int32_t stride = 0, maxW = 0;
     int32_t L = 64, tab_u64 = 16;  // lanes per row of the format; descriptor words per batch
     int32_t wide = 0;              // 10-bit codes / 11-bit window columns (VsFmt<1>)
+    int32_t RB = 0, NW = 4;        // long rows: rows per block the plan was made with, waves per workgroup of its launches
+    bool small = false;            // RB / NW chosen by vs_small_shape ("batch_major_small"), not the context's defaults
     uint8_t *stream = nullptr;
     int64_t *sb = nullptr;
     uint64_t *tab = nullptr;
@@ -369,6 +371,9 @@ struct alfd_ctx {
   int win_vi = 1;                           // dictionary-coded values in window blocks (ALFD_SPMV_VALUE_INDEX)
   int win_short_scale = 2;                  // short-row block = min(512, win_RB * scale * 64 / L) rows; 0 = off
   int vs_enable = 1, vs_NW = 4, vs_RB = 96, vs_xcd = 0, vs_share = 1, vs_wide = 1;
+  int vs_small = 1;                         // "batch_major_small": level / patch operators that leave the chip under-filled get smaller row blocks (vs_small_shape)
+  int vs_cus = 0;                           // compute units of the device (hipDeviceProp_t::multiProcessorCount)
+  int vs_force_RB = 0, vs_force_NW = 0;     // alfd_bench_operator: the shape of the next build_vs, whatever the rule says
   int vs_lds_base_ok = -1;                  // -1 unknown; the absolute LDS addressing of kernels_vs.hpp needs base 0   // batch-major format (alfd_set_tunable "batch_major")
   std::vector<int64_t> rb_ptr[ALFD_NSLOTS + 1];   // row-block hint per slot (alfd_set_row_blocks)
   std::vector<int32_t> rb_rows[ALFD_NSLOTS + 1];
@@ -797,7 +802,7 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
   if (v.L == 32) return launch_vss<32>(ctx, m, x, y, epi, alpha, d, y2), true;
   if (v.L == 16) return launch_vss<16>(ctx, m, x, y, epi, alpha, d, y2), true;
   if (v.L == 8) return launch_vss<8>(ctx, m, x, y, epi, alpha, d, y2), true;
-  const int NW = ctx->vs_NW;
+  const int NW = v.NW;
   const size_t lds = (size_t)(v.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)v.maxW * sizeof(double);
   if (n_blocks < 0) n_blocks = v.nb - first_block;
   if (n_blocks <= 0) return true;
@@ -813,9 +818,9 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
     else if (m.tag == 0)                                                                                         \
       hipLaunchKernelGGL((spmv_vs_kernel<EPI, 0, NWV>), dim3(grid), dim3(64 * NWV), lds, ctx->stream, \
                          ALFD_VS_ARGS);                                                                          \
-    else /* multigrid level matrix: its own instantiation, so that profiles keep the two apart */               \
-      hipLaunchKernelGGL((spmv_vs_kernel<EPI, 1, 4>), dim3(grid), dim3(256), lds, ctx->stream,        \
-                         ALFD_VS_ARGS);                                                                          \
+    else /* multigrid level matrix: its own instantiation, so that profiles keep the two apart (8 waves: 4) */  \
+      hipLaunchKernelGGL((spmv_vs_kernel<EPI, 1, (NWV > 4 ? 4 : NWV)>), dim3(grid), dim3(64 * (NWV > 4 ? 4 : NWV)), lds, \
+                         ctx->stream, ALFD_VS_ARGS);                                                             \
   } while (0)
 #define ALFD_VS_E(NWV)                  \
   do {                                  \
@@ -826,6 +831,7 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
   } while (0)
   if (NW == 8) ALFD_VS_E(8);
   else if (NW == 2) ALFD_VS_E(2);
+  else if (NW == 1) ALFD_VS_E(1);
   else ALFD_VS_E(4);
 #undef ALFD_VS_E
 #undef ALFD_VS
@@ -958,14 +964,14 @@ static bool tail_form(const DevCsr &m) { return m.present && !m.vs.on && !m.win;
 
 // ---- pair launch ("ml_fuse" >= 2): y = A x and t = w .* (C x) of a factored operator read the same x and
 // write different vectors, and the C product is a latency-bound kernel of a few microseconds.  Where A runs on the
-// long-row batch-major kernel (4 waves, narrow codes) or on spmv_stream_kernel<2, 8>, C rides as extra workgroups of
+// long-row batch-major kernel (1, 2 or 4 waves, narrow codes) or on spmv_stream_kernel<2, 8>, C rides as extra workgroups of
 // that grid (PairC, kernels.hpp).  Same sums, same bits; one launch, timed as A's.
 
 // which PAIR instantiation spmv_launch_local's choice for A has: 1 batch-major, 2 stream, 0 none
 static int pair_form_A(alfd_ctx *ctx, const DevCsr &A) {
   if (!A.present || A.sparse || A.n_list == 0) return 0;
   if (A.vs.on && ctx->vs_enable && !ctx->vi_off)
-    return A.vs.L == 64 && !A.vs.wide && ctx->vs_NW == 4 && A.vs.nb > 0 && vs_lds_base_ok(ctx) ? 1 : 0;
+    return A.vs.L == 64 && !A.vs.wide && A.vs.NW <= 4 && A.vs.nb > 0 && vs_lds_base_ok(ctx) ? 1 : 0;
   if (A.win) return 0;
   return A.L == 64 && ctx->spmv_stream_R == 2 && ctx->spmv_stream_U == 8 && !ctx->spmv_nt ? 2 : 0;
 }
@@ -998,12 +1004,22 @@ static int launch_pair(alfd_ctx *ctx, int form, const DevCsr &A, int clsA, const
     const DevCsr::Vs &v = A.vs;
     const size_t lds = (size_t)VsFmt<0>::kWinOff + (size_t)v.maxW * sizeof(double);
     pc.nA = (uint32_t)v.nb;
-#define ALFD_VS_PAIR(TAG)                                                                                                  \
-  hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, true>), dim3(pc.nA + pc.nC), dim3(256), lds, ctx->stream, v.stream,    \
-                     v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0,            \
+    // the second party works in groups of 64 NW threads: as many workgroups as cover its rows once, grid-stride beyond
+    const int64_t rpb = 64 * v.NW / C.L;
+    pc.nC = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((C.n_list + rpb - 1) / rpb, 256 * 8));
+#define ALFD_VS_PAIR(TAG, NWV)                                                                                             \
+  hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, NWV, 0, true>), dim3(pc.nA + pc.nC), dim3(64 * NWV), lds, ctx->stream,       \
+                     v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0,  \
                      (const double *)nullptr, (double *)nullptr, ctx->vs_xcd, 0, pc)
-    if (A.tag == 0) ALFD_VS_PAIR(0);
-    else ALFD_VS_PAIR(1);
+#define ALFD_VS_PAIR_T(TAG)              \
+  do {                                   \
+    if (v.NW == 1) ALFD_VS_PAIR(TAG, 1); \
+    else if (v.NW == 2) ALFD_VS_PAIR(TAG, 2); \
+    else ALFD_VS_PAIR(TAG, 4);           \
+  } while (0)
+    if (A.tag == 0) ALFD_VS_PAIR_T(0);
+    else ALFD_VS_PAIR_T(1);
+#undef ALFD_VS_PAIR_T
 #undef ALFD_VS_PAIR
   } else {   // as launch_stream<2, 8, false>
     const int64_t nbatches = (A.nrows + 1) / 2;
@@ -3171,8 +3187,38 @@ static void plan_vss(int64_t nrows, int L, const int64_t *rp, const int32_t *col
   pl.ok = true;
 }
 
+// ---- row blocks of SMALL long-row operators ("batch_major_small").  A launch of spmv_vs_kernel is one
+// workgroup of NW waves per row block, and a wave walks its share of the block's batches one after another.  An operator
+// of a few ten thousand rows planned with the context-wide block (96 rows) gives a few hundred workgroups: most of the
+// chip's wave slots stay empty while every wave that does run works through a queue of batches.  The rule below shrinks
+// the block of such an operator until blocks x waves reaches HALF the resident wave slots of the device (4 of the 8
+// waves a SIMD holds) or every wave is down to one batch, whichever comes first.  Half, not all: every block pays its
+// frame (dictionary and x window into LDS) again, and in the sweep of profiles/small_operator_shapes the two patch
+// operators of the N = 74 system gain down to 56 % of the slots and lose beyond, while A_2, at 71 % with the default
+// block, loses at every smaller one.  The waves per workgroup stay: 4 beat 2 and 1 at every block size there.  It is a
+// function of the operator (rows, and blocks / batches of its default plan) and of the device (compute units) alone:
+// two setups of one problem plan the same blocks.  Results do not depend on the blocks (every row keeps its canonical sum).
+constexpr int kVsFillWavesPerCu = 16;   // 4 SIMDs x 4 of the 8 resident waves (amdgpu_waves_per_eu(8, 8))
+constexpr int kVsSmallMinRows = 16;     // never below one full shared batch
+static void vs_small_shape(int64_t nrows, int64_t blocks, int64_t batches, int rows, int waves, int cus, int *rows_out,
+                           int *waves_out) {
+  *rows_out = rows;
+  *waves_out = waves;
+  const int64_t slots = (int64_t)std::max(cus, 1) * kVsFillWavesPerCu;
+  if (nrows <= 0 || blocks <= 0 || batches <= 0 || blocks * waves >= slots) return;   // the default plan fills the chip
+  // whole 16-row shared batches: the floor -- one batch per wave, a block of `waves` batches holds waves * nrows /
+  // batches rows on average -- rounded up, the block that gives blocks x waves = slots rounded down (so that it does)
+  const int64_t floor_rows = ((nrows * waves + batches - 1) / batches + 15) / 16 * 16;
+  const int64_t fill_rows = (nrows * waves + slots - 1) / slots / 16 * 16;
+  const int64_t r = std::max<int64_t>(std::max(floor_rows, fill_rows), kVsSmallMinRows);
+  if (r < rows) *rows_out = (int)r;
+}
+
 static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const int32_t *col, const double *val) {
   VsPlan pl;
+  int RB = ctx->vs_RB, NW = ctx->vs_NW;
+  const bool forced = slot == kScratchSlot && ctx->vs_force_RB > 0;
+  if (forced) RB = ctx->vs_force_RB, NW = ctx->vs_force_NW;
   const int64_t nlc = (ctx->nranks > 1 && !m.rep) ? (int64_t)m.n_local_cols : -1;   // columns >= nlc are halo columns
   bool hint = slot >= 0 && slot < ALFD_NSLOTS && !ctx->rb_ptr[slot].empty();
   if (hint && ctx->rb_ptr[slot].back() != m.nrows) {
@@ -3196,24 +3242,43 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
     }
     for (size_t i = 0; good && i + 1 < bp.size(); ++i) good = bp[i] <= bp[i + 1];
     if (!good) return ctx->err = "alfd_set_row_blocks: the blocks are not a partition of the matrix rows", ALFD_E_INVALID;
-    plan_vs(m.nrows, rp, col, val, ctx->vs_RB, ctx->win_maxW, ctx->win_gap, (int64_t)bp.size() - 1, bp.data(),
+    plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, (int64_t)bp.size() - 1, bp.data(),
             br.data(), pl, ctx->vs_share != 0, 0, nlc);
   } else {
-    plan_vs(m.nrows, rp, col, val, ctx->vs_RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pl, ctx->vs_share != 0, 0, nlc);
+    plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pl, ctx->vs_share != 0, 0, nlc);
   }
   if (ctx->vs_wide && (!pl.ok || pl.dict_split)) {
     // blocks with more than 512 distinct values had to be halved (or the plan failed): the same blocks with 10-bit
     // codes and 11-bit window columns, kept if the stream gets smaller
     VsPlan pw;
     if (hint)
-      plan_vs(m.nrows, rp, col, val, ctx->vs_RB, ctx->win_maxW, ctx->win_gap, (int64_t)ctx->rb_ptr[slot].size() - 1,
+      plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, (int64_t)ctx->rb_ptr[slot].size() - 1,
               ctx->rb_ptr[slot].data(), ctx->rb_rows[slot].data(), pw, ctx->vs_share != 0, 1, nlc);
     else
-      plan_vs(m.nrows, rp, col, val, ctx->vs_RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pw, ctx->vs_share != 0, 1, nlc);
+      plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pw, ctx->vs_share != 0, 1, nlc);
     if (pw.ok && (!pl.ok || pw.stream.size() + 128 * (size_t)pw.nbatch < pl.stream.size() + 128 * (size_t)pl.nbatch)) pl = std::move(pw);
   }
   if (!pl.ok) return ALFD_OK;
+  bool small = false;
+  if (ctx->vs_small && !forced && !hint && slot == kScratchSlot && !pl.wide) {
+    // the library's own operators (multigrid levels, the interface patch; replicated ones on partitioned contexts
+    // included): re-planned ONCE at the shape of vs_small_shape when the default plan leaves the chip under-filled.
+    // Narrow codes only: the wide instantiations exist for 4 waves, and no level or patch operator needs them.
+    int rs = RB, ws = NW;
+    vs_small_shape(m.nrows, pl.nb, pl.nbatch, RB, NW, ctx->vs_cus, &rs, &ws);
+    if (rs != RB || ws != NW) {
+      VsPlan ps;
+      plan_vs(m.nrows, rp, col, val, rs, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, ps, ctx->vs_share != 0, 0, nlc);
+      if (ps.ok && !ps.dict_split) {
+        pl = std::move(ps);
+        RB = rs, NW = ws, small = true;
+      }
+    }
+  }
   DevCsr::Vs &v = m.vs;
+  v.RB = RB;
+  v.NW = pl.wide ? 4 : NW;
+  v.small = small;
   // block headers and the fixed-stride segment table (the kernel reads one segment past a block's last, and its first
   // round of 8 x 4 segments unconditionally; the descriptor table is read up to 16 batches past a block's last)
   int32_t max_nseg = 0;
@@ -6893,6 +6958,11 @@ int alfd_create(alfd_ctx_t *out, int device_id) {
   if (const char *e = std::getenv("ALFD_SPMV_VI_LEVELS")) ctx->vi_levels = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR")) ctx->vs_enable = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR_ROWS")) ctx->vs_RB = std::max(4, std::min(kVsMaxRows, std::atoi(e)));
+  if (const char *e = std::getenv("ALFD_SPMV_SMALL_SHAPES")) ctx->vs_small = std::atoi(e) != 0;
+  {
+    hipDeviceProp_t prop;
+    if (hipGetDeviceProperties(&prop, device_id) == hipSuccess) ctx->vs_cus = prop.multiProcessorCount;
+  }
   if (const char *e = std::getenv("ALFD_SPMV_VI_XCD")) ctx->vi_xcd = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_VI_BATCHED")) ctx->vi_batched = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_WINDOW_RB_VI")) ctx->win_RB_vi = std::atoi(e);
@@ -8408,6 +8478,116 @@ int alfd_host_window_plan(int64_t nrows, const int64_t *rp, const int32_t *col, 
   return ALFD_OK;
 }
 
+static void shape_of(const alfd_ctx *ctx, const DevCsr &m, alfd_batch_major_shape *out) {
+  std::memset(out, 0, sizeof(*out));
+  const bool on = m.vs.on && ctx->vs_enable, lng = on && m.vs.L == 64;
+  out->batch_major = on ? (m.vs.bricks ? 2 : 1) : 0;
+  out->lanes = m.L;
+  out->nrows = m.nrows;
+  out->nnz = m.nnz;
+  out->shared_nnz = m.vs.on ? m.vs.shared_nnz : 0;
+  out->rows = lng ? m.vs.RB : 0;
+  out->waves = lng ? (m.tag == 1 && m.vs.NW > 4 ? 4 : m.vs.NW) : 0;
+  out->small = lng && m.vs.small ? 1 : 0;
+  out->blocks = m.vs.on ? m.vs.nb : 0;
+  out->batches = m.vs.on ? m.vs.nbatch : 0;
+  out->compute_units = ctx->vs_cus;
+  out->lds_bytes = lng ? (int64_t)(m.vs.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + 8 * (int64_t)m.vs.maxW : 0;
+}
+
+int alfd_get_matrix_shape(alfd_ctx_t ctx, int slot, alfd_batch_major_shape *out) {
+  CHECK_CTX();
+  if (slot < 0 || slot >= ALFD_NSLOTS || !ctx->mat[slot].present || !out) return ALFD_E_INVALID;
+  shape_of(ctx, ctx->mat[slot], out);
+  return ALFD_OK;
+}
+
+// the operators the library builds for itself (alfd_operator): null when the context has none such
+static DevCsr *own_operator(alfd_ctx *ctx, int op, int level) {
+  DevCsr *m = nullptr;
+  if (op == ALFD_OPERATOR_LEVEL) {
+    std::vector<MlLevel> &ml = ctx->hier[0].ml;
+    if (level < 1 || level >= (int)ml.size()) return nullptr;
+    m = ml[level].rep.A.present ? &ml[level].rep.A : &ml[level].loc.A;
+  } else if (op == ALFD_OPERATOR_PATCH_SS || op == ALFD_OPERATOR_PATCH_S) {
+    if (!ctx->patch.on) return nullptr;
+    m = op == ALFD_OPERATOR_PATCH_SS ? &ctx->patch.Ass : &ctx->patch.As;
+  }
+  return m && m->present ? m : nullptr;
+}
+
+int alfd_get_operator_shape(alfd_ctx_t ctx, int op, int level, alfd_batch_major_shape *out) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  const DevCsr *m = own_operator(ctx, op, level);
+  if (!m || !out) return ALFD_E_INVALID;
+  shape_of(ctx, *m, out);
+  return ALFD_OK;
+}
+
+int alfd_host_small_shape(int64_t nrows, int64_t blocks, int64_t batches, int32_t rows, int32_t waves, int32_t compute_units,
+                          int32_t *rows_out, int32_t *waves_out) {
+  if (!rows_out || !waves_out || rows < 4 || rows > kVsMaxRows || waves < 1 || compute_units < 1) return ALFD_E_INVALID;
+  int r = rows, w = waves;
+  vs_small_shape(nrows, blocks, batches, rows, waves, compute_units, &r, &w);
+  *rows_out = r;
+  *waves_out = w;
+  return ALFD_OK;
+}
+
+int alfd_bench_operator(alfd_ctx_t ctx, int op, int level, int32_t rows, int32_t waves, int32_t reps, double *us_per_launch,
+                        alfd_batch_major_shape *info) {
+  CHECK_CTX();
+  CHECK_SETUP();
+  if (ctx->nranks > 1) return ALFD_E_UNSUPPORTED;
+  DevCsr *own = own_operator(ctx, op, level);
+  if (!own || reps < 1) return ALFD_E_INVALID;
+  if (rows != 0 && (rows < 4 || rows > kVsMaxRows || (waves != 1 && waves != 2 && waves != 4))) return ALFD_E_INVALID;
+  if (!own->vs.on || own->vs.L != 64 || own->sparse) return ctx->err = "not a long-row batch-major operator", ALFD_E_UNSUPPORTED;
+  DevCsr tmp;
+  struct Guard {
+    DevCsr &t;
+    ~Guard() { csr_free(t); }
+  } guard{tmp};
+  const DevCsr *m = own;
+  if (rows != 0) {   // the same operator planned once more at the given shape, beside the one the solver keeps
+    HostCsr h;
+    RC(download_csr(ctx, *own, h));
+    tmp.nrows = tmp.n_list = own->nrows, tmp.ncols = own->ncols, tmp.nnz = own->nnz;
+    tmp.L = 64, tmp.tag = own->tag, tmp.n_local_cols = own->n_local_cols, tmp.rep = own->rep;
+    ctx->vs_force_RB = rows, ctx->vs_force_NW = waves;
+    const int rc = build_vs(ctx, tmp, kScratchSlot, h.rp.data(), h.col.data(), h.val.data());
+    ctx->vs_force_RB = ctx->vs_force_NW = 0;
+    RC(rc);
+    if (!tmp.vs.on) return ctx->err = "the operator does not take the batch-major form at this shape", ALFD_E_UNSUPPORTED;
+    tmp.present = true;
+    m = &tmp;
+  }
+  double *dx = nullptr, *dy = nullptr;
+  HIPC(hipMalloc((void **)&dx, std::max<int64_t>(m->ncols, 1) * sizeof(double)));
+  HIPC(hipMalloc((void **)&dy, std::max<int64_t>(m->nrows, 1) * sizeof(double)));
+  hipLaunchKernelGGL(hash_vector_kernel, dim3((unsigned)std::max<int64_t>(1, (m->ncols + 255) / 256)), dim3(256), 0, ctx->stream,
+                     m->ncols, (int64_t)0, dx);
+  hipEvent_t a = nullptr, b = nullptr;
+  float ms = 0;
+  bool ok = hipEventCreate(&a) == hipSuccess && hipEventCreate(&b) == hipSuccess;
+  ok = ok && launch_vs(ctx, *m, dx, dy, 0, 0.0, nullptr, nullptr);   // warm-up
+  ok = ok && hipEventRecord(a, ctx->stream) == hipSuccess;
+  for (int i = 0; ok && i < reps; ++i) ok = launch_vs(ctx, *m, dx, dy, 0, 0.0, nullptr, nullptr);
+  ok = ok && hipEventRecord(b, ctx->stream) == hipSuccess && hipEventSynchronize(b) == hipSuccess &&
+       hipEventElapsedTime(&ms, a, b) == hipSuccess;
+  hipStreamSynchronize(ctx->stream);
+  if (a) hipEventDestroy(a);
+  if (b) hipEventDestroy(b);
+  hipFree(dx);
+  hipFree(dy);
+  HIPC(hipGetLastError());
+  if (!ok) return ctx->err = "alfd_bench_operator: launch or timing failed", ALFD_E_HIP;
+  if (us_per_launch) *us_per_launch = 1000.0 * (double)ms / reps;
+  if (info) shape_of(ctx, *m, info);
+  return ALFD_OK;
+}
+
 int alfd_get_matrix_info(alfd_ctx_t ctx, int slot, alfd_matrix_info *out) {
   CHECK_CTX();
   if (slot < 0 || slot >= ALFD_NSLOTS || !ctx->mat[slot].present || !out) return ALFD_E_INVALID;
@@ -8824,8 +9004,18 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
     return ALFD_OK;
   }
   if (std::strcmp(name, "batch_major_waves") == 0) {
-    if (value != 2 && value != 4 && value != 8) return ctx->err = "batch_major_waves: 2, 4 or 8", ALFD_E_INVALID;
+    if (value != 1 && value != 2 && value != 4 && value != 8) return ctx->err = "batch_major_waves: 1, 2, 4 or 8", ALFD_E_INVALID;
     ctx->vs_NW = value;
+    // the default of every operator whose shape the small-operator rule did not choose: the matrices of the slots follow
+    // at once (level and patch operators run their own 4-wave instantiations unless that rule shaped them)
+    for (int sl = 0; sl < ALFD_NSLOTS; ++sl) {
+      DevCsr::Vs &v = ctx->mat[sl].vs;
+      if (v.on && v.L == 64 && !v.small && !v.wide) v.NW = value;
+    }
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "batch_major_small") == 0) {   // 0: level / patch operators keep the context-wide shape (at the next alfd_set_matrix / alfd_setup)
+    ctx->vs_small = value != 0;
     return ALFD_OK;
   }
   if (std::strcmp(name, "batch_major_rows") == 0) {

@@ -208,15 +208,16 @@ __device__ __forceinline__ double block_reduce_256(double v, double *lds4) {
 //   EPI 3: y[r]  = s and y2[r] = d[r] * s        (C x kept for the constraint row too)
 // SPARSE: rows[] lists the non-empty rows, rp[] is indexed by list position.
 // Columns >= n_local read the halo buffer (multi-GPU row partition).
-// The body is shared with the second party of a pair launch (pair_rows below): workgroup `block` of `nblocks`.
-template <int L, int EPI, bool SPARSE>
+// The body is shared with the second party of a pair launch (pair_rows below): workgroup `block` of `nblocks`, of BLK
+// threads (a pair launch has the workgroup size of its first party).
+template <int L, int EPI, bool SPARSE, int BLK = kBlock>
 __device__ __forceinline__ void spmv_rows(int64_t block, int64_t nblocks, int64_t nrows,
                                           const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
                                           const double *__restrict__ val, const int32_t *__restrict__ rows,
                                           const double *__restrict__ x, const double *__restrict__ x_halo,
                                           int32_t n_local, double *__restrict__ y, double alpha,
                                           const double *__restrict__ d, double *__restrict__ y2) {
-  constexpr int RPB = kBlock / L;
+  constexpr int RPB = BLK / L;
   const int lane = threadIdx.x % L;
   const int sub = threadIdx.x / L;
   const int64_t ngroups = (nrows + RPB - 1) / RPB;
@@ -282,14 +283,16 @@ __device__ __forceinline__ uint32_t pair_nA(const NoPair &) { return gridDim.x; 
 __device__ __forceinline__ uint32_t pair_nA(const PairC &c) { return c.nA; }
 
 // the second party, or false: this workgroup belongs to the first
+template <int BLK = kBlock>
 __device__ __forceinline__ bool pair_rows(const NoPair &, const double *) { return false; }
+template <int BLK = kBlock>
 __device__ __forceinline__ bool pair_rows(const PairC &c, const double *__restrict__ x) {
   if (blockIdx.x < c.nA) return false;
   const int64_t block = blockIdx.x - c.nA;
   switch (c.L) {   // block-uniform
-    case 16: spmv_rows<16, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
-    case 32: spmv_rows<32, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
-    default: spmv_rows<64, 2, false>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+    case 16: spmv_rows<16, 2, false, BLK>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+    case 32: spmv_rows<32, 2, false, BLK>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
+    default: spmv_rows<64, 2, false, BLK>(block, c.nC, c.nrows, c.rp, c.col, c.val, nullptr, x, c.x_halo, c.n_local, c.t, 0.0, c.d, nullptr); break;
   }
   return true;
 }

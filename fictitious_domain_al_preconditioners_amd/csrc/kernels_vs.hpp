@@ -178,8 +178,8 @@ __device__ __forceinline__ void vs_shared(int32_t rem, const int32_t (&sh)[R], i
   }
 }
 
-// PAIR (NW = 4 only: the second party is written for 256 threads): the grid carries a second party behind its first nA
-// workgroups, pair_rows in kernels.hpp.  It owns no LDS, so the absolute LDS offsets of the first party stay right.
+// PAIR (NW = 1, 2 or 4: the second party takes its rows in groups of 64 NW threads): the grid carries a second party behind
+// its first nA workgroups, pair_rows in kernels.hpp.  It owns no LDS, so the absolute LDS offsets of the first party stay right.
 template <int EPI, int TAG, int NW, int WD = 0, bool PAIR = false>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmv_vs_kernel(
     const uint8_t *__restrict__ stream, const uint64_t *__restrict__ tab, int32_t stride,
@@ -187,8 +187,8 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     const double *__restrict__ dict, const double *__restrict__ x, const double *__restrict__ x_halo,
     int32_t n_local, double *__restrict__ y, double alpha, const double *__restrict__ d, double *__restrict__ y2,
     int xcd_remap, int32_t block_base, PairArg<PAIR> pc) {
-  static_assert(!PAIR || NW == 4, "the second party runs on kBlock threads");
-  if (pair_rows(pc, x)) return;
+  static_assert(!PAIR || NW <= 4, "the second party needs a lane group of 64 within 64 NW <= kBlock threads");
+  if (pair_rows<64 * NW>(pc, x)) return;
   extern __shared__ double xs[];
   char *sm = (char *)xs;
   double *ds = (double *)(sm + kVsDictOff);

@@ -44,6 +44,7 @@ ABI_SYMBOLS = [
     "alfd_host_strength_graph", "alfd_host_aggregate_graph", "alfd_build_strength_graph", "alfd_get_strength_graph",
     "alfd_upload_rhs_device", "alfd_download_solution_device", "alfd_solve_device", "alfd_precond_apply_device",
     "alfd_system_apply_device", "alfd_augment_rhs_device",
+    "alfd_get_matrix_shape", "alfd_get_operator_shape", "alfd_bench_operator", "alfd_host_small_shape",
 ]
 
 
@@ -114,6 +115,10 @@ def load_library():
         "alfd_get_setup_seconds": (C.c_int, [vp, vp]),
         "alfd_get_matrix_info": (C.c_int, [vp, C.c_int, C.POINTER(_abi.MatrixInfo)]),
         "alfd_bench_spmv_format": (C.c_int, [vp, C.c_int, i32, C.c_int, C.POINTER(dbl), C.POINTER(dbl)]),
+        "alfd_get_matrix_shape": (C.c_int, [vp, C.c_int, C.POINTER(_abi.BatchMajorShape)]),
+        "alfd_get_operator_shape": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(_abi.BatchMajorShape)]),
+        "alfd_bench_operator": (C.c_int, [vp, C.c_int, C.c_int, i32, i32, i32, C.POINTER(dbl), C.POINTER(_abi.BatchMajorShape)]),
+        "alfd_host_small_shape": (C.c_int, [i64, i64, i64, i32, i32, i32, C.POINTER(i32), C.POINTER(i32)]),
         "alfd_host_window_plan": (C.c_int, [i64, vp, vp, vp, i32, i32, C.POINTER(_abi.WindowPlanInfo)]),
         "alfd_set_tunable": (C.c_int, [vp, C.c_char_p, C.c_int]),
         "alfd_build_aggregates": (C.c_int, [vp, i32, dbl, i32, i64, i32, C.POINTER(i32)]),
@@ -646,9 +651,27 @@ class Context:
         return ms.value, nbytes.value
 
     def matrix_info(self, slot):
-        info = _abi.MatrixInfo()
+        """alfd_get_matrix_info, and the batch-major shape (alfd_get_matrix_shape) under batch_major_rows / _waves /
+        _small / _batches / _lds_bytes and nrows."""
+        info, shape = _abi.MatrixInfo(), _abi.BatchMajorShape()
         self._ck(self._lib.alfd_get_matrix_info(self._h, slot, C.byref(info)))
-        return {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+        self._ck(self._lib.alfd_get_matrix_shape(self._h, slot, C.byref(shape)))
+        out = {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+        out.update({k: v for k, v in shape.as_dict().items() if k not in out})
+        return out
+
+    def operator_info(self, op, level=0):
+        """The batch-major shape of an operator the library built at setup (alfd_get_operator_shape), keys as in
+        matrix_info: _abi.OPERATOR_LEVEL with level >= 1, _abi.OPERATOR_PATCH_SS, _abi.OPERATOR_PATCH_S."""
+        shape = _abi.BatchMajorShape()
+        self._ck(self._lib.alfd_get_operator_shape(self._h, op, level, C.byref(shape)))
+        return shape.as_dict()
+
+    def bench_operator(self, op, level=0, rows=0, waves=0, reps=200):
+        """(microseconds per launch, shape) of such an operator as it is (rows = 0) or re-planned at rows x waves."""
+        us, shape = C.c_double(), _abi.BatchMajorShape()
+        self._ck(self._lib.alfd_bench_operator(self._h, op, level, rows, waves, reps, C.byref(us), C.byref(shape)))
+        return us.value, shape.as_dict()
 
     def set_tunable(self, name, value):
         """Run-time switch (alfd_set_tunable), e.g. ("value_index", 0): general-matrix SpMV kernel."""

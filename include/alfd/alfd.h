@@ -705,6 +705,32 @@ typedef struct alfd_matrix_info {
                                         * before the halo exchange is started (the rest after it has arrived); else 0 */
 } alfd_matrix_info;
 int alfd_get_matrix_info(alfd_ctx_t ctx, int slot, alfd_matrix_info *out);
+/* The shape of a batch-major operator: what alfd_matrix_info has no room for.  rows / waves: rows per block the long-row
+ * form was planned with and waves per workgroup of its launches; small = 1 when the small-operator rule chose them
+ * (tunable "batch_major_small") and not the context-wide defaults; lds_bytes: dynamic LDS of one workgroup (dictionary
+ * + largest x window).  alfd_get_matrix_shape: a matrix slot.  alfd_get_operator_shape: the operators the library
+ * builds at alfd_setup -- A_l of level `level` >= 1 of the velocity hierarchy, A[S,S] / A[S,:] of the interface patch
+ * (level ignored); ALFD_E_INVALID when the context has no such operator. */
+typedef struct alfd_batch_major_shape {
+  int32_t batch_major, lanes;     /* as in alfd_matrix_info */
+  int64_t nrows, nnz, shared_nnz;
+  int64_t rows, waves, small;
+  int64_t blocks, batches, lds_bytes;
+  int64_t compute_units;          /* of the context's device: what the small-operator rule sizes against */
+} alfd_batch_major_shape;
+enum alfd_operator { ALFD_OPERATOR_LEVEL = 0, ALFD_OPERATOR_PATCH_SS = 1, ALFD_OPERATOR_PATCH_S = 2 };
+int alfd_get_matrix_shape(alfd_ctx_t ctx, int slot, alfd_batch_major_shape *out);
+int alfd_get_operator_shape(alfd_ctx_t ctx, int op, int level, alfd_batch_major_shape *out);
+/* Measurement hook (one rank): `reps` back-to-back y = A x launches of such an operator in its long-row batch-major form,
+ * timed with HIP events on the library's stream after one warm-up launch.  rows = 0: the operator as the solver holds
+ * it; rows in 4..250 and waves in {1, 2, 4}: a second copy planned at that shape for the call (the solver's stays as it
+ * is).  info, if not NULL, describes what was timed. */
+int alfd_bench_operator(alfd_ctx_t ctx, int op, int level, int32_t rows, int32_t waves, int32_t reps,
+                        double *us_per_launch, alfd_batch_major_shape *info);
+/* Host-only: the shape the small-operator rule gives an operator of nrows rows whose default plan (rows per block,
+ * waves per workgroup) has `blocks` blocks and `batches` batches, on a device of compute_units CUs. */
+int alfd_host_small_shape(int64_t nrows, int64_t blocks, int64_t batches, int32_t rows, int32_t waves,
+                          int32_t compute_units, int32_t *rows_out, int32_t *waves_out);
 /* Host-only (no device, no context): plans the LDS-window / value-indexed storage of
  * a CSR matrix exactly as alfd_set_matrix would (default tunables), decodes the plan
  * back -- window columns through the segment table, values through the block
@@ -789,12 +815,16 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  row) matrices whose rows are mostly translates of one another, use the batch-major forms of
  *                  csrc/kernels_vs.hpp (decided at alfd_set_matrix; also switches the kernel at launch); 0: the
  *                  round-1 window formats.  "batch_major_rows" (4..250, default 96): rows per block of the long-row
- *                  form when no alfd_set_row_blocks hint is given; "batch_major_waves" (2, 4, 8): waves per workgroup;
+ *                  form when no alfd_set_row_blocks hint is given; "batch_major_waves" (1, 2, 4, 8): waves per workgroup;
  *                  "batch_major_xcd" (0/1): XCD-contiguous block order (measured slower); "batch_major_share" (0/1):
  *                  store rows that are translates of one another once (0: every row stored, ~3.1 B/nnz -- what a
  *                  matrix with repeating values but no translate structure gets; at the next alfd_set_matrix);
  *                  "batch_major_wide" (0/1, default 1): blocks with more than 512 distinct values are re-planned with
  *                  10-bit codes / 11-bit window columns instead of being halved (cell-wise assembled matrices).
+ *                  "batch_major_small" (0/1; environment ALFD_SPMV_SMALL_SHAPES, read at alfd_create): 1: the level and
+ *                  patch operators the library builds whose default plan gives fewer blocks x waves than half the resident
+ *                  wave slots of the device (16 per compute unit) are planned with smaller row blocks, down to one batch
+ *                  per wave; 0: rows / waves above for every operator.  At the next alfd_setup.
  *   "nested_mp_host_stepped" (0/1, default 0): grad_div_in_A = 0, one rank: the nested CG on Mp inside Aug is
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
