@@ -4395,7 +4395,7 @@ static int dev_spgemm(alfd_ctx *ctx, int64_t nrows, const int64_t *arp, const in
                      counts, (const int64_t *)nullptr, (int32_t *)nullptr, (double *)nullptr, ovf);
   std::vector<int32_t> hc(nrows);
   int32_t hovf = 0;
-  HIPC(hipMemcpyAsync(hc.data(), counts, nrows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+  if (nrows) HIPC(hipMemcpyAsync(hc.data(), counts, nrows * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipMemcpyAsync(&hovf, ovf, sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
   if (hovf) {
@@ -5418,22 +5418,34 @@ static int upload_raw(alfd_ctx *ctx, const HostCsr &h, DevRawCsr &d) {
   return ALFD_OK;
 }
 
-// out = A * Pm with the device kernel when it fits, else on the host (both in the canonical order)
+// out = A * Pm with the device kernel whatever the size; on the host when a row does not fit (*on_device = false).
+// Both in the canonical order (alfd_sparse_product, and product() above its size gate).
+static int product_dev(alfd_ctx *ctx, const HostCsr &A, const HostCsr &Pm, HostCsr &out, bool *on_device) {
+  *on_device = false;
+  DevRawCsr dA, dP, dC;
+  RC(upload_raw(ctx, A, dA));
+  RC(upload_raw(ctx, Pm, dP));
+  bool fits = false;
+  const int rc = dev_spgemm(ctx, A.nrows, dA.rp, dA.col, dA.val, dP.rp, dP.col, dP.val, Pm.ncols, dC, &fits);
+  dA.release();
+  dP.release();
+  if (rc != ALFD_OK) return rc;
+  if (fits) {
+    const int rc2 = download_raw(ctx, dC, out);
+    dC.release();
+    *on_device = rc2 == ALFD_OK;
+    return rc2;
+  }
+  spgemm_host(A, Pm, out);
+  return ALFD_OK;
+}
+
+// out = A * Pm with the device kernel when the product is large enough to pay for the transfers and it fits, else on
+// the host (both in the canonical order)
 static int product(alfd_ctx *ctx, const HostCsr &A, const HostCsr &Pm, HostCsr &out) {
   if (ctx->ml_gpu_galerkin && A.nnz() > 200000) {
-    DevRawCsr dA, dP, dC;
-    RC(upload_raw(ctx, A, dA));
-    RC(upload_raw(ctx, Pm, dP));
-    bool fits = false;
-    const int rc = dev_spgemm(ctx, A.nrows, dA.rp, dA.col, dA.val, dP.rp, dP.col, dP.val, Pm.ncols, dC, &fits);
-    dA.release();
-    dP.release();
-    if (rc != ALFD_OK) return rc;
-    if (fits) {
-      const int rc2 = download_raw(ctx, dC, out);
-      dC.release();
-      return rc2;
-    }
+    bool on_device = false;
+    return product_dev(ctx, A, Pm, out, &on_device);
   }
   spgemm_host(A, Pm, out);
   return ALFD_OK;
@@ -5956,9 +5968,17 @@ static int rep_level0_products(alfd_ctx *ctx, const HostCsr &P0, const std::vect
     bool fits = false;
     RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, dP.rp, dP.col, dP.val, n1, dAP, &fits));
     dP.release();
-    if (!fits) return ctx->err = "partitioned Galerkin product: a row exceeds the device kernel's column set", ALFD_E_UNSUPPORTED;
-    RC(download_raw(ctx, dAP, AP_loc));
-    dAP.release();
+    if (fits) {
+      RC(download_raw(ctx, dAP, AP_loc));
+      dAP.release();
+    } else {
+      // a row with more than kSgMaxOut columns: this rank forms its rows on the host (same bits).  The product of a
+      // rank's rows is rank-local, so the peers may stay on the device; every rank goes on to the fetch_rows below.
+      HostCsr Al;
+      RC(download_csr(ctx, dA, Al));   // columns in the local space [owned | halo], the row order of PpA
+      Al.ncols = PpA.nrows;
+      spgemm_host(Al, PpA, AP_loc);
+    }
   }
   {
     std::vector<int64_t> want(dA.halo_globals.begin(), dA.halo_globals.end());
@@ -7426,6 +7446,30 @@ int alfd_get_aggregates_block(alfd_ctx_t ctx, int block, int level, int32_t *agg
   return ALFD_OK;
 }
 
+// One level's prolongator from its aggregates, d = diag(Aug) (sa_diag) and omega: the rows of sa_prolongator_dev, or
+// the host rows and the host truncation when a row has more candidates than the kernels hold (*on_device = false; same
+// bits).  sa_build_levels and alfd_smoothed_prolongator.
+static int sa_level_prolongator(alfd_ctx *ctx, const HostCsr &A, const SaPenalty &pen, const std::vector<int32_t> &agg,
+                                int64_t nc, const std::vector<double> &d, double omega, int bs, double tau, int cap,
+                                HostCsr &P, bool *on_device) {
+  std::vector<double> f;
+  HostCsr Q;
+  sa_factors(agg, d, omega, f);
+  RC(sa_penalty_rows(ctx, pen, agg, nc, Q));
+  bool fits = false;
+  RC(sa_prolongator_dev(ctx, A, agg, nc, f, Q, bs, tau, cap, P, &fits));
+  if (!fits) {
+    sa_rows_host(A, agg, nc, f, pen.on() ? &Q : nullptr, P);
+    if (tau != 0.0 || cap != 0) {
+      HostCsr T;
+      sa_truncate_host(P, agg, bs, tau, cap, T);
+      std::swap(P, T);
+    }
+  }
+  *on_device = fits;
+  return ALFD_OK;
+}
+
 struct SaParams {
   int32_t block_size, max_aggregate_nodes, cap, max_levels, its;
   double threshold, damping, tau, gamma;
@@ -7443,8 +7487,8 @@ static int sa_build_levels(alfd_ctx *ctx, alfd_ctx::Hierarchy &H, const SaParams
   const double threshold = sp.threshold, damping = sp.damping, tau = sp.tau, gamma = sp.gamma;
   const int64_t min_coarse = sp.min_coarse;
   const bool use_pen = sp.use_pen;
-  HostCsr An, Cn, Q, P, R, AP;
-  std::vector<double> d, f;
+  HostCsr An, Cn, P, R, AP;
+  std::vector<double> d;
   while (nlev < max_levels) {
     std::vector<int32_t> agg;
     int64_t nc = 0;
@@ -7460,19 +7504,8 @@ static int sa_build_levels(alfd_ctx *ctx, alfd_ctx::Hierarchy &H, const SaParams
                         " is not positive and finite (zero diagonal?)", ALFD_E_INVALID;
     }
     const double omega = damping / lam;
-    sa_factors(agg, d, omega, f);
-    RC(sa_penalty_rows(ctx, pen, agg, nc, Q));
-    bool fits = false;
-    RC(sa_prolongator_dev(ctx, A, agg, nc, f, Q, block_size, tau, cap, P, &fits));
-    if (!fits) {
-      sa_rows_host(A, agg, nc, f, use_pen ? &Q : nullptr, P);
-      if (tau != 0.0 || cap != 0) {
-        HostCsr T;
-        sa_truncate_host(P, agg, block_size, tau, cap, T);
-        std::swap(P, T);
-      }
-    }
-    Q = HostCsr();
+    bool on_device = false;
+    RC(sa_level_prolongator(ctx, A, pen, agg, nc, d, omega, block_size, tau, cap, P, &on_device));
     if (omega_out) omega_out[nlev] = omega;
     H.agg[nlev] = agg;
     H.P[nlev] = P;
@@ -7873,10 +7906,19 @@ int alfd_get_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t *ro
   return ALFD_OK;
 }
 
-int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
-                                   int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
-                                   const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
-                                   int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz) {
+// The operands of one level's prolongator from the caller's arrays (alfd_host_smoothed_prolongator,
+// alfd_smoothed_prolongator): A, Ct / C and the penalty view, the aggregates, d = diag(Aug) and its check.
+struct SaLevelInput {
+  HostCsr A, Ct, C;
+  SaPenalty pen;
+  std::vector<int32_t> agg;
+  std::vector<double> d;
+};
+
+static int sa_level_input(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val, int64_t n_mult,
+                          const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val, const double *w_inv,
+                          double gamma, const int32_t *agg, int64_t n_coarse, double omega, const int64_t *nnz,
+                          SaLevelInput &in) {
   if (nrows < 1 || !row_ptr || !col || !val || !agg || n_coarse < 1 || n_coarse > INT32_MAX || !nnz ||
       !std::isfinite(omega) || !std::isfinite(gamma) || row_ptr[0] != 0)
     return ALFD_E_INVALID;
@@ -7884,12 +7926,11 @@ int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const 
     if (row_ptr[i + 1] < row_ptr[i] || agg[i] < -1 || agg[i] >= n_coarse) return ALFD_E_INVALID;
   for (int64_t k = 0; k < row_ptr[nrows]; ++k)
     if (col[k] < 0 || col[k] >= nrows) return ALFD_E_INVALID;
-  HostCsr A, Ct, C, Q, P;
+  HostCsr &A = in.A, &Ct = in.Ct;
   A.nrows = A.ncols = nrows;
   A.rp.assign(row_ptr, row_ptr + nrows + 1);
   A.col.assign(col, col + A.rp[nrows]);
   A.val.assign(val, val + A.rp[nrows]);
-  SaPenalty pen;
   if (ct_row_ptr) {
     if (n_mult < 0 || !ct_col || !ct_val || !w_inv || ct_row_ptr[0] != 0) return ALFD_E_INVALID;
     for (int64_t i = 0; i < nrows; ++i)
@@ -7901,25 +7942,106 @@ int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const 
     Ct.rp.assign(ct_row_ptr, ct_row_ptr + nrows + 1);
     Ct.col.assign(ct_col, ct_col + Ct.rp[nrows]);
     Ct.val.assign(ct_val, ct_val + Ct.rp[nrows]);
-    transpose_host(Ct, C);
-    pen.Ct = &Ct, pen.C = &C, pen.w = w_inv, pen.gamma = gamma;
+    transpose_host(Ct, in.C);
+    in.pen.Ct = &in.Ct, in.pen.C = &in.C, in.pen.w = w_inv, in.pen.gamma = gamma;
   }
-  std::vector<int32_t> a(agg, agg + nrows);
-  std::vector<double> d, f;
-  sa_diag(A, pen, d);
+  in.agg.assign(agg, agg + nrows);
+  sa_diag(A, in.pen, in.d);
   for (int64_t i = 0; i < nrows; ++i)
-    if (a[i] >= 0 && !(d[i] != 0.0)) return ALFD_E_INVALID;
-  sa_factors(a, d, omega, f);
-  RC(sa_penalty_rows(nullptr, pen, a, n_coarse, Q));
-  sa_rows_host(A, a, n_coarse, f, pen.on() ? &Q : nullptr, P);
-  *nnz = P.nnz();
-  if (p_row_ptr) std::copy(P.rp.begin(), P.rp.end(), p_row_ptr);
-  if (p_col || p_val) {
-    if (capacity < P.nnz()) return ALFD_E_INVALID;
-    if (p_col) std::copy(P.col.begin(), P.col.end(), p_col);
-    if (p_val) std::copy(P.val.begin(), P.val.end(), p_val);
+    if (in.agg[i] >= 0 && !(in.d[i] != 0.0)) return ALFD_E_INVALID;
+  return ALFD_OK;
+}
+
+// the two-call protocol of the CSR results: sizes and the row pointer first, then the arrays with capacity
+static int csr_result(const HostCsr &M, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity, int64_t *nnz) {
+  *nnz = M.nnz();
+  if (row_ptr) std::copy(M.rp.begin(), M.rp.end(), row_ptr);
+  if (col || val) {
+    if (capacity < M.nnz()) return ALFD_E_INVALID;
+    if (col) std::copy(M.col.begin(), M.col.end(), col);
+    if (val) std::copy(M.val.begin(), M.val.end(), val);
   }
   return ALFD_OK;
+}
+
+int alfd_host_smoothed_prolongator(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                                   int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
+                                   const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
+                                   int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz) {
+  SaLevelInput in;
+  RC(sa_level_input(nrows, row_ptr, col, val, n_mult, ct_row_ptr, ct_col, ct_val, w_inv, gamma, agg, n_coarse, omega, nnz, in));
+  HostCsr Q, P;
+  std::vector<double> f;
+  sa_factors(in.agg, in.d, omega, f);
+  RC(sa_penalty_rows(nullptr, in.pen, in.agg, n_coarse, Q));
+  sa_rows_host(in.A, in.agg, n_coarse, f, in.pen.on() ? &Q : nullptr, P);
+  return csr_result(P, p_row_ptr, p_col, p_val, capacity, nnz);
+}
+
+int alfd_smoothed_prolongator(alfd_ctx_t ctx, int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                              int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
+                              const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
+                              int32_t block_size, double drop_tolerance, int32_t max_row_entries, int64_t *p_row_ptr,
+                              int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz, int32_t *on_device) {
+  CHECK_CTX();
+  if (block_size < 1 || !(drop_tolerance >= 0.0) || !(drop_tolerance < 1.0) || max_row_entries < 0)
+    return ctx->err = "alfd_smoothed_prolongator: bad block_size, drop_tolerance or max_row_entries", ALFD_E_INVALID;
+  SaLevelInput in;
+  if (sa_level_input(nrows, row_ptr, col, val, n_mult, ct_row_ptr, ct_col, ct_val, w_inv, gamma, agg, n_coarse, omega, nnz,
+                     in) != ALFD_OK)
+    return ctx->err = "alfd_smoothed_prolongator: bad arguments (shapes, column or aggregate ranges, a zero diagonal)",
+           ALFD_E_INVALID;
+  HostCsr P;
+  bool dev = false;
+  RC(sa_level_prolongator(ctx, in.A, in.pen, in.agg, n_coarse, in.d, omega, block_size, drop_tolerance, max_row_entries,
+                          P, &dev));
+  if (on_device) *on_device = dev ? 1 : 0;
+  return csr_result(P, p_row_ptr, p_col, p_val, capacity, nnz);
+}
+
+// a caller's CSR arrays as a HostCsr; false for a bad shape, row pointer or column
+static bool csr_input(int64_t nrows, int64_t ncols, const int64_t *row_ptr, const int32_t *col, const double *val,
+                      HostCsr &M) {
+  if (nrows < 0 || ncols < 0 || ncols > INT32_MAX || !row_ptr || row_ptr[0] != 0) return false;
+  for (int64_t i = 0; i < nrows; ++i)
+    if (row_ptr[i + 1] < row_ptr[i]) return false;
+  const int64_t nnz = row_ptr[nrows];
+  if (nnz > 0 && (!col || !val)) return false;
+  for (int64_t k = 0; k < nnz; ++k)
+    if (col[k] < 0 || col[k] >= ncols) return false;
+  M.nrows = nrows;
+  M.ncols = ncols;
+  M.rp.assign(row_ptr, row_ptr + nrows + 1);
+  M.col.assign(col, col + nnz);
+  M.val.assign(val, val + nnz);
+  return true;
+}
+
+int alfd_host_sparse_product(int64_t a_nrows, int64_t a_ncols, const int64_t *a_row_ptr, const int32_t *a_col,
+                             const double *a_val, int64_t p_ncols, const int64_t *p_row_ptr, const int32_t *p_col,
+                             const double *p_val, int64_t *out_row_ptr, int32_t *out_col, double *out_val,
+                             int64_t capacity, int64_t *nnz) {
+  HostCsr A, Pm, out;
+  if (!nnz || !csr_input(a_nrows, a_ncols, a_row_ptr, a_col, a_val, A) ||
+      !csr_input(a_ncols, p_ncols, p_row_ptr, p_col, p_val, Pm))
+    return ALFD_E_INVALID;
+  spgemm_host(A, Pm, out);
+  return csr_result(out, out_row_ptr, out_col, out_val, capacity, nnz);
+}
+
+int alfd_sparse_product(alfd_ctx_t ctx, int64_t a_nrows, int64_t a_ncols, const int64_t *a_row_ptr, const int32_t *a_col,
+                        const double *a_val, int64_t p_ncols, const int64_t *p_row_ptr, const int32_t *p_col,
+                        const double *p_val, int64_t *out_row_ptr, int32_t *out_col, double *out_val, int64_t capacity,
+                        int64_t *nnz, int32_t *on_device) {
+  CHECK_CTX();
+  HostCsr A, Pm, out;
+  if (!nnz || !csr_input(a_nrows, a_ncols, a_row_ptr, a_col, a_val, A) ||
+      !csr_input(a_ncols, p_ncols, p_row_ptr, p_col, p_val, Pm))
+    return ctx->err = "alfd_sparse_product: bad arguments (shapes, row pointers or column ranges)", ALFD_E_INVALID;
+  bool dev = false;
+  RC(product_dev(ctx, A, Pm, out, &dev));
+  if (on_device) *on_device = dev ? 1 : 0;
+  return csr_result(out, out_row_ptr, out_col, out_val, capacity, nnz);
 }
 
 int alfd_host_truncate_prolongator(int64_t nrows, int64_t n_coarse, const int64_t *p_row_ptr, const int32_t *p_col,
@@ -9029,6 +9151,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "ml_fuse") == 0) {   // 0: separate launches; 1: aug_tail; 2: + pair launches; 3: + on the fine level
     ctx->ml_fuse = std::max(0, std::min(3, value));   // as ALFD_ML_FUSE: values outside 0..3 take the nearest level
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "ml_gpu_galerkin") == 0) {   // 0: every Galerkin product of the setup / the builder on the host (next alfd_setup / build)
+    if (value != 0 && value != 1) return ctx->err = "ml_gpu_galerkin: 0 or 1", ALFD_E_INVALID;
+    ctx->ml_gpu_galerkin = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "ml_tail_rows") == 0) {   // 0: off; levels >= 1 of the immersed hierarchy up to this size in one launch

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "alfd_upload_rhs_device", "alfd_download_solution_device", "alfd_solve_device", "alfd_precond_apply_device",
     "alfd_system_apply_device", "alfd_augment_rhs_device",
     "alfd_get_matrix_shape", "alfd_get_operator_shape", "alfd_bench_operator", "alfd_host_small_shape",
+    "alfd_host_sparse_product", "alfd_sparse_product", "alfd_smoothed_prolongator",
 ]
 
 
@@ -133,6 +134,11 @@ def load_library():
                                            C.POINTER(i64)]),
         "alfd_host_smoothed_prolongator": (C.c_int, [i64, vp, vp, vp, i64, vp, vp, vp, vp, dbl, vp, i64, dbl,
                                                      vp, vp, vp, i64, C.POINTER(i64)]),
+        "alfd_host_sparse_product": (C.c_int, [i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64)]),
+        "alfd_sparse_product": (C.c_int, [vp, i64, i64, vp, vp, vp, i64, vp, vp, vp, vp, vp, vp, i64, C.POINTER(i64),
+                                          C.POINTER(i32)]),
+        "alfd_smoothed_prolongator": (C.c_int, [vp, i64, vp, vp, vp, i64, vp, vp, vp, vp, dbl, vp, i64, dbl, i32, dbl, i32,
+                                                vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i32)]),
         "alfd_comm_init_host": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp]),
         "alfd_get_device_memory": (C.c_int, [vp, C.POINTER(i64), C.POINTER(i64)]),
         "alfd_set_row_blocks": (C.c_int, [vp, C.c_int, i64, vp, vp]),
@@ -677,6 +683,27 @@ class Context:
         """Run-time switch (alfd_set_tunable), e.g. ("value_index", 0): general-matrix SpMV kernel."""
         self._ck(self._lib.alfd_set_tunable(self._h, name.encode(), int(value)))
 
+    def sparse_product(self, A, P):
+        """out = A P on the device whatever the size (alfd_sparse_product), with the bits of host_sparse_product; A, P
+        problems.Csr.  Returns (problems.Csr, on_device): on_device is False when a product row has more than 1024
+        distinct columns and the host routine formed the product."""
+        on = C.c_int32(-1)
+        out = _two_call_product(lambda *a: self._lib.alfd_sparse_product(self._h, *a, C.byref(on)), A, P, self._ck)
+        return out, bool(on.value)
+
+    def smoothed_prolongator(self, A, agg, n_coarse, omega, Ct=None, w_inv=None, gamma=0.0, block_size=1,
+                             drop_tolerance=0.0, max_row_entries=0):
+        """ONE level's smoothed prolongator from the caller's aggregates on the device (alfd_smoothed_prolongator), by
+        the routines of build_smoothed_aggregation: host_smoothed_prolongator's arguments and the truncation rule's.
+        Returns (problems.Csr, on_device): on_device is False when a row has more than 512 candidates and the host
+        routines formed the rows."""
+        on = C.c_int32(-1)
+        tail = (int(block_size), float(drop_tolerance), int(max_row_entries))
+        out = _two_call_prolongator(
+            lambda head, *res: self._lib.alfd_smoothed_prolongator(self._h, *head, *tail, *res, C.byref(on)),
+            A, agg, n_coarse, omega, Ct, w_inv, gamma, self._ck)
+        return out, bool(on.value)
+
     def set_row_blocks(self, slot, block_ptr, rows):
         """Row-block hint of the batch-major SpMV format (alfd_set_row_blocks); None removes it."""
         if block_ptr is None:
@@ -828,12 +855,10 @@ def host_aggregate_graph(graph, block_size=1, max_aggregate_nodes=8):
     return agg, int(nc.value)
 
 
-def host_smoothed_prolongator(A, agg, n_coarse, omega, Ct=None, w_inv=None, gamma=0.0):
-    """Host-only: ONE level's smoothed-aggregation prolongator P = P_tent - omega D^-1 (A + gamma Ct diag(w_inv) Ct^T)
-    P_tent with the library's arithmetic (alfd_host_smoothed_prolongator); A, Ct problems.Csr, agg from
-    host_aggregate_level / Context.build_smoothed_aggregation.  Ct None: A alone.  Returns a problems.Csr."""
+def _two_call_prolongator(fn, A, agg, n_coarse, omega, Ct, w_inv, gamma, check):
+    """The two calls of alfd_host_smoothed_prolongator / alfd_smoothed_prolongator: fn(head, p_row_ptr, p_col, p_val,
+    capacity, nnz) with head = the arguments the two share; check(rc) raises."""
     from .problems import Csr
-    lib = load_library()
     rp = np.ascontiguousarray(A.row_ptr, np.int64)
     col = np.ascontiguousarray(A.col, np.int32)
     val = np.ascontiguousarray(A.val, np.float64)
@@ -850,22 +875,63 @@ def host_smoothed_prolongator(A, agg, n_coarse, omega, Ct=None, w_inv=None, gamm
         pen = (int(Ct.ncols), crp.ctypes.data, ccol.ctypes.data, cval.ctypes.data, w.ctypes.data, float(gamma))
     else:
         pen = (0, None, None, None, None, 0.0)
+    head = (A.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, *pen, agg.ctypes.data, int(n_coarse), float(omega))
     prp = np.empty(A.nrows + 1, np.int64)
     nnz = C.c_int64(0)
-
-    def call(pc, pv, cap):
-        return lib.alfd_host_smoothed_prolongator(A.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, *pen,
-                                                  agg.ctypes.data, int(n_coarse), float(omega), prp.ctypes.data, pc,
-                                                  pv, cap, C.byref(nnz))
-    rc = call(None, None, 0)
-    if rc != _abi.OK:
-        raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
+    check(fn(head, prp.ctypes.data, None, None, 0, C.byref(nnz)))
     pcol = np.empty(nnz.value, np.int32)
     pval = np.empty(nnz.value, np.float64)
-    rc = call(pcol.ctypes.data, pval.ctypes.data, pcol.size)
-    if rc != _abi.OK:
-        raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
+    check(fn(head, prp.ctypes.data, pcol.ctypes.data, pval.ctypes.data, pcol.size, C.byref(nnz)))
     return Csr(int(A.nrows), int(n_coarse), prp, pcol, pval)
+
+
+def host_smoothed_prolongator(A, agg, n_coarse, omega, Ct=None, w_inv=None, gamma=0.0):
+    """Host-only: ONE level's smoothed-aggregation prolongator P = P_tent - omega D^-1 (A + gamma Ct diag(w_inv) Ct^T)
+    P_tent with the library's arithmetic (alfd_host_smoothed_prolongator); A, Ct problems.Csr, agg from
+    host_aggregate_level / Context.build_smoothed_aggregation.  Ct None: A alone.  Returns a problems.Csr."""
+    lib = load_library()
+
+    def check(rc):
+        if rc != _abi.OK:
+            raise AlfdError(rc, "alfd_host_smoothed_prolongator failed")
+    return _two_call_prolongator(lambda head, *res: lib.alfd_host_smoothed_prolongator(*head, *res), A, agg, n_coarse,
+                                 omega, Ct, w_inv, gamma, check)
+
+
+def _two_call_product(fn, A, P, check):
+    """The two calls of alfd_host_sparse_product / alfd_sparse_product: fn(operands..., out_row_ptr, out_col, out_val,
+    capacity, nnz); check(rc) raises."""
+    from .problems import Csr
+    if A.ncols != P.nrows:
+        raise ValueError("A has as many columns as P has rows")
+    arp = np.ascontiguousarray(A.row_ptr, np.int64)
+    acol = np.ascontiguousarray(A.col, np.int32)
+    aval = np.ascontiguousarray(A.val, np.float64)
+    prp = np.ascontiguousarray(P.row_ptr, np.int64)
+    pcol = np.ascontiguousarray(P.col, np.int32)
+    pval = np.ascontiguousarray(P.val, np.float64)
+    if arp.size != A.nrows + 1 or prp.size != P.nrows + 1 or acol.size != aval.size or pcol.size != pval.size:
+        raise ValueError("inconsistent CSR arrays")
+    ops = (int(A.nrows), int(A.ncols), arp.ctypes.data, acol.ctypes.data, aval.ctypes.data, int(P.ncols),
+           prp.ctypes.data, pcol.ctypes.data, pval.ctypes.data)
+    orp = np.empty(A.nrows + 1, np.int64)
+    nnz = C.c_int64(0)
+    check(fn(*ops, orp.ctypes.data, None, None, 0, C.byref(nnz)))
+    ocol = np.empty(nnz.value, np.int32)
+    oval = np.empty(nnz.value, np.float64)
+    check(fn(*ops, orp.ctypes.data, ocol.ctypes.data, oval.ctypes.data, ocol.size, C.byref(nnz)))
+    return Csr(int(A.nrows), int(P.ncols), orp, ocol, oval)
+
+
+def host_sparse_product(A, P):
+    """Host-only: out = A P with the library's arithmetic (alfd_host_sparse_product: one fma chain per entry, the rows
+    sorted by column, the pattern structural); A, P problems.Csr.  Returns a problems.Csr."""
+    lib = load_library()
+
+    def check(rc):
+        if rc != _abi.OK:
+            raise AlfdError(rc, "alfd_host_sparse_product failed")
+    return _two_call_product(lib.alfd_host_sparse_product, A, P, check)
 
 
 def host_truncate_prolongator(P, agg, block_size=1, drop_tolerance=0.0, max_row_entries=0):

@@ -418,7 +418,11 @@ int alfd_get_strength_graph(alfd_ctx_t ctx, double *d, int32_t *fixed, int64_t *
  * A rank group without alfd_set_partition has no rows to build from: ALFD_E_UNSUPPORTED, as before.
  * The offsets of block 0 must be multiples of block_size: ALFD_E_INVALID on every rank otherwise.  A failure on one
  * rank is returned by all of them, and a row with more than 512 candidates on any rank sends all ranks to the host
- * routines (same bits).  The context stays usable after an error. */
+ * routines (same bits).  The device product holds at most 1024 distinct columns per row of A P_l, P_l^T (A P_l) or
+ * C P_l: a wider row sends that product to the host routine (same bits).  On a partitioned context the level-0 product
+ * A_r P_0 of a rank's own rows is rank-local, so only the rank that holds the wide row forms it on the host while its
+ * peers stay on the device, and every rank goes on to the next collective; the replicated products fall back on all
+ * ranks alike.  The same holds at alfd_setup with CSR prolongators.  The context stays usable after an error. */
 int alfd_build_smoothed_aggregation(alfd_ctx_t ctx, int32_t block_size, double threshold, int32_t max_aggregate_nodes,
                                     double damping, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
                                     double *omega_out);
@@ -490,6 +494,43 @@ int alfd_host_truncate_prolongator(int64_t nrows, int64_t n_coarse, const int64_
                                    const double *p_val, const int32_t *agg, int32_t block_size, double drop_tolerance,
                                    int32_t max_row_entries, int64_t *out_row_ptr, int32_t *out_col, double *out_val,
                                    int64_t capacity, int64_t *nnz);
+/* Host-only (no device, no context): the sparse product out = A P of the multigrid setup (A P_l, P_l^T (A P_l), C P_l),
+ * A a_nrows x a_ncols and P a_ncols x p_ncols in CSR, rows in any order.  Canonical order: entry
+ * (i, J) is ONE sequential chain acc = fma(a_ik, p_kJ, acc) from 0 over the entries k of row i of A in CSR order and
+ * the entries of row col_k of P in CSR order; the pattern is structural (stored zeros count, an entry that cancels
+ * stays, as +0.0) and the rows come out with ascending columns.  Two calls as alfd_host_smoothed_prolongator:
+ * out_col == out_val == NULL returns *nnz (and out_row_ptr[a_nrows + 1] if given), then arrays with capacity >= nnz.
+ * a_nrows == 0 and operands without entries are valid.  ALFD_E_INVALID: a negative size, a row pointer that does not
+ * start at 0 or decreases, a column outside [0, a_ncols) / [0, p_ncols), nnz == NULL, capacity < nnz. */
+int alfd_host_sparse_product(int64_t a_nrows, int64_t a_ncols, const int64_t *a_row_ptr, const int32_t *a_col,
+                             const double *a_val, int64_t p_ncols, const int64_t *p_row_ptr, const int32_t *p_col,
+                             const double *p_val, int64_t *out_row_ptr, int32_t *out_col, double *out_val,
+                             int64_t capacity, int64_t *nnz);
+/* The same product on the context's device, whatever its size: both operands are uploaded and spgemm_rows_kernel forms
+ * the rows (one 64-lane workgroup per row), with the bits of alfd_host_sparse_product.  The kernel holds at most 1024
+ * distinct columns per product row; when ANY row has more, the whole product is formed by the host routine instead
+ * (same bits) and *on_device (may be NULL) is 0, else 1.  This is the product alfd_setup and the builders run for
+ * operators with more than 200 000 entries (tunable "ml_gpu_galerkin"); single-rank, not collective.  Same two-call
+ * protocol (each call forms the product) and the same ALFD_E_INVALID cases. */
+int alfd_sparse_product(alfd_ctx_t ctx, int64_t a_nrows, int64_t a_ncols, const int64_t *a_row_ptr, const int32_t *a_col,
+                        const double *a_val, int64_t p_ncols, const int64_t *p_row_ptr, const int32_t *p_col,
+                        const double *p_val, int64_t *out_row_ptr, int32_t *out_col, double *out_val, int64_t capacity,
+                        int64_t *nnz, int32_t *on_device);
+/* ONE level's smoothed prolongator from the caller's aggregates on the context's device, by the routines of
+ * alfd_build_smoothed_aggregation[_truncated]: the arguments of alfd_host_smoothed_prolongator, then block_size,
+ * drop_tolerance and max_row_entries of the truncation rule (0 and 0: nothing is truncated; the result then has the
+ * bits of alfd_host_smoothed_prolongator, otherwise those of alfd_host_truncate_prolongator applied to it).  The
+ * kernels hold at most 512 candidates (distinct aggregates of the row's columns, penalty columns and agg[i]) per row;
+ * when ANY row has more, all rows and the truncation are formed by the host routines instead (same bits) and
+ * *on_device (may be NULL) is 0, else 1.  Rows of A of any length stay on the device.  Single-rank, not collective;
+ * the hierarchy stored in the context is not touched.  Same two-call protocol (each call forms the rows).
+ * ALFD_E_INVALID as alfd_host_smoothed_prolongator (a zero diagonal in a row with an aggregate included), and for
+ * block_size < 1, drop_tolerance < 0, >= 1 or not finite, max_row_entries < 0. */
+int alfd_smoothed_prolongator(alfd_ctx_t ctx, int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                              int64_t n_mult, const int64_t *ct_row_ptr, const int32_t *ct_col, const double *ct_val,
+                              const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
+                              int32_t block_size, double drop_tolerance, int32_t max_row_entries, int64_t *p_row_ptr,
+                              int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz, int32_t *on_device);
 int alfd_configure(alfd_ctx_t ctx, const alfd_config *cfg);
 /* New stop rules for the following solves WITHOUT a new alfd_setup (alfd_configure invalidates the setup): the
  * reference's SolverControl objects are plain members that a caller may change between two solve() calls
@@ -843,6 +884,11 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  and in the environment (before the levels, every non-zero value meant 1).  The first step needs Ct in the plain
  *                  row-per-lane-group form, the second the forms alfd_spmv_pair names; partitioned contexts,
  *                  grad_div_in_A = 0, w_inverse != diagonal and aug_assembled always use the separate launches.
+ *   "ml_gpu_galerkin" (0/1, default 1; environment ALFD_ML_GPU_GALERKIN, read at alfd_create): the Galerkin products of
+ *                  alfd_setup with CSR prolongators and of the builders run on the device (alfd_sparse_product; inside
+ *                  the builders and on replicated levels only for operators with more than 200 000 entries).  0: all
+ *                  of them on the host.  Same bits either way; takes effect at the next alfd_setup / build.  The
+ *                  level-0 product of a partitioned context runs on the device at either value.
  *   "ml_tail_rows" (>= 0, default 0 = off): the levels l >= 1 of the block-1 (immersed) hierarchy from the first one
  *                  with at most this many unknowns down to the coarsest run their part of the V-cycle in ONE launch
  *                  (ml_tail_kernel: one workgroup, a barrier where the launches were) instead of 15-21 launches per
