@@ -36,6 +36,11 @@ INNER_THROW, INNER_ACCEPT = range(2)
 # enum alfd_timing_class
 T_SPMV_A, T_SPMV_OTHER, T_DOT, T_VEC = range(4)
 T_NCLASSES = 4
+# enum alfd_setup_count (alfd_get_setup_counts)
+SC_PRODUCTS_A, SC_PRODUCTS_C, SC_LEVEL_A_UPLOADS, SC_TRANSFER_UPLOADS, SC_PATCH_BUILDS, SC_POWER_ITERATIONS = range(6)
+SC_NCOUNTS = 6
+SETUP_COUNT_NAMES = ("products_a", "products_c", "level_a_uploads", "transfer_uploads", "patch_builds",
+                     "power_iterations")
 UNIQUE_ID_BYTES = 128
 
 

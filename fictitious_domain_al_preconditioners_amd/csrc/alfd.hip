@@ -283,6 +283,8 @@ struct alfd_ctx {
     int64_t ncoarse[ALFD_MAX_LEVELS] = {0, 0, 0, 0, 0, 0, 0, 0};
     HostCsr P[ALFD_MAX_LEVELS];                // CSR prolongator of a level (alfd_set_prolongator), replaces its aggregates
     DevCsr inv;                                // explicit inverse of the coarsest operator (alfd_config::ml_coarse_direct)
+    HostCsr coarse_A, coarse_C, coarse_Ct;     // host copies of the coarsest level of a CSR-prolongator hierarchy: what
+                                               // coarse_inverse reads (alfd_setup_coupling replaces the last two only)
     std::vector<MlLevel> ml;
     TailTable *tail_tab = nullptr;             // level descriptors of ml_tail_kernel (hierarchy 1; setup workspace)
     bool built_partitioned = false;            // made by alfd_build_smoothed_aggregation on a partitioned context:
@@ -358,6 +360,16 @@ struct alfd_ctx {
   double t_fbytes[ALFD_T_NCLASSES] = {0, 0, 0, 0};   // the same launches priced by format bytes
   double setup_s[ALFD_SETUP_NPHASES] = {0, 0, 0, 0, 0, 0, 0, 0};
   bool upload_since_setup = false;
+  // alfd_setup_coupling: what the last successful setup of either kind saw.  gen / dgen count the uploads per slot and
+  // diagonal; needs_full names an input (prolongator, aggregates, row-block hint) set since then, which only alfd_setup
+  // takes in; coupling_ready = 0 until an alfd_setup succeeds and again after a setup of either kind fails half way.
+  uint64_t gen[ALFD_NSLOTS + 1] = {}, gen_setup[ALFD_NSLOTS + 1] = {};
+  uint64_t dgen[ALFD_NDIAGS] = {}, dgen_setup[ALFD_NDIAGS] = {};
+  alfd_config cfg_setup;
+  const char *needs_full = nullptr;
+  bool coupling_ready = false;
+  int64_t setup_counts[ALFD_SC_NCOUNTS] = {};
+  std::vector<void *> cp_allocs[2];                    // the setup workspace that alfd_setup_coupling replaces, per hierarchy
   std::vector<void *> allocs;
   int spmv_stream_R = 2, spmv_stream_U = 8, spmv_nt = 0, spmv_grid_mult = 8;  // tunables (env ALFD_SPMV_*)
   int spmv_group_R = 4, spmv_group_U = 4;  // batch shape of the short-row window kernel
@@ -3569,13 +3581,22 @@ static int upload_transpose(alfd_ctx *ctx, int slot, int64_t nrows, int64_t ncol
 
 static int nblocks_of(int variant) { return variant == ALFD_AL2 || variant == ALFD_RATIONAL ? 2 : 3; }
 
-static int ws_alloc_zero(alfd_ctx *ctx, double **p, int64_t count) {
+static int ws_alloc_zero(alfd_ctx *ctx, double **p, int64_t count, std::vector<void *> *list = nullptr) {
   void *q = nullptr;
   HIPC(hipMalloc(&q, std::max<int64_t>(count, 1) * sizeof(double)));
-  ctx->ws_allocs.push_back(q);
+  (list ? *list : ctx->ws_allocs).push_back(q);
   *p = static_cast<double *>(q);
   HIPC(hipMemsetAsync(q, 0, std::max<int64_t>(count, 1) * sizeof(double), ctx->stream));
   return ALFD_OK;
+}
+// workspace whose size or content follows the coupling (the patch, the row masks, the tail table): released by both kinds
+// of setup, where ws_alloc_zero's is released by alfd_setup alone
+static int cp_alloc_zero(alfd_ctx *ctx, int h, double **p, int64_t count) {
+  return ws_alloc_zero(ctx, p, count, &ctx->cp_allocs[h]);
+}
+static void cp_release(alfd_ctx *ctx, int h) {
+  for (void *p : ctx->cp_allocs[h]) hipFree(p);
+  ctx->cp_allocs[h].clear();
 }
 
 // dinv = 1 / (diag(Adiag) + g * sum_k w_k R_ik^2): the diagonal of Adiag + g R diag(w) R^T
@@ -3632,6 +3653,7 @@ static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *
 template <class Apply>
 static int power_lambda(alfd_ctx *ctx, int64_t npad, const double *dinv, double *v, double *wv, Apply apply, double *lambda) {
   *lambda = 0;
+  ctx->setup_counts[ALFD_SC_POWER_ITERATIONS]++;
   for (int it = 0; it < ctx->cfg.cheb_power_its; ++it) {
     RC(dot_async(ctx, npad, v, v, S_TMP));
     RC(read_scalars(ctx, S_TMP, 1));
@@ -3691,19 +3713,37 @@ static int power_iteration(alfd_ctx *ctx, int op) {
 // Chebyshev post-smoothing of the residual; the coarsest level is "solved" by a
 // high-degree Chebyshev sweep.  Every piece is a fixed polynomial in SPD
 // operators, so the preconditioner is a fixed SPD operator and plain CG applies.
+// What of hierarchy h follows the coupling and the penalty: the coarsest inverse, the row masks, the tail table and (h = 0)
+// the interface patch, with the workspace they live in; with `operators` also C_l / Ct_l of the levels l >= 1.
+static void free_coupling(alfd_ctx *ctx, int h, bool operators) {
+  alfd_ctx::Hierarchy &H = ctx->hier[h];
+  for (MlLevel &L : H.ml) {
+    if (operators)
+      for (LevelStore *S : {&L.loc, &L.rep})
+        for (DevCsr *m : {&S->C, &S->Ct}) csr_free(*m);
+    L.tail_mask = nullptr;
+  }
+  H.tail_tab = nullptr;
+  csr_free(H.inv);
+  if (h == 0) {
+    for (DevCsr *m : {&ctx->patch.Ass, &ctx->patch.As, &ctx->patch.Ats, &ctx->patch.Cs, &ctx->patch.Cts, &ctx->patch.Cts_loc,
+                      &ctx->patch.Ctg})
+      csr_free(*m);
+    ctx->patch = alfd_ctx::Patch();
+  }
+  cp_release(ctx, h);
+}
+
 static void free_levels(alfd_ctx *ctx) {
-  for (alfd_ctx::Hierarchy &H : ctx->hier) {
+  for (int h = 0; h < 2; ++h) {
+    alfd_ctx::Hierarchy &H = ctx->hier[h];
+    free_coupling(ctx, h, true);
     for (MlLevel &L : H.ml)
       for (LevelStore *S : {&L.loc, &L.rep})
-        for (DevCsr *m : {&S->A, &S->C, &S->Ct, &S->P, &S->R}) csr_free(*m);
+        for (DevCsr *m : {&S->A, &S->P, &S->R}) csr_free(*m);
     H.ml.clear();
-    H.tail_tab = nullptr;   // setup workspace
-    csr_free(H.inv);
+    H.coarse_A = H.coarse_C = H.coarse_Ct = HostCsr();
   }
-  for (DevCsr *m : {&ctx->patch.Ass, &ctx->patch.As, &ctx->patch.Ats, &ctx->patch.Cs, &ctx->patch.Cts, &ctx->patch.Cts_loc,
-                    &ctx->patch.Ctg})
-    csr_free(*m);
-  ctx->patch = alfd_ctx::Patch();   // its vectors belong to the setup workspace
   ctx->ml_rep_level = -1;
 }
 
@@ -4061,12 +4101,12 @@ static int fused_correct(alfd_ctx *ctx, const AugOp &F, int degree, double ratio
   return cheb_fused(ctx, F, degree, ratio, t, zc, zout, true);
 }
 
-// the mask of aug_tail_kernel for the operator whose Ct is m (setup workspace: released with it)
-static int build_tail_mask(alfd_ctx *ctx, const DevCsr &m, int64_t npad, uint8_t **mask) {
+// the mask of aug_tail_kernel for the operator of hierarchy h whose Ct is m (coupling workspace: released with it)
+static int build_tail_mask(alfd_ctx *ctx, int h, const DevCsr &m, int64_t npad, uint8_t **mask) {
   *mask = nullptr;
   if (ctx->nranks > 1 || !m.present || npad == 0 || m.nrows > npad) return ALFD_OK;
   double *q = nullptr;
-  RC(ws_alloc_zero(ctx, &q, npad / 8));
+  RC(cp_alloc_zero(ctx, h, &q, npad / 8));
   *mask = reinterpret_cast<uint8_t *>(q);
   if (m.n_list > 0)
     hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((m.n_list + 255) / 256)), dim3(256), 0, ctx->stream, m.n_list,
@@ -4111,7 +4151,7 @@ static int build_tail_table(alfd_ctx *ctx) {
     for (int j = 1; j < F.degree && j <= kTailMaxDegree; ++j) k.step(F.c1[j - 1], F.c2[j - 1]);
   }
   double *q = nullptr;
-  RC(ws_alloc_zero(ctx, &q, (int64_t)((sizeof(TailTable) + 7) / 8)));
+  RC(cp_alloc_zero(ctx, 1, &q, (int64_t)((sizeof(TailTable) + 7) / 8)));
   H.tail_tab = reinterpret_cast<TailTable *>(q);
   HIPC(hipMemcpyAsync(H.tail_tab, &T, sizeof(TailTable), hipMemcpyHostToDevice, ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));   // T leaves scope
@@ -4533,18 +4573,19 @@ static int patch_setup(alfd_ctx *ctx, const HostCsr *A_full, const HostCsr &C, c
   Q.mpad = pad_chunk(m);
   void *q = nullptr;
   HIPC(hipMalloc(&q, m * sizeof(int32_t)));
-  ctx->ws_allocs.push_back(q);
+  ctx->cp_allocs[0].push_back(q);
   Q.S = static_cast<int32_t *>(q);
   HIPC(hipMemcpyAsync(Q.S, S.data(), m * sizeof(int32_t), hipMemcpyHostToDevice, ctx->stream));
-  for (double **v : {&Q.dinv, &Q.rS, &Q.zS, &Q.uS, &Q.eS, &Q.cd, &Q.cres, &Q.ctmp}) RC(ws_alloc_zero(ctx, v, Q.mpad));
-  RC(ws_alloc_zero(ctx, &Q.rr, pad_chunk(n)));
+  for (double **v : {&Q.dinv, &Q.rS, &Q.zS, &Q.uS, &Q.eS, &Q.cd, &Q.cres, &Q.ctmp}) RC(cp_alloc_zero(ctx, 0, v, Q.mpad));
+  RC(cp_alloc_zero(ctx, 0, &Q.rr, pad_chunk(n)));
   const unsigned gm = (unsigned)((m + 255) / 256);
   hipLaunchKernelGGL(gather_kernel, dim3(gm), dim3(256), 0, ctx->stream, m, Q.S, ctx->dinv_aug, Q.dinv);
   // lambda_max(D^-1 Aug_SS): power iteration from the integer-hash vector (patch-compact index)
   RC(aug_lambda_max(ctx, patch_aug(ctx), m, 0, Q.rS, Q.zS, &Q.lmax));
-  RC(build_tail_mask(ctx, Q.Cts, Q.mpad, &Q.tail_mask));
+  RC(build_tail_mask(ctx, 0, Q.Cts, Q.mpad, &Q.tail_mask));
   HIPC(hipStreamSynchronize(ctx->stream));
   Q.on = true;
+  ctx->setup_counts[ALFD_SC_PATCH_BUILDS]++;
   if (c.log_level > 0 && ctx->rank == 0)
     std::fprintf(stderr, "[alfd] interface patch: %lld rows, A[S,S] %lld nnz, %lld rows of A touch it, lambda_max %.3f\n",
                  (long long)m, (long long)Q.Ass.nnz, (long long)Trows.size(), Q.lmax);
@@ -6202,79 +6243,122 @@ static int ml_setup_rep_prolongators(alfd_ctx *ctx, int nlev) {
 // Vectors of level l of hierarchy h (n unknowns, the first of them the global index goff).  Level 0 takes 1 / diag and
 // lambda_max from its inner operator; a level below gets 1 / diag(Aug_l) and lambda_max(D^-1 Aug_l) by power iteration
 // from the integer-hash vector (global index) -- its operators are in place by then.
-static int level_init(alfd_ctx *ctx, int h, int l, int64_t n, int64_t goff) {
-  const alfd_config &c = ctx->cfg;
-  MlLevel &L = ctx->hier[h].ml[l];
-  LevelStore &S = L.loc;
+// The two halves: level_vectors allocates (sizes follow A and P alone), level_penalty fills what follows C, invW and the
+// penalty weight.  alfd_setup runs both, alfd_setup_coupling the second on the vectors it finds.
+static int level_vectors(alfd_ctx *ctx, int h, int l, int64_t n) {
+  LevelStore &S = ctx->hier[h].ml[l].loc;
   S.n = n;
   S.npad = pad_chunk(n);
   RC(store_vectors(ctx, S, true));
+  if (l > 0) RC(ws_alloc_zero(ctx, &S.dinv, S.npad));
+  return ALFD_OK;
+}
+static int level_penalty(alfd_ctx *ctx, int h, int l, int64_t goff) {
+  const alfd_config &c = ctx->cfg;
+  MlLevel &L = ctx->hier[h].ml[l];
+  LevelStore &S = L.loc;
   if (l == 0) {
     S.dinv = h == 0 ? ctx->dinv_aug : ctx->dinv_a22;
     L.lmax = ctx->lam_max[h == 0 ? OP_AUG : OP_A22];
     return ALFD_OK;
   }
   PhaseClock pc(ctx, ALFD_SETUP_ML_LAMBDA);
-  RC(ws_alloc_zero(ctx, &S.dinv, S.npad));
   const AugOp F = level_view(ctx, h, l).op;
-  RC(diag_plus_m(ctx, S.A, S.Ct, c.aug_assembled ? 0.0 : F.gamma, n, S.dinv));
-  return aug_lambda_max(ctx, F, n, goff, S.t, S.r, &L.lmax);
+  RC(diag_plus_m(ctx, S.A, S.Ct, c.aug_assembled ? 0.0 : F.gamma, S.n, S.dinv));
+  // the work vectors of the power iteration: zero after alfd_setup's allocation, whatever a solve left there otherwise
+  HIPC(hipMemsetAsync(S.t, 0, S.npad * sizeof(double), ctx->stream));
+  HIPC(hipMemsetAsync(S.r, 0, S.npad * sizeof(double), ctx->stream));
+  return aug_lambda_max(ctx, F, S.n, goff, S.t, S.r, &L.lmax);
 }
 
 // The next level Nx through a general CSR prolongator Pm (single rank): A_c = P^T (A P), C_c = C P, Ct_c = C_c^T from the
 // device operators dA, dC.  The three products run on the device (spgemm_rows_kernel; results fetched for the format
 // planner) when gpu_products allows and they fit, else on the host from hA / hC (null: fetched from the device here).
 // An, Cn, Ctn return the host copies of the new level.
-static int csr_level(alfd_ctx *ctx, const HostCsr &Pm, DevCsr &dA, DevCsr &dC, bool gpu_products, const HostCsr *hA,
-                     const HostCsr *hC, LevelStore &Nx, HostCsr &An, HostCsr &Cn, HostCsr &Ctn) {
+//
+// Two halves, each with its own fallback (the device and the host product have the same bits, so which of them ran
+// never shows): csr_level_A uploads P, R = P^T and A_c and depends on A and P alone; csr_level_C forms C_c and Ct_c
+// with the P that csr_level_A uploaded.  alfd_setup runs both, alfd_setup_coupling only the second.
+static int csr_level_A(alfd_ctx *ctx, const HostCsr &Pm, DevCsr &dA, bool gpu_products, const HostCsr *hA, LevelStore &Nx,
+                       HostCsr &An) {
   HostCsr R;
   {
     PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
     transpose_host(Pm, R);
     RC(upload_level_part(ctx, Nx.P, Pm, nullptr, true));
     RC(upload_level_part(ctx, Nx.R, R, nullptr, true));
+    ctx->setup_counts[ALFD_SC_TRANSFER_UPLOADS] += 2;
   }
   bool done = false;
-  if (gpu_products && !dA.sparse && !dC.sparse && !Nx.P.sparse && !Nx.R.sparse && dA.nnz > 0) {
+  if (gpu_products && !dA.sparse && !Nx.P.sparse && !Nx.R.sparse && dA.nnz > 0) {
     PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
-    DevRawCsr AP, RAP, CP;
-    bool f1 = false, f2 = false, f3 = false;
+    DevRawCsr AP, RAP;
+    bool f1 = false, f2 = false;
     RC(dev_spgemm(ctx, dA.nrows, dA.rp, dA.col, dA.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, AP, &f1));
     if (f1) RC(dev_spgemm(ctx, Nx.R.nrows, Nx.R.rp, Nx.R.col, Nx.R.val, AP.rp, AP.col, AP.val, Pm.ncols, RAP, &f2));
     AP.release();
-    if (f2) RC(dev_spgemm(ctx, dC.nrows, dC.rp, dC.col, dC.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, CP, &f3));
-    if (f3) {
+    if (f2) {
       RC(download_raw(ctx, RAP, An));
-      RC(download_raw(ctx, CP, Cn));
-      transpose_host(Cn, Ctn);
       done = true;
     }
     RAP.release();
-    CP.release();
   }
   if (!done) {
-    HostCsr fA, fC;
-    if (!hA || !hC) {
+    HostCsr fA;
+    if (!hA) {
       PhaseClock pc(ctx, ALFD_SETUP_ML_FETCH);
-      if (!hA) RC(download_csr(ctx, dA, fA));
-      if (!hC) RC(download_csr(ctx, dC, fC));
+      RC(download_csr(ctx, dA, fA));
     }
     PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
     HostCsr AP;
     spgemm_host(hA ? *hA : fA, Pm, AP);
     spgemm_host(R, AP, An);
-    AP = HostCsr();
-    spgemm_host(hC ? *hC : fC, Pm, Cn);
-    transpose_host(Cn, Ctn);
   }
+  ctx->setup_counts[ALFD_SC_PRODUCTS_A] += 2;
   PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
   RC(upload_level_part(ctx, Nx.A, An, nullptr, false));
+  ctx->setup_counts[ALFD_SC_LEVEL_A_UPLOADS]++;
+  return ALFD_OK;
+}
+
+static int csr_level_C(alfd_ctx *ctx, const HostCsr &Pm, DevCsr &dC, bool gpu_products, const HostCsr *hC, LevelStore &Nx,
+                       HostCsr &Cn, HostCsr &Ctn) {
+  bool done = false;
+  if (gpu_products && !dC.sparse && !Nx.P.sparse) {
+    PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
+    DevRawCsr CP;
+    bool f3 = false;
+    RC(dev_spgemm(ctx, dC.nrows, dC.rp, dC.col, dC.val, Nx.P.rp, Nx.P.col, Nx.P.val, Pm.ncols, CP, &f3));
+    if (f3) {
+      RC(download_raw(ctx, CP, Cn));
+      done = true;
+    }
+    CP.release();
+  }
+  if (!done) {
+    HostCsr fC;
+    if (!hC) {
+      PhaseClock pc(ctx, ALFD_SETUP_ML_FETCH);
+      RC(download_csr(ctx, dC, fC));
+    }
+    PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
+    spgemm_host(hC ? *hC : fC, Pm, Cn);
+  }
+  {
+    PhaseClock pc(ctx, ALFD_SETUP_ML_GALERKIN);
+    transpose_host(Cn, Ctn);
+  }
+  ctx->setup_counts[ALFD_SC_PRODUCTS_C]++;
+  PhaseClock pc(ctx, ALFD_SETUP_ML_UPLOAD);
   RC(upload_level_part(ctx, Nx.C, Cn, nullptr, false));
   RC(upload_level_part(ctx, Nx.Ct, Ctn, nullptr, false));
   return ALFD_OK;
 }
 
-static int ml_setup(alfd_ctx *ctx) {
+// full: alfd_setup, everything.  Otherwise alfd_setup_coupling on the hierarchy a full setup left (one rank, CSR
+// prolongators throughout; checked by the caller): A_l, P_l, R_l and the level vectors stay, the patch, the penalty
+// parts of every level and the coarsest inverse are redone, and with c_changed (CT or C uploaded) C_l and Ct_l as well.
+static int ml_setup(alfd_ctx *ctx, bool full, bool c_changed) {
   const alfd_config &c = ctx->cfg;
   ctx->dots_replicated = false;   // the Krylov dots reduce across ranks, whatever an earlier setup left behind
   if (c.ml_smooth_degree < 1 || c.ml_coarse_degree < 1 || !(c.ml_smooth_ratio > 1.0) || !(c.ml_coarse_ratio > 1.0))
@@ -6313,8 +6397,12 @@ static int ml_setup(alfd_ctx *ctx) {
     if ((isP ? ctx->hier[0].P[l].nrows : (int64_t)ctx->hier[0].agg[l].size()) != off[l][rk + 1] - off[l][rk])
       return ctx->err = "aggregates / prolongator of level " + std::to_string(l) + " do not match this rank's unknowns", ALFD_E_INVALID;
   }
-  free_levels(ctx);
-  ctx->hier[0].ml.assign(nlev + 1, MlLevel());
+  if (full) {
+    free_levels(ctx);
+    ctx->hier[0].ml.assign(nlev + 1, MlLevel());
+  } else {
+    free_coupling(ctx, 0, c_changed);
+  }
   // multi-rank: levels with few unknowns are replicated on every rank after the partitioned build
   // (their kernels take microseconds, their halo exchanges would dominate)
   int rep_from = -1;
@@ -6346,7 +6434,7 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(download_csr(ctx, ctx->mat[ALFD_CT], Ct));
   }
   const bool gpu_products = ctx->ml_gpu_galerkin && ctx->nranks == 1;
-  if (!gpu_products || ctx->hier[0].P[0].rp.empty()) RC(fetch_A(ctx->mat[ALFD_A]));
+  if (full && (!gpu_products || ctx->hier[0].P[0].rp.empty())) RC(fetch_A(ctx->mat[ALFD_A]));
   const int64_t lam0 = ctx->nranks > 1 ? ctx->part[last][rk] : 0;
   const int64_t lam_global = ctx->nranks > 1 ? ctx->part[last].back() : ctx->n[last];
   if (c.ml_patch_degree > 0) {
@@ -6356,17 +6444,20 @@ static int ml_setup(alfd_ctx *ctx) {
   for (int l = 0; l <= nlev; ++l) {
     LevelStore &L = ctx->hier[0].ml[l].loc;
     const int64_t n = off[l][rk + 1] - off[l][rk];
-    RC(level_init(ctx, 0, l, n, off[l][rk]));
+    if (full) RC(level_vectors(ctx, 0, l, n));
+    RC(level_penalty(ctx, 0, l, off[l][rk]));
     if (l == nlev) break;
     if (!ctx->hier[0].P[l].rp.empty()) {
       // ---- next level through a general CSR prolongator (single rank)
-      RC(csr_level(ctx, ctx->hier[0].P[l], l == 0 ? ctx->mat[ALFD_A] : L.A, l == 0 ? ctx->mat[ALFD_C] : L.C, gpu_products,
-                   have_host_A ? &A : nullptr, &C, ctx->hier[0].ml[l + 1].loc, An, Cn, Ctn));
+      LevelStore &Nx = ctx->hier[0].ml[l + 1].loc;
+      if (full)
+        RC(csr_level_A(ctx, ctx->hier[0].P[l], l == 0 ? ctx->mat[ALFD_A] : L.A, gpu_products, have_host_A ? &A : nullptr, Nx, An));
+      if (full || c_changed)
+        RC(csr_level_C(ctx, ctx->hier[0].P[l], l == 0 ? ctx->mat[ALFD_C] : L.C, gpu_products, &C, Nx, Cn, Ctn));
       if (l + 1 < nlev) {
-        A = std::move(An);      // host copies of the new level: the next level's fallback product, aggregation levels
-        have_host_A = true;
-        C = std::move(Cn);
-        Ct = std::move(Ctn);
+        // host copies of the new level: the next level's fallback product, aggregation levels
+        if (full) A = std::move(An), have_host_A = true;
+        if (full || c_changed) C = std::move(Cn), Ct = std::move(Ctn);
       }
       continue;
     }
@@ -6416,6 +6507,12 @@ static int ml_setup(alfd_ctx *ctx) {
     RC(upload_level_part(ctx, Nx.Ct, Ctn, ctx->nranks > 1 ? ctx->part[last].data() : nullptr, false));
     RC(upload_level_part(ctx, Nx.P, P, nullptr, true));
     RC(upload_level_part(ctx, Nx.R, R, nullptr, true));
+    // counted as the CSR-prolongator path counts: P^T (A P), formed by galerkin() in one pass, is two products with an
+    // A_l operand; C P is one with a C_l operand, and Ct_{l+1} = P^T Ct_l stands where that path transposes C_{l+1}
+    ctx->setup_counts[ALFD_SC_PRODUCTS_A] += 2;
+    ctx->setup_counts[ALFD_SC_PRODUCTS_C]++;
+    ctx->setup_counts[ALFD_SC_LEVEL_A_UPLOADS]++;
+    ctx->setup_counts[ALFD_SC_TRANSFER_UPLOADS] += 2;
     if (rep_from > 0 && l + 1 >= rep_from) {
       stash[l + 1].A = An;  // global column ids
       stash[l + 1].C = Cn;
@@ -6431,12 +6528,15 @@ static int ml_setup(alfd_ctx *ctx) {
     }
   }
   if (c.ml_coarse_direct > 0 && ctx->hier[0].ml[nlev].loc.n > 0 && ctx->hier[0].ml[nlev].loc.n <= c.ml_coarse_direct) {
-    // An / Cn / Ctn still hold the coarsest level (global = local column ids on one rank)
+    // An / Cn / Ctn still hold the coarsest level (global = local column ids on one rank): kept for alfd_setup_coupling
+    alfd_ctx::Hierarchy &H = ctx->hier[0];
+    if (full) H.coarse_A = std::move(An);
+    if (full || c_changed) H.coarse_C = std::move(Cn), H.coarse_Ct = std::move(Ctn);
     std::vector<double> w(ctx->n[last]);
     HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
-    RC(coarse_inverse(ctx, An, Cn, Ctn, w, c.gamma, ctx->hier[0].inv));
+    RC(coarse_inverse(ctx, H.coarse_A, H.coarse_C, H.coarse_Ct, w, c.gamma, H.inv));
   }
   if (rep_from > 0) {
     // ---- replicate levels rep_from .. nlev: gather operators, diagonals and W on every rank
@@ -6464,15 +6564,17 @@ static int ml_setup(alfd_ctx *ctx) {
     ctx->ml_rep_level = rep_from;
   }
   for (int l = 0; l <= nlev; ++l)
-    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].loc.Ct, ctx->hier[0].ml[l].loc.npad, &ctx->hier[0].ml[l].tail_mask));
+    RC(build_tail_mask(ctx, 0, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].loc.Ct, ctx->hier[0].ml[l].loc.npad, &ctx->hier[0].ml[l].tail_mask));
   return ALFD_OK;
 }
 
 // The second hierarchy (ALFD_PREC_MULTILEVEL on an elliptic variant): the V-cycle for A22 = A2 + gamma2 M invW M, built
-// from (A2, M, M, invW, gamma2) by the steps hierarchy 0 takes on (A, C, Ct, invW, gamma) -- level_init, csr_level, the
+// from (A2, M, M, invW, gamma2) by the steps hierarchy 0 takes on (A, C, Ct, invW, gamma) -- level_vectors / level_penalty,
+// csr_level_A / csr_level_C, the
 // explicit coarsest inverse, the masks of the fused smoother.  CSR prolongators, one rank, no interface patch (M touches
 // every row).  Without prolongators of block 1 there is no such hierarchy and A22 keeps the Chebyshev sweep.
-static int ml_setup_immersed(alfd_ctx *ctx) {
+// full / c_changed as in ml_setup, c_changed standing for an upload of M.
+static int ml_setup_immersed(alfd_ctx *ctx, bool full, bool c_changed) {
   const alfd_config &c = ctx->cfg;
   alfd_ctx::Hierarchy &H = ctx->hier[1];
   int nlev = 0;
@@ -6486,36 +6588,136 @@ static int ml_setup_immersed(alfd_ctx *ctx) {
     if (H.P[l].nrows != (l == 0 ? ctx->n[1] : H.P[l - 1].ncols))
       return ctx->err = "block-1 prolongator of level " + std::to_string(l) + " does not match the unknowns of that level",
              ALFD_E_INVALID;
-  H.ml.assign(nlev + 1, MlLevel());
+  if (full)
+    H.ml.assign(nlev + 1, MlLevel());
+  else
+    free_coupling(ctx, 1, c_changed);
   const bool gpu_products = ctx->ml_gpu_galerkin != 0;
   HostCsr An, Cn, Ctn, A, C;
   for (int l = 0; l <= nlev; ++l) {
     LevelStore &L = H.ml[l].loc;
-    RC(level_init(ctx, 1, l, l == 0 ? ctx->n[1] : H.ncoarse[l - 1], 0));
+    if (full) RC(level_vectors(ctx, 1, l, l == 0 ? ctx->n[1] : H.ncoarse[l - 1]));
+    RC(level_penalty(ctx, 1, l, 0));
     if (l == nlev) break;
-    RC(csr_level(ctx, H.P[l], l == 0 ? ctx->mat[ALFD_A2] : L.A, l == 0 ? ctx->mat[ALFD_M] : L.C, gpu_products,
-                 l == 0 ? nullptr : &A, l == 0 ? nullptr : &C, H.ml[l + 1].loc, An, Cn, Ctn));
+    LevelStore &Nx = H.ml[l + 1].loc;
+    if (full) RC(csr_level_A(ctx, H.P[l], l == 0 ? ctx->mat[ALFD_A2] : L.A, gpu_products, l == 0 ? nullptr : &A, Nx, An));
+    if (full || c_changed)
+      RC(csr_level_C(ctx, H.P[l], l == 0 ? ctx->mat[ALFD_M] : L.C, gpu_products, l == 0 ? nullptr : &C, Nx, Cn, Ctn));
     if (l + 1 < nlev) {
-      A = std::move(An);
-      C = std::move(Cn);
+      if (full) A = std::move(An);
+      if (full || c_changed) C = std::move(Cn);
     }
   }
   if (c.ml_coarse_direct > 0 && H.ml[nlev].loc.n <= c.ml_coarse_direct) {
+    if (full) H.coarse_A = std::move(An);
+    if (full || c_changed) H.coarse_C = std::move(Cn), H.coarse_Ct = std::move(Ctn);
     std::vector<double> w(ctx->n[2]);
     HIPC(hipMemcpyAsync(w.data(), ctx->diag[ALFD_INVW], w.size() * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     PhaseClock pc(ctx, ALFD_SETUP_ML_COARSE);
-    RC(coarse_inverse(ctx, An, Cn, Ctn, w, c.gamma2, H.inv));
+    RC(coarse_inverse(ctx, H.coarse_A, H.coarse_C, H.coarse_Ct, w, c.gamma2, H.inv));
   }
   for (int l = 0; l <= nlev; ++l)
-    RC(build_tail_mask(ctx, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].loc.Ct, H.ml[l].loc.npad, &H.ml[l].tail_mask));
+    RC(build_tail_mask(ctx, 1, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].loc.Ct, H.ml[l].loc.npad, &H.ml[l].tail_mask));
   return build_tail_table(ctx);
+}
+
+// 1 / diag(M) of the exact W^-1 into dinv_m (allocated, padding zero), from the host copy of slot M
+static int mass_diagonal(alfd_ctx *ctx) {
+  const HostCsr &M = ctx->h_M;
+  const int last = ctx->nblocks - 1;
+  if (!ctx->mat[ALFD_M].present || M.rp.empty() || M.nrows != ctx->n[last])
+    return ctx->err = "slot M (immersed mass matrix) must be set for the exact W^-1", ALFD_E_NOT_SETUP;
+  const int64_t nlp = pad_chunk(ctx->n[last]);
+  const int64_t row0 = ctx->nranks > 1 ? ctx->part[last][ctx->rank] : 0;
+  std::vector<double> dm(nlp, 0.0);
+  for (int64_t i = 0; i < M.nrows; ++i) {
+    double dii = 0.0;
+    for (int64_t k = M.rp[i]; k < M.rp[i + 1]; ++k)
+      if (M.col[k] == row0 + i) dii = M.val[k];
+    if (!(dii > 0.0)) return ctx->err = "mass matrix needs a positive diagonal", ALFD_E_INVALID;
+    dm[i] = 1.0 / dii;
+  }
+  HIPC(hipMemcpyAsync(ctx->dinv_m, dm.data(), nlp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return ALFD_OK;
+}
+
+// 1 / diag and lambda_max of the inner operators into the vectors setup() allocated: everything here follows the
+// coupling, invW or a penalty weight
+static int diag_lambda(alfd_ctx *ctx) {
+  const alfd_config &c = ctx->cfg;
+  const bool ell = is_elliptic(c.variant);
+  const bool gd_off = !c.grad_div_in_A && (c.variant == ALFD_AL_STOKES || c.variant == ALFD_AL_STOKES_DIAG);
+  const bool cheb = c.inner_prec == ALFD_PREC_CHEBYSHEV || c.inner_prec == ALFD_PREC_MULTILEVEL;
+  const int64_t n0p = pad_chunk(ctx->n[0]);
+  for (int k = 0; k < 7; ++k) ctx->lam_max[k] = 0;
+  // diag(Aug) = diag(A) + gamma sum_k w_k Ct_ik^2 (SURVEY.md a16; no product matrix is formed)
+  PhaseClock diag_clock(ctx, ALFD_SETUP_DIAG_LAMBDA);
+  if (gd_off) {
+    // d_i = fma(gamma_gd, sum_k l_k b_ki^2, fma(gamma, sum_k w_k c_ki^2, a_ii)), then 1 / d_i: the diagonal of the
+    // surrogate Aug the inner preconditioner sees (op_apply, exact_w = false); DESIGN section 4
+    RC(diag_plus_m(ctx, &ctx->mat[ALFD_A], ctx->mat[ALFD_CT], ctx->diag[ALFD_INVW], c.gamma, ctx->n[0], ctx->dA, false));
+    RC(diag_plus_m(ctx, nullptr, ctx->mat[ALFD_BT], ctx->diag[ALFD_MP_LUMPED_INV], c.gamma_grad_div, ctx->n[0],
+                   ctx->dinv_aug, true));
+  } else {
+    RC(diag_plus(ctx, ALFD_A, ALFD_CT, c.aug_assembled ? 0.0 : c.gamma, ctx->n[0], ctx->dinv_aug));
+  }
+  if (ell) {
+    // diag(A22_aug) = diag(A2) + gamma2 sum_k w_k M_ik^2
+    RC(diag_plus(ctx, ALFD_A2, ALFD_M, c.gamma2, ctx->n[1], ctx->dinv_a22));
+    if (c.variant == ALFD_AL_ELL_IDEAL) {
+      HIPC(hipMemcpyAsync(ctx->dinv_aug2, ctx->dinv_aug, n0p * sizeof(double), hipMemcpyDeviceToDevice,
+                          ctx->stream));
+      HIPC(hipMemcpyAsync(ctx->dinv_aug2 + ctx->off[1], ctx->dinv_a22, pad_chunk(ctx->n[1]) * sizeof(double),
+                          hipMemcpyDeviceToDevice, ctx->stream));
+      if (cheb) RC(power_iteration(ctx, OP_AUG2));
+    }
+    // the modified variant's two inner CGs; the ideal one's block-diagonal multilevel preconditioner smooths with them too
+    if (cheb && (c.variant == ALFD_AL_ELL_MODIFIED || c.inner_prec == ALFD_PREC_MULTILEVEL)) {
+      RC(power_iteration(ctx, OP_AUG));
+      RC(power_iteration(ctx, OP_A22));
+    }
+  } else if (cheb) {
+    RC(power_iteration(ctx, OP_AUG));
+  }
+  ctx->lambda_max = ctx->lam_max[c.variant == ALFD_AL_ELL_IDEAL ? OP_AUG2 : OP_AUG];
+  return ALFD_OK;
+}
+
+// The checks of gamma and gamma2 -- the two fields alfd_setup_coupling takes anew -- that both kinds of setup make:
+// parameter sanity the reference asserts (elliptic_interface.cc:874-884, 912-920).  Reads the context only.
+static int check_penalty_weights(alfd_ctx *ctx) {
+  const alfd_config &c = ctx->cfg;
+  if (c.variant == ALFD_AL_ELL_MODIFIED && c.gamma2 > 20.0)
+    return ctx->err = "gamma_AL_immersed is too large for modified AL preconditioner", ALFD_E_INVALID;
+  if (c.variant == ALFD_AL_ELL_MODIFIED && std::fabs(c.gamma2 - c.gamma) <= 1e-1)
+    return ctx->err = "modified AL preconditioner: gamma_1 and gamma_2 should not be too close", ALFD_E_INVALID;
+  if (c.variant == ALFD_AL_ELL_IDEAL && std::fabs(c.gamma - c.gamma2) >= 1e-12)
+    return ctx->err = "ideal AL preconditioner: gamma must be identical", ALFD_E_INVALID;
+  return ALFD_OK;
+}
+
+static void setup_begin(alfd_ctx *ctx) {
+  for (int ph = ALFD_SETUP_DIAG_LAMBDA; ph < ALFD_SETUP_NPHASES; ++ph) ctx->setup_s[ph] = 0.0;
+  for (int64_t &k : ctx->setup_counts) k = 0;
+  ctx->upload_since_setup = false;
+  ctx->is_setup = false;
+  ctx->coupling_ready = false;   // until this setup succeeds
+}
+// a setup of either kind succeeded: what alfd_setup_coupling compares the next call against
+static void setup_done(alfd_ctx *ctx, bool coupling_ready) {
+  std::copy(ctx->gen, ctx->gen + ALFD_NSLOTS + 1, ctx->gen_setup);
+  std::copy(ctx->dgen, ctx->dgen + ALFD_NDIAGS, ctx->dgen_setup);
+  ctx->cfg_setup = ctx->cfg;
+  ctx->needs_full = nullptr;
+  ctx->coupling_ready = coupling_ready;
+  ctx->is_setup = true;
 }
 
 static int setup(alfd_ctx *ctx) {
   if (!ctx->configured) return ctx->err = "alfd_configure not called", ALFD_E_NOT_SETUP;
-  for (int ph = ALFD_SETUP_DIAG_LAMBDA; ph < ALFD_SETUP_NPHASES; ++ph) ctx->setup_s[ph] = 0.0;
-  ctx->upload_since_setup = false;
+  setup_begin(ctx);
   const alfd_config &c = ctx->cfg;
   const bool rat = c.variant == ALFD_RATIONAL;
   if (rat && ctx->nranks > 1) return ctx->err = "rational variant is single-rank", ALFD_E_UNSUPPORTED;
@@ -6537,13 +6739,7 @@ static int setup(alfd_ctx *ctx) {
   if ((c.inner_prec == ALFD_PREC_CHEBYSHEV || c.inner_prec == ALFD_PREC_MULTILEVEL) &&
       (c.cheb_degree < 1 || c.cheb_power_its < 1 || !(c.cheb_eig_ratio > 1.0)))
     return ctx->err = "bad Chebyshev parameters", ALFD_E_INVALID;
-  // parameter sanity the reference asserts (elliptic_interface.cc:874-884, 912-920)
-  if (c.variant == ALFD_AL_ELL_MODIFIED && c.gamma2 > 20.0)
-    return ctx->err = "gamma_AL_immersed is too large for modified AL preconditioner", ALFD_E_INVALID;
-  if (c.variant == ALFD_AL_ELL_MODIFIED && std::fabs(c.gamma2 - c.gamma) <= 1e-1)
-    return ctx->err = "modified AL preconditioner: gamma_1 and gamma_2 should not be too close", ALFD_E_INVALID;
-  if (c.variant == ALFD_AL_ELL_IDEAL && std::fabs(c.gamma - c.gamma2) >= 1e-12)
-    return ctx->err = "ideal AL preconditioner: gamma must be identical", ALFD_E_INVALID;
+  RC(check_penalty_weights(ctx));
   ctx->nblocks = nblocks_of(c.variant);
   const int last = ctx->nblocks - 1;
   if (!ctx->mat[ALFD_A].present || !ctx->mat[ALFD_CT].present || !ctx->mat[ALFD_C].present ||
@@ -6637,24 +6833,11 @@ static int setup(alfd_ctx *ctx) {
     if (c.w_inverse != ALFD_W_MASS_INV_SQUARED && c.w_inverse != ALFD_W_MASS_INV)
       return ctx->err = "unknown alfd_config::w_inverse", ALFD_E_INVALID;
     if (rat) return ctx->err = "the rational variant has no W^-1", ALFD_E_UNSUPPORTED;
-    const HostCsr &M = ctx->h_M;
-    if (!ctx->mat[ALFD_M].present || M.rp.empty() || M.nrows != ctx->n[last])
-      return ctx->err = "slot M (immersed mass matrix) must be set for the exact W^-1", ALFD_E_NOT_SETUP;
     const int64_t nlp = pad_chunk(ctx->n[last]);
-    const int64_t row0 = ctx->nranks > 1 ? ctx->part[last][ctx->rank] : 0;
-    std::vector<double> dm(nlp, 0.0);
-    for (int64_t i = 0; i < M.nrows; ++i) {
-      double dii = 0.0;
-      for (int64_t k = M.rp[i]; k < M.rp[i + 1]; ++k)
-        if (M.col[k] == row0 + i) dii = M.val[k];
-      if (!(dii > 0.0)) return ctx->err = "mass matrix needs a positive diagonal", ALFD_E_INVALID;
-      dm[i] = 1.0 / dii;
-    }
     RC(ws_alloc_zero(ctx, &ctx->dinv_m, nlp));
-    HIPC(hipMemcpyAsync(ctx->dinv_m, dm.data(), nlp * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
-    HIPC(hipStreamSynchronize(ctx->stream));
     RC(ws_alloc_zero(ctx, &ctx->m_tmp, nlp));
     RC(ws_alloc_zero(ctx, &ctx->m_tmp2, nlp));
+    RC(mass_diagonal(ctx));
   }
   const bool cheb = c.inner_prec == ALFD_PREC_CHEBYSHEV || c.inner_prec == ALFD_PREC_MULTILEVEL;
   if (rat) {
@@ -6738,55 +6921,103 @@ static int setup(alfd_ctx *ctx) {
     HIPC(hipMemcpyAsync(ctx->rt_coef, coef, sizeof(coef), hipMemcpyHostToDevice, ctx->stream));
     HIPC(hipStreamSynchronize(ctx->stream));
     ctx->lambda_max = ctx->lam_max[OP_K];
-    ctx->is_setup = true;
+    setup_done(ctx, false);
     return ALFD_OK;
   }
-  // diag(Aug) = diag(A) + gamma sum_k w_k Ct_ik^2 (SURVEY.md a16; no product matrix is formed)
-  std::unique_ptr<PhaseClock> diag_clock(new PhaseClock(ctx, ALFD_SETUP_DIAG_LAMBDA));
   if (c.aug_assembled && is_elliptic(c.variant))
     return ctx->err = "aug_assembled (operator form) is implemented for the AL2 / Stokes variants", ALFD_E_UNSUPPORTED;
-  if (gd_off) {
-    // d_i = fma(gamma_gd, sum_k l_k b_ki^2, fma(gamma, sum_k w_k c_ki^2, a_ii)), then 1 / d_i: the diagonal of the
-    // surrogate Aug the inner preconditioner sees (op_apply, exact_w = false); DESIGN section 4
-    RC(diag_plus_m(ctx, &ctx->mat[ALFD_A], ctx->mat[ALFD_CT], ctx->diag[ALFD_INVW], c.gamma, ctx->n[0], ctx->dA, false));
-    RC(diag_plus_m(ctx, nullptr, ctx->mat[ALFD_BT], ctx->diag[ALFD_MP_LUMPED_INV], c.gamma_grad_div, ctx->n[0],
-                   ctx->dinv_aug, true));
-  } else {
-    RC(diag_plus(ctx, ALFD_A, ALFD_CT, c.aug_assembled ? 0.0 : c.gamma, ctx->n[0], ctx->dinv_aug));
-  }
   if (ell) {
-    // diag(A22_aug) = diag(A2) + gamma2 sum_k w_k M_ik^2
     RC(ws_alloc_zero(ctx, &ctx->dinv_a22, pad_chunk(ctx->n[1])));
-    RC(diag_plus(ctx, ALFD_A2, ALFD_M, c.gamma2, ctx->n[1], ctx->dinv_a22));
-    if (c.variant == ALFD_AL_ELL_IDEAL) {
-      RC(ws_alloc_zero(ctx, &ctx->dinv_aug2, ctx->off[2]));
-      HIPC(hipMemcpyAsync(ctx->dinv_aug2, ctx->dinv_aug, n0p * sizeof(double), hipMemcpyDeviceToDevice,
-                          ctx->stream));
-      HIPC(hipMemcpyAsync(ctx->dinv_aug2 + ctx->off[1], ctx->dinv_a22, pad_chunk(ctx->n[1]) * sizeof(double),
-                          hipMemcpyDeviceToDevice, ctx->stream));
-      if (cheb) RC(power_iteration(ctx, OP_AUG2));
-    }
-    // the modified variant's two inner CGs; the ideal one's block-diagonal multilevel preconditioner smooths with them too
-    if (cheb && (c.variant == ALFD_AL_ELL_MODIFIED || c.inner_prec == ALFD_PREC_MULTILEVEL)) {
-      RC(power_iteration(ctx, OP_AUG));
-      RC(power_iteration(ctx, OP_A22));
-    }
-  } else if (cheb) {
-    RC(power_iteration(ctx, OP_AUG));
+    if (c.variant == ALFD_AL_ELL_IDEAL) RC(ws_alloc_zero(ctx, &ctx->dinv_aug2, ctx->off[2]));
   }
-  ctx->lambda_max = ctx->lam_max[c.variant == ALFD_AL_ELL_IDEAL ? OP_AUG2 : OP_AUG];
-  diag_clock.reset();
+  RC(diag_lambda(ctx));
   free_levels(ctx);
   if (c.inner_prec == ALFD_PREC_MULTILEVEL) {
     if (c.variant == ALFD_AL_ELL_IDEAL &&
         (ctx->hier[1].P[0].rp.empty() || (ctx->hier[0].P[0].rp.empty() && ctx->hier[0].agg[0].empty())))
       return ctx->err = "multilevel inner preconditioner: the 2x2 block CG of the ideal variant needs a hierarchy on both "
                         "blocks (alfd_set_prolongator_block)", ALFD_E_UNSUPPORTED;
-    RC(ml_setup(ctx));
-    RC(ml_setup_immersed(ctx));
+    RC(ml_setup(ctx, true, true));
+    RC(ml_setup_immersed(ctx, true, true));
   }
   HIPC(hipStreamSynchronize(ctx->stream));
-  ctx->is_setup = true;
+  setup_done(ctx, true);
+  return ALFD_OK;
+}
+
+// Do two configs differ in more than gamma, gamma2 and the stop rules of alfd_set_controls?
+// alfd_config has no padding (the sum of its members, checked below), so comparing the bytes compares the fields
+static_assert(sizeof(alfd_config) == 18 * sizeof(int32_t) + 9 * sizeof(double) + 5 * sizeof(alfd_control) &&
+                  sizeof(alfd_control) == 2 * sizeof(int32_t) + 2 * sizeof(double),
+              "alfd_config gained padding or a member: config_needs_setup compares its bytes");
+static bool config_needs_setup(const alfd_config &now, const alfd_config &then) {
+  alfd_config a = now;
+  a.gamma = then.gamma, a.gamma2 = then.gamma2;
+  a.outer = then.outer, a.inner = then.inner, a.mp_inner = then.mp_inner;
+  return std::memcmp(&a, &then, sizeof(alfd_config)) != 0;
+}
+
+// alfd_setup_coupling: the coupling halves of setup() on the context a setup left.  Everything up to setup_begin only
+// reads the context.
+static int setup_coupling(alfd_ctx *ctx) {
+  const alfd_config &c = ctx->cfg;
+  const std::string fn = "alfd_setup_coupling: ";
+  // the same answer on every rank, before any exchange
+  if (ctx->nranks > 1) return ctx->err = fn + "partitioned contexts keep using alfd_setup", ALFD_E_UNSUPPORTED;
+  if (ctx->configured && c.variant == ALFD_RATIONAL)
+    return ctx->err = fn + "the rational variant keeps using alfd_setup", ALFD_E_UNSUPPORTED;
+  if (!ctx->configured || !ctx->coupling_ready)
+    return ctx->err = fn + "the context was never set up (alfd_setup first)", ALFD_E_NOT_SETUP;
+  const bool ml = c.inner_prec == ALFD_PREC_MULTILEVEL;
+  if (ctx->needs_full) return ctx->err = fn + ctx->needs_full + " since the last setup: needs alfd_setup", ALFD_E_INVALID;
+  if (config_needs_setup(c, ctx->cfg_setup))
+    return ctx->err = fn + "the configuration differs in more than gamma, gamma2 and the controls: needs alfd_setup",
+           ALFD_E_INVALID;
+  if (c.aug_assembled)
+    return ctx->err = fn + "aug_assembled = 1 keeps the coupling inside A: needs alfd_setup", ALFD_E_INVALID;
+  RC(check_penalty_weights(ctx));   // a gamma / gamma2 that alfd_setup refuses is refused here, with its message
+  for (int s = 0; s < ALFD_NSLOTS; ++s)
+    if (s != ALFD_CT && s != ALFD_C && s != ALFD_M && ctx->gen[s] != ctx->gen_setup[s])
+      return ctx->err = fn + "matrix slot " + std::to_string(s) + " was uploaded since the last setup: needs alfd_setup",
+             ALFD_E_INVALID;
+  for (int s = 0; s < ALFD_NDIAGS; ++s)
+    if (s != ALFD_INVW && ctx->dgen[s] != ctx->dgen_setup[s])
+      return ctx->err = fn + "diagonal " + std::to_string(s) + " was uploaded since the last setup: needs alfd_setup",
+             ALFD_E_INVALID;
+  const int last = ctx->nblocks - 1;
+  const DevCsr &Ct = ctx->mat[ALFD_CT], &C = ctx->mat[ALFD_C], &M = ctx->mat[ALFD_M];
+  const bool uses_M = is_elliptic(c.variant) || c.w_inverse != ALFD_W_DIAGONAL;
+  if (Ct.nrows != ctx->n[0] || Ct.ncols != ctx->n[last] || C.nrows != ctx->n[last] || C.ncols != ctx->n[0] ||
+      ctx->diag_n[ALFD_INVW] != ctx->n[last] ||
+      (uses_M && (!M.present || M.nrows != ctx->n[last] || M.ncols != ctx->n[last] || ctx->h_M.nrows != ctx->n[last])))
+    return ctx->err = fn + "a block size changed: needs alfd_setup", ALFD_E_INVALID;
+  if (ml) {
+    int nlev = 0;
+    while (nlev < ALFD_MAX_LEVELS && (!ctx->hier[0].agg[nlev].empty() || !ctx->hier[0].P[nlev].rp.empty())) {
+      if (ctx->hier[0].P[nlev].rp.empty())
+        return ctx->err = fn + "a hierarchy given as aggregates keeps using alfd_setup", ALFD_E_UNSUPPORTED;
+      ++nlev;
+    }
+    if ((int)ctx->hier[0].ml.size() != nlev + 1)
+      return ctx->err = fn + "the hierarchy is not the one of the last setup: needs alfd_setup", ALFD_E_INVALID;
+  }
+  const bool c_changed = ctx->gen[ALFD_CT] != ctx->gen_setup[ALFD_CT] || ctx->gen[ALFD_C] != ctx->gen_setup[ALFD_C];
+  const bool m_changed = ctx->gen[ALFD_M] != ctx->gen_setup[ALFD_M];
+  // hierarchy 1 reads (A2, M, M, invW, gamma2): untouched when none of the last three changed
+  const bool h1_changed = m_changed || ctx->dgen[ALFD_INVW] != ctx->dgen_setup[ALFD_INVW] || c.gamma2 != ctx->cfg_setup.gamma2;
+  // ---- from here on the context changes; a failure leaves it to alfd_setup
+  setup_begin(ctx);
+  HIPC(hipStreamSynchronize(ctx->stream));
+  spectrum_release(ctx);   // may point into the patch
+  ctx->n_owner = NESTED_FREE;
+  if (c.w_inverse != ALFD_W_DIAGONAL) RC(mass_diagonal(ctx));
+  RC(diag_lambda(ctx));
+  if (ml) {
+    RC(ml_setup(ctx, false, c_changed));
+    if (h1_changed && !ctx->hier[1].ml.empty()) RC(ml_setup_immersed(ctx, false, m_changed));
+  }
+  HIPC(hipStreamSynchronize(ctx->stream));
+  setup_done(ctx, true);
   return ALFD_OK;
 }
 
@@ -6915,6 +7146,12 @@ static void fill_result(alfd_ctx *ctx, alfd_result *res, int status) {
 }
 
 }  // namespace alfd
+
+// an input that only alfd_setup takes in was set: alfd_setup_coupling refuses until then
+static void hierarchy_input_changed(alfd_ctx *ctx) {
+  ctx->is_setup = false;
+  ctx->needs_full = "a prolongator, aggregates or a row-block hint was set";
+}
 
 // =================================================================== C ABI
 #define CHECK_CTX()                       \
@@ -7114,6 +7351,7 @@ int alfd_set_matrix(alfd_ctx_t ctx, int slot, int64_t nrows, int64_t ncols, cons
   for (int64_t k = 0; k < nnz; ++k)
     if (col[k] < 0 || col[k] >= ncols) return ctx->err = "column index out of range", ALFD_E_INVALID;
   ctx->is_setup = false;
+  ctx->gen[slot]++;
   if (ctx->nranks > 1 && ctx->nblocks == 0)
     return ctx->err = "alfd_set_partition must precede alfd_set_matrix", ALFD_E_INVALID;
   if (!ctx->upload_since_setup) ctx->setup_s[ALFD_SETUP_UPLOAD] = 0.0, ctx->upload_since_setup = true;
@@ -7157,6 +7395,7 @@ int alfd_set_diag(alfd_ctx_t ctx, int slot, int64_t n, const double *d) {
   CHECK_CTX();
   if (slot < 0 || slot >= ALFD_NDIAGS || n < 0 || (n > 0 && !d)) return ALFD_E_INVALID;
   ctx->is_setup = false;
+  ctx->dgen[slot]++;
   if (ctx->diag[slot]) {
     ctx->allocs.erase(std::remove(ctx->allocs.begin(), ctx->allocs.end(), (void *)ctx->diag[slot]), ctx->allocs.end());
     hipFree(ctx->diag[slot]);
@@ -7217,7 +7456,7 @@ int alfd_set_aggregates(alfd_ctx_t ctx, int level, int64_t n_fine, const int32_t
   ctx->hier[0].P[level] = HostCsr();
   ctx->hier[0].built_partitioned = false;
   for (int l = level + 1; l < ALFD_MAX_LEVELS; ++l) ctx->hier[0].agg[l].clear(), ctx->hier[0].wgt[l].clear(), ctx->hier[0].P[l] = HostCsr();
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   return ALFD_OK;
 }
 
@@ -7260,7 +7499,7 @@ int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_f
     H.agg[l].clear();
     H.P[l] = HostCsr();
   }
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   return ALFD_OK;
 }
 
@@ -7273,7 +7512,7 @@ int alfd_clear_hierarchy(alfd_ctx_t ctx, int block) {
   CHECK_CTX();
   if (block != 0 && block != 1) return ctx->err = "multigrid hierarchy: block must be 0 or 1", ALFD_E_INVALID;
   ctx->hier[block].clear_input();
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   return ALFD_OK;
 }
 
@@ -7311,7 +7550,7 @@ int alfd_build_aggregates(alfd_ctx_t ctx, int32_t block_size, double threshold, 
   }
   if (nlev == 0) return ctx->err = "algebraic aggregation found nothing to coarsen", ALFD_E_INVALID;
   if (levels_out) *levels_out = nlev;
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   return ALFD_OK;
 }
 
@@ -7570,7 +7809,7 @@ static int build_sa_partitioned(alfd_ctx *ctx, SaParams sp, int32_t *levels_out,
     return ctx->err = "alfd_build_smoothed_aggregation: Ct, C and W^-1 must be uploaded on every rank or on none", ALFD_E_INVALID;
   sp.use_pen = have;
   H.clear_input();
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   *touched = true;
   // ---- aggregates: device graph rows, gathered; greedy passes on every rank
   RC(strength_graph_dev(ctx, bs, sp.threshold));
@@ -7815,7 +8054,7 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_s
     return ctx->err = "alfd_build_smoothed_aggregation: bad arguments", ALFD_E_INVALID;
   if (!(tau >= 0.0) || !(tau < 1.0) || cap < 0) {
     H.clear_input();
-    ctx->is_setup = false;
+    hierarchy_input_changed(ctx);
     return ctx->err = "alfd_build_smoothed_aggregation_truncated: drop_tolerance must be in [0, 1), max_row_entries >= 0",
            ALFD_E_INVALID;
   }
@@ -7852,7 +8091,7 @@ static int build_smoothed_aggregation(alfd_ctx_t ctx, int block, int32_t block_s
     transpose_host(Ct, C);
   }
   H.clear_input();
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   int nlev = 0;
   const SaParams sp{block_size, max_aggregate_nodes, cap, max_levels, its, threshold, damping, tau, gamma, min_coarse, use_pen};
   RC(sa_build_levels(ctx, H, sp, A, C, Ct, w, nlev, omega_out));
@@ -8081,7 +8320,7 @@ int alfd_set_aggregate_partition(alfd_ctx_t ctx, int level, const int64_t *coars
   CHECK_CTX();
   if (level < 0 || level >= ALFD_MAX_LEVELS || !coarse_offsets) return ALFD_E_INVALID;
   ctx->ml_coff[level].assign(coarse_offsets, coarse_offsets + ctx->nranks + 1);
-  ctx->is_setup = false;
+  hierarchy_input_changed(ctx);
   return ALFD_OK;
 }
 
@@ -8110,6 +8349,17 @@ int alfd_set_controls(alfd_ctx_t ctx, const alfd_control *outer, const alfd_cont
 int alfd_setup(alfd_ctx_t ctx) {
   CHECK_CTX();
   return setup(ctx);
+}
+
+int alfd_setup_coupling(alfd_ctx_t ctx) {
+  CHECK_CTX();
+  return setup_coupling(ctx);
+}
+
+int alfd_get_setup_counts(alfd_ctx_t ctx, int64_t *counts) {
+  if (!ctx || !counts) return ALFD_E_INVALID;
+  std::copy(ctx->setup_counts, ctx->setup_counts + ALFD_SC_NCOUNTS, counts);
+  return ALFD_OK;
 }
 
 int alfd_precond_apply(alfd_ctx_t ctx, const double *const *src, double *const *dst, alfd_result *res) {
@@ -9235,6 +9485,7 @@ int alfd_set_row_blocks(alfd_ctx_t ctx, int slot, int64_t n_blocks, const int64_
   if (!ctx || slot < 0 || slot >= ALFD_NSLOTS) return ALFD_E_INVALID;
   ctx->rb_ptr[slot].clear();
   ctx->rb_rows[slot].clear();
+  ctx->needs_full = "a prolongator, aggregates or a row-block hint was set";
   if (n_blocks <= 0 || !block_ptr || !rows) return ALFD_OK;   // hint removed
   // the prefix is checked before anything is copied with it (a negative, huge or non-monotone value would be
   // undefined behaviour in vector::assign); that the blocks partition the rows is checked against the matrix at upload

@@ -46,6 +46,7 @@ ABI_SYMBOLS = [
     "alfd_system_apply_device", "alfd_augment_rhs_device",
     "alfd_get_matrix_shape", "alfd_get_operator_shape", "alfd_bench_operator", "alfd_host_small_shape",
     "alfd_host_sparse_product", "alfd_sparse_product", "alfd_smoothed_prolongator",
+    "alfd_setup_coupling", "alfd_get_setup_counts",
 ]
 
 
@@ -87,6 +88,8 @@ def load_library():
         "alfd_configure": (C.c_int, [vp, C.POINTER(_abi.Config)]),
         "alfd_default_config": (None, [C.POINTER(_abi.Config), C.c_int]),
         "alfd_setup": (C.c_int, [vp]),
+        "alfd_setup_coupling": (C.c_int, [vp]),
+        "alfd_get_setup_counts": (C.c_int, [vp, vp]),
         "alfd_precond_apply": (C.c_int, [vp, PP, PP, C.POINTER(_abi.Result)]),
         "alfd_system_apply": (C.c_int, [vp, PP, PP]),
         "alfd_augment_rhs": (C.c_int, [vp, PP]),
@@ -397,6 +400,19 @@ class Context:
     def setup(self, block_sizes):
         self._ck(self._lib.alfd_setup(self._h))
         self.block_sizes = [int(b) for b in block_sizes]
+
+    def setup_coupling(self):
+        """Re-setup after a change of the coupling alone (alfd_setup_coupling): CT / C / M / INVW uploaded again, or a
+        config that differs in gamma / gamma2 only.  Keeps A, the level operators A_l and the transfers; same bits as a
+        fresh setup.  Raises AlfdError (E_INVALID "needs alfd_setup", E_UNSUPPORTED, E_NOT_SETUP) where only setup()
+        will do; the context is then unchanged."""
+        self._ck(self._lib.alfd_setup_coupling(self._h))
+
+    def setup_counts(self):
+        """What the last setup() or setup_coupling() ran (alfd_get_setup_counts), by _abi.SETUP_COUNT_NAMES."""
+        k = np.zeros(_abi.SC_NCOUNTS, np.int64)
+        self._ck(self._lib.alfd_get_setup_counts(self._h, k.ctypes.data))
+        return {name: int(k[i]) for i, name in enumerate(_abi.SETUP_COUNT_NAMES)}
 
     # -- hot path
     def _in(self, blocks):
@@ -1157,6 +1173,30 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
     finish_hierarchy()
     ctx.configure(cfg)
     ctx.setup(pb.block_sizes)
+    return ctx
+
+
+def update_coupling(ctx: Context, Ct, inv_w=None, M=None, C=None, gamma=None) -> Context:
+    """The immersed body moved over a fixed background mesh: upload the new coupling and redo only what depends on it
+    (Context.setup_coupling).  Ct: the new coupling matrix (problems.Csr, n_u x n_l), or None when the body stayed (a
+    gamma sweep: nothing is uploaded and no product C_l P_l is formed); C: its transpose, formed here when None so that an
+    explicitly uploaded C never meets the Ct of another position; inv_w: the new W^-1 diagonal; M: the new immersed mass
+    matrix (exact W^-1, elliptic variants); gamma: a new penalty weight, configured on a copy of the context's config
+    (the caller's Config object is left alone).  Block sizes must be those of the last setup."""
+    if Ct is None and C is not None:
+        raise ValueError("update_coupling: C without Ct")
+    if Ct is not None:
+        ctx.set_matrix(_abi.C_, Ct.transpose() if C is None else C)
+        ctx.set_matrix(_abi.CT, Ct)
+    if M is not None:
+        ctx.set_matrix(_abi.M, M)
+    if inv_w is not None:
+        ctx.set_diag(_abi.INVW, inv_w)
+    if gamma is not None:
+        cfg = _abi.Config.from_buffer_copy(ctx.cfg)
+        cfg.gamma = float(gamma)
+        ctx.configure(cfg)
+    ctx.setup_coupling()
     return ctx
 
 

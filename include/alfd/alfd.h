@@ -540,6 +540,60 @@ void alfd_default_config(alfd_config *cfg, int variant);
 /* Builds transposes, sparse-row views, diag(Aug), lambda_max, halo plans
  * (replaces the setup in stokes...:1027-1045 / utilities.h:112-331). */
 int alfd_setup(alfd_ctx_t ctx);
+/* Re-setup after a change of the coupling alone (a fictitious-domain run whose immersed body moves over a fixed
+ * background mesh): redoes what depends on Ct / C, invW, M and the penalty weights and keeps what depends on A and the
+ * transfer operators alone.
+ *
+ * Contract.  The context was set up by alfd_setup or by an earlier alfd_setup_coupling.  Since then the caller may have
+ *   - uploaded any of the slots ALFD_CT, ALFD_C, ALFD_M and the diagonal ALFD_INVW again (same block sizes);
+ *   - called alfd_configure with a config that differs from the one of the last setup in gamma and / or gamma2 only
+ *     (stop rules go through alfd_set_controls as before).
+ * After ALFD_OK the context is in the state alfd_setup produces on a fresh context with the same operators, prolongators
+ * and config, bit for bit: solutions, residual histories, every iteration count, alfd_inner_prec_apply,
+ * alfd_precond_apply, alfd_system_apply.  A call with nothing changed is valid and leaves the same bits; a context
+ * updated many times does not grow (what is replaced is freed).
+ *
+ * Kept (neither recomputed, re-planned nor uploaded again): slot A and its plans; the level operators A_l (l >= 1); P_l
+ * and R_l; everything of B, Bt, Mp; the level vectors; for the elliptic variants A2 and the A2_l of the block-1 hierarchy.
+ * Recomputed, by the routines and in the order of alfd_setup: the diagonals and lambda_max of the inner operators; with an
+ * upload of CT / C the products C_{l+1} = C_l P_l and their transposes (device product, host fallback); the diagonals and
+ * lambda_max of every level; the whole interface patch (S may grow or shrink); the explicit coarsest inverse; the row
+ * masks of the fused smoother; the compacted operators of alfd_estimate_spectrum (on its next call); the diagonal of the
+ * mass solve (exact W^-1).  The block-1 hierarchy is touched only when M, ALFD_INVW or gamma2 changed, its M_l products
+ * only after an upload of M.  An inner preconditioner other than multilevel recomputes its diagonal and lambda_max.
+ *
+ * FROZEN TRANSFERS: a hierarchy built by alfd_build_smoothed_aggregation[_truncated] counts as CSR prolongators.  The
+ * update keeps the P that were built and does not rebuild them, although they were smoothed with the OLD coupling: the
+ * result equals alfd_setup on a context that was handed those P through alfd_set_prolongator, not a new build.
+ *
+ * Refusals are decided before anything is modified; the context is then as before the call (not set up when something
+ * was uploaded), and alfd_setup on it succeeds.
+ *   ALFD_E_NOT_SETUP    never set up (or the last setup of either kind failed).
+ *   ALFD_E_INVALID      with "needs alfd_setup" in alfd_last_error: another slot or diagonal was uploaded since the last
+ *                       setup; a prolongator, aggregates or a row-block hint was set; a block size changed; the config
+ *                       differs in any other field; aug_assembled = 1 (the coupling lives inside A).  Also, with
+ *                       alfd_setup's own message, a gamma / gamma2 that alfd_setup refuses for the variant (modified
+ *                       elliptic: gamma2 > 20 or within 0.1 of gamma; ideal elliptic: gamma != gamma2).
+ *   ALFD_E_UNSUPPORTED  a partitioned context (the same answer on every rank, before any exchange); the rational
+ *                       variant; a hierarchy given as aggregates (alfd_set_aggregates / alfd_build_aggregates), whose
+ *                       level products run on the host from a fetched A.  These callers keep using alfd_setup.
+ * A failure after the refusals (a HIP error, a coarsest operator that is not positive definite) leaves the context to
+ * alfd_setup.  alfd_get_setup_seconds then reports the phases of this call; ALFD_SETUP_UPLOAD keeps its meaning. */
+int alfd_setup_coupling(alfd_ctx_t ctx);
+/* What the last alfd_setup or alfd_setup_coupling ran, counted rather than timed (one-rank contexts; the replicated
+ * levels of a partitioned setup are not counted). */
+enum alfd_setup_count {
+  ALFD_SC_PRODUCTS_A = 0,        /* sparse products, device or host, with an A_l / A2_l operand, R (A P) included: 2 per
+                                  * level, also where an aggregates level forms P^T A P in one pass */
+  ALFD_SC_PRODUCTS_C = 1,        /* sparse products with a C_l / M_l operand: 1 per level (C_l P_l; the transpose that
+                                  * gives Ct_{l+1}, formed as P^T Ct_l on an aggregates level, is not counted) */
+  ALFD_SC_LEVEL_A_UPLOADS = 2,   /* plans + uploads of a level operator A_l / A2_l, l >= 1 */
+  ALFD_SC_TRANSFER_UPLOADS = 3,  /* uploads of P_l, R_l */
+  ALFD_SC_PATCH_BUILDS = 4,      /* interface patches built */
+  ALFD_SC_POWER_ITERATIONS = 5,  /* power iterations for a lambda_max (each alfd_config::cheb_power_its steps) */
+  ALFD_SC_NCOUNTS = 6
+};
+int alfd_get_setup_counts(alfd_ctx_t ctx, int64_t *counts /*[ALFD_SC_NCOUNTS]*/);
 
 /* --------------------------------------------------------------- hot path
  * Depth 1. Replaces <Preconditioner>::vmult(dst, src)

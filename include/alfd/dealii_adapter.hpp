@@ -249,6 +249,26 @@ class System {
     check(alfd_configure(ctx_, &cfg));
   }
   void setup() { check(alfd_setup(ctx_)); }
+  // The immersed body moved, the background mesh did not: the new coupling matrix and W^-1 diagonal, then
+  // alfd_setup_coupling, which redoes what depends on them and keeps A, the level operators and the transfers of the
+  // last setup() (same results as uploading everything into a new System and calling setup(); alfd.h has the contract).
+  // A new gamma goes through configure() before this call.  Throws Error with ALFD_E_INVALID / ALFD_E_UNSUPPORTED
+  // where only setup() will do (another operator changed, partitioned System, aggregates, rational variant).
+  // C: the library derives it from Ct again only while nobody has uploaded slot ALFD_C (the usual case: the call sites
+  // upload ALFD_CT alone).  A caller who once called set_matrix(ALFD_C, ...) owns that slot and must upload the new C
+  // the same way BEFORE this call, or the old C meets the new Ct.
+  template <class SparseMatrixType, class VectorType>
+  void update_coupling(const SparseMatrixType &Ct, const VectorType &invW) {
+    set_matrix(ALFD_CT, Ct);       // re-derives C unless slot ALFD_C was uploaded explicitly (see above)
+    set_diag(ALFD_INVW, invW);
+    check(alfd_setup_coupling(ctx_));
+  }
+  // what the last setup() / update_coupling() ran: indexed by alfd_setup_count
+  std::vector<int64_t> setup_counts() const {
+    std::vector<int64_t> k(ALFD_SC_NCOUNTS, 0);
+    check(alfd_get_setup_counts(ctx_, k.data()));
+    return k;
+  }
   const alfd_config &config() const { return cfg_; }
   alfd_ctx_t handle() const { return ctx_; }
 
