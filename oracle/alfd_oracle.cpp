@@ -255,6 +255,7 @@ struct Problem {
   double lambda_max = 0;
   // stats
   int64_t inner_its = 0, mp_its = 0;
+  int64_t inner_its_op[3] = {0, 0, 0};                // inner_its by alfd_inner_op (orc_h_inner_iterations)
   int inner_failures = 0, precond_applications = 0;
   int status = ALFD_OK;
   int64_t ntot() const { return off[nblocks]; }
@@ -541,6 +542,8 @@ static int inner_solve(Problem &P, int kind, const double *b, double *x) {
       st = pcg(P, op, pr, P.cfg.inner, b, x, its, res, P.cfg.log_level, "aug");
     }
     P.inner_its += its;
+    if (kind == OP_AUG || kind == OP_A22 || kind == OP_AUG2)
+      P.inner_its_op[kind == OP_AUG ? ALFD_INNER_OP_AUG : kind == OP_A22 ? ALFD_INNER_OP_A22 : ALFD_INNER_OP_AUG2] += its;
   }
   if (P.winv_status != ALFD_OK) return P.winv_status;
   if (st == FAILURE) {
@@ -1769,6 +1772,7 @@ int orc_h_precond_apply(void *h, const alfd_control *inner_override, const doubl
   orc::Problem &P = *static_cast<orc::Problem *>(h);
   if (inner_override) P.cfg.inner = *inner_override;
   P.inner_its = P.mp_its = P.rational_its = P.mass_its = 0;
+  P.inner_its_op[0] = P.inner_its_op[1] = P.inner_its_op[2] = 0;
   P.inner_failures = P.precond_applications = 0;
   std::vector<double> u, v(P.ntot(), 0.0);
   pack(P, src, u);
@@ -1784,6 +1788,7 @@ int orc_h_solve(void *h, const double *const *rhs, double *const *x, alfd_result
                 int32_t history_cap, int32_t *history_count) {
   orc::Problem &P = *static_cast<orc::Problem *>(h);
   P.inner_its = P.mp_its = P.rational_its = P.mass_its = 0;
+  P.inner_its_op[0] = P.inner_its_op[1] = P.inner_its_op[2] = 0;
   P.inner_failures = P.precond_applications = 0;
   std::vector<double> bb, xx, hist;
   pack(P, rhs, bb);
@@ -1801,6 +1806,14 @@ int orc_h_solve(void *h, const double *const *rhs, double *const *x, alfd_result
   if (history)
     for (int i = 0; i < (int)hist.size() && i < history_cap; ++i) history[i] = hist[i];
   return rc;
+}
+
+// Inner CG iterations of the last orc_h_precond_apply / orc_h_solve by alfd_inner_op (alfd_get_inner_iterations).
+int orc_h_inner_iterations(void *h, int64_t counts[3]) {
+  if (!h || !counts) return ALFD_E_INVALID;
+  const orc::Problem &P = *static_cast<orc::Problem *>(h);
+  std::copy(P.inner_its_op, P.inner_its_op + 3, counts);
+  return ALFD_OK;
 }
 
 int orc_h_system_apply(void *h, const double *const *src, double *const *dst) {

@@ -67,6 +67,8 @@ def lib():
         l.orc_h_solve.argtypes = [C.c_void_p, PP, PP, C.POINTER(_abi.Result), C.c_void_p, C.c_int32, C.POINTER(C.c_int32)]
         l.orc_h_system_apply.restype = C.c_int
         l.orc_h_system_apply.argtypes = [C.c_void_p, PP, PP]
+        l.orc_h_inner_iterations.restype = C.c_int
+        l.orc_h_inner_iterations.argtypes = [C.c_void_p, C.c_void_p]
         l.orc_h_inner_prec_apply.restype = C.c_int
         l.orc_h_inner_prec_apply.argtypes = [C.c_void_p, C.c_int, C.c_void_p, C.c_void_p]
         l.orc_set_threads.restype = C.c_int
@@ -206,6 +208,15 @@ class OracleSystem:
         dst = [np.zeros(n) for n in self.block_sizes]
         rc = lib().orc_h_system_apply(h, _blocks(src), _blocks(dst))
         return rc, dst
+
+    @staticmethod
+    def handle_inner_iterations(h):
+        """Inner CG iterations of the handle's last precond_apply / solve by inner operator, with the keys of
+        solver.Context.inner_iterations (orc_h_inner_iterations)."""
+        counts = np.zeros(3, np.int64)
+        rc = lib().orc_h_inner_iterations(h, counts.ctypes.data)
+        assert rc == 0
+        return dict(aug=int(counts[0]), a22=int(counts[1]), aug2=int(counts[2]))
 
     def handle_inner_prec_apply(self, h, r, op=_abi.INNER_OP_AUG):
         """(rc, z = M^-1 r): the inner CG's preconditioner alone (orc_h_inner_prec_apply); r as for
