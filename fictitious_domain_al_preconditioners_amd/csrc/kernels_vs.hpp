@@ -107,9 +107,9 @@ __device__ __forceinline__ void vs_batch(const int32_t (&rem)[4], int32_t maxrem
       xv[i] = vs_lds_f64(VsFmt<WD>::kWinOff + (f[i] & VsFmt<WD>::kColMask));
       v[i] = vs_lds_f64(kVsDictOff + ((f[i] >> VsFmt<WD>::kDictShift) & VsFmt<WD>::kDictMask));
     }
-    // keep the eight gathers of the chunk ahead of the (masked) fmas
-#pragma unroll
-    for (int i = 0; i < 4; ++i) asm volatile("" : "+v"(xv[i]), "+v"(v[i]));
+    // keep the eight gathers of the chunk ahead of the (masked) fmas: ONE statement, so one wait for all eight (a
+    // statement per gather gets a wait of its own each)
+    asm volatile("" : "+v"(xv[0]), "+v"(v[0]), "+v"(xv[1]), "+v"(v[1]), "+v"(xv[2]), "+v"(v[2]), "+v"(xv[3]), "+v"(v[3]));
 #pragma unroll
     for (int i = 0; i < 4; ++i) {
       if (j == NCH - 1) {
@@ -125,10 +125,13 @@ __device__ __forceinline__ void vs_batch(const int32_t (&rem)[4], int32_t maxrem
 // entry, window columns differing by one constant per row) -- the rows of one node type inside a mesh
 // brick.  One row is stored (a dword per lane and chunk, lane-major), the others add their window shift
 // sh[i] (bytes): 1/R of the stream, one dictionary gather instead of R.
-// Its stream words are fetched ONE BATCH AHEAD (vs_shared_fetch, issued before the tree and the store of the batch
-// in front, or before the block frame for a wave's first batch): a wave spent most of a batch's ~7 000 cycles waiting
-// for exactly this round trip.  w[0] = the last, partial chunk; w[1 + j] = full chunk j (static register indices for
-// every chunk count).
+// Its stream words are fetched at the END OF THE BATCH IN FRONT (vs_shared_fetch, issued behind that batch's reduction
+// tree and before its store; before the block frame for a wave's first batch): w[6] is live until the last chunk and
+// the register file has no room for a second set, so the fetch is ahead of the batch's first gathers by the store, the
+// back edge and the ~20 v_readlane of the loop head, not by a batch.  (Tried and measured slower, profiles/batch_loop: a
+// one-register touch of the words' cache lines a whole batch ahead; tried and not kept for the copies of loaded words or
+// the spills it brought: the fetch in front of the tree.)  w[0] = the last, partial chunk; w[1 + j] = full chunk j
+// (static register indices for every chunk count).
 __device__ __forceinline__ void vs_shared_fetch(uint32_t d0, const uint8_t *__restrict__ sbase, int lane, uint32_t (&w)[6]) {
   const int cls = vs_cls(d0);
   const uint8_t *fb = sbase + 16u * (size_t)vs_off(d0);
@@ -152,28 +155,39 @@ __device__ __forceinline__ void vs_shared(int32_t rem, const int32_t (&sh)[R], i
     const uint32_t lc = wj & VsFmt<WD>::kColMask;
     double v = vs_lds_f64(kVsDictOff + ((wj >> VsFmt<WD>::kDictShift) & VsFmt<WD>::kDictMask));
     constexpr int G = R > 8 ? 4 : R;   // gathers in flight (a 16-row batch takes four rounds: with 8 the kernel spills, 0.64 instead of 0.44 ms)
+    // the rounds of a chunk: G gathers, ONE wait for them (one pinning statement naming them all, and v in round 0: a
+    // statement per gather gets an s_waitcnt of its own each, and the batch loop, unrolled by two, then spills), G fmas
+    auto rounds = [&]() __attribute__((always_inline)) {
 #pragma unroll
-    for (int g = 0; g < R; g += G) {
-      double xv[G];
+      for (int g = 0; g < R; g += G) {
+        double xv[G];
 #pragma unroll
-      for (int i = 0; i < G; ++i) xv[i] = vs_lds_f64(VsFmt<WD>::kWinOff + (uint32_t)((int32_t)lc + sh[g + i]));
-#pragma unroll
-      for (int i = 0; i < G; ++i) asm volatile("" : "+v"(xv[i]));
-      if (g == 0) asm volatile("" : "+v"(v));
-      if (j == NCH - 1) {
-        if (lane < rem) {   // one exec mask around the fmas (the empty asm keeps it a branch, not 2 G selects)
-          asm volatile("");
-#pragma unroll
-          for (int i = 0; i < G; ++i) acc[g + i] = fma(v, xv[i], acc[g + i]);
+        for (int i = 0; i < G; ++i) xv[i] = vs_lds_f64(VsFmt<WD>::kWinOff + (uint32_t)((int32_t)lc + sh[g + i]));
+        if constexpr (G == 4) {
+          if (g == 0)
+            asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(v));
+          else
+            asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]));
+        } else {
+          static_assert(G == 8, "one pinning statement per round: written out for rounds of 4 and of 8 gathers");
+          asm volatile("" : "+v"(xv[0]), "+v"(xv[1]), "+v"(xv[2]), "+v"(xv[3]), "+v"(xv[4]), "+v"(xv[5]), "+v"(xv[6]),
+                       "+v"(xv[7]), "+v"(v));
         }
-      } else {
 #pragma unroll
         for (int i = 0; i < G; ++i) acc[g + i] = fma(v, xv[i], acc[g + i]);
-      }
-      if (R > 8) {   // round by round: G gathers, G fmas (left alone the fmas sink below ALL gathers of the batch: spills)
+        if (R > 8) {   // round by round: G gathers, G fmas (left alone the fmas sink below ALL gathers of the batch: spills)
 #pragma unroll
-        for (int i = 0; i < G; ++i) asm volatile("" : "+v"(acc[g + i]));
+          for (int i = 0; i < G; ++i) asm volatile("" : "+v"(acc[g + i]));
+        }
       }
+    };
+    if (j == NCH - 1) {
+      if (lane < rem) {   // one exec mask around the chunk's rounds (the empty asm keeps it a branch, not selects)
+        asm volatile("");
+        rounds();
+      }
+    } else {
+      rounds();
     }
   }
 }
@@ -274,13 +288,21 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
       }
     }
   };
-  for (int32_t bi = wave; bi < nbatch; bi += NW) {
+  // One batch.  hc holds the batch's descriptor, hn the descriptor of the wave's next batch; at its end the batch
+  // requests the descriptor of the batch after that INTO hc, whose contents it has used up.  The loop below is unrolled by
+  // two and calls it with the two registers swapping roles, so the register a descriptor is loaded into is the one it is
+  // read from two batches later.  Rotating them in a loop of one batch (hv1 = hv2; hv2 = load) cannot be had without a
+  // copy of the value just requested, and that copy stood behind a vmcnt(0) at the end of every batch: a full round trip
+  // on the descriptor line, plus the acknowledgement of the batch's own store.  Now no wait stands between the
+  // descriptor load and the back edge; the load is covered by the wait for the stream words at the head of the next
+  // batch, which were requested just in front of it.
+  auto batch = [&](uint32_t &hc, uint32_t &hn, const int32_t bi) __attribute__((always_inline)) {
     uint32_t lo[16];   // low dwords of the rows: offset | count | class (row 0, plain rows), window shifts (shared rows 1..)
 #pragma unroll
-    for (int i = 0; i < 16; ++i) lo[i] = hdr(hv1, 2 * i);
-    const bool shared = (int32_t)hdr(hv1, 1) < 0;                       // wave-uniform
-    const bool sixteen = shared && (int32_t)hdr(hv1, 17) >= 0;          // a ninth row
-    const bool eight = shared && !sixteen && (int32_t)hdr(hv1, 9) >= 0;  // a fifth row
+    for (int i = 0; i < 16; ++i) lo[i] = hdr(hc, 2 * i);
+    const bool shared = (int32_t)hdr(hc, 1) < 0;                       // wave-uniform
+    const bool sixteen = shared && (int32_t)hdr(hc, 17) >= 0;          // a ninth row
+    const bool eight = shared && !sixteen && (int32_t)hdr(hc, 9) >= 0;  // a fifth row
     const uint32_t eb = vs_off(lo[0]);
     const int cls = vs_cls(lo[0]);
     const int32_t full = cls > 0 ? 64 * (cls - 1) : 0;
@@ -355,11 +377,11 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
         case 6: vs_batch<6, WD>(rem, maxrem, lane, fb, sm, acc); break;
         default: break;  // class 0: empty rows
       }
-      // the next descriptor is read BEFORE the store: after it, the wait that makes hv2 readable would also wait for
+      // the next descriptor is read BEFORE the store: after it, the wait that makes hn readable would also wait for
       // the store's acknowledgement, and only then would the next batch's loads go out (two round trips in a row)
-      n0 = hdr(hv2, 0);
-      n1 = hdr(hv2, 1);
-      store(reduce_rows4(acc[0], acc[1], acc[2], acc[3]), (int32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hv1), (lane & 15) == 0);
+      n0 = hdr(hn, 0);
+      n1 = hdr(hn, 1);
+      store(reduce_rows4(acc[0], acc[1], acc[2], acc[3]), (int32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hc), (lane & 15) == 0);
       mstep = 0;
     }
     // the stream words of the wave's next shared batch (the ONE place of the loop that writes w: no copies of loaded
@@ -368,15 +390,19 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     // also wait for the store's acknowledgement (as the round-2 kernel did, once per batch).
     int32_t rid = -1;
     if (mstep) {
-      rid = (int32_t)((uint32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hv1) &
+      rid = (int32_t)((uint32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hc) &
                       (lane < 8 ? 0x7fffffffu : 0xffffffffu));   // bit 63 of row 0 is the shared-batch flag
-      n0 = hdr(hv2, 0);
-      n1 = hdr(hv2, 1);
+      n0 = hdr(hn, 0);
+      n1 = hdr(hn, 1);
     }
-    hv1 = hv2;
     if (bi + NW < nbatch && (int32_t)n1 < 0) vs_shared_fetch(n0, sbase, lane, w);
-    hv2 = hdr_load(bi + 2 * NW);
+    hc = hdr_load(bi + 2 * NW);
     if (mstep) store(sres, rid, (lane & (mstep - 1)) == 0);
+  };
+  for (int32_t bi = wave; bi < nbatch; bi += 2 * NW) {
+    batch(hv1, hv2, bi);
+    if (bi + NW >= nbatch) break;
+    batch(hv2, hv1, bi + NW);
   }
 }
 
