@@ -123,6 +123,26 @@ class BatchMajorShape(C.Structure):
         return {(k if k in plain else "batch_major_" + k): getattr(self, k) for k, _ in self._fields_}
 
 
+# enum alfd_prec_values / alfd_prec_values_reason (alfd_set_preconditioner_values)
+PREC_VALUES_FP64, PREC_VALUES_FP32 = range(2)
+PREC_VALUES_BY_NAME = {"fp64": PREC_VALUES_FP64, "fp32": PREC_VALUES_FP32}
+PV_NONE, PV_NOT_REQUESTED, PV_NO_MATRIX, PV_SHORT_ROWS, PV_SPARSE_ROWS, PV_DICTIONARY_FORM, PV_PARTITIONED, \
+    PV_OUT_OF_RANGE, PV_NOT_APPLIED = range(9)
+PREC_VALUES_REASON_NAMES = ("none", "not_requested", "no_matrix", "short_rows", "sparse_rows", "dictionary_form",
+                            "partitioned", "out_of_range", "not_applied")
+PREC_VALUES_FAMILY_NAMES = ("plain", "stream", "window")
+
+
+class PrecValuesInfo(C.Structure):
+    """alfd_prec_values_info: the single-precision copy of slot A inside the inner preconditioner."""
+    _fields_ = [
+        ("requested", C.c_int32), ("stored", C.c_int32), ("used", C.c_int32), ("reason", C.c_int32),
+        ("family", C.c_int32), ("reserved", C.c_int32),
+        ("nnz", C.c_int64), ("flushed_to_zero", C.c_int64), ("copy_bytes", C.c_int64),
+        ("streamed_bytes_fp64", C.c_double), ("streamed_bytes_fp32", C.c_double),
+    ]
+
+
 # alfd_operator: the operators the library builds at alfd_setup (alfd_get_operator_info, alfd_bench_operator)
 OPERATOR_LEVEL, OPERATOR_PATCH_SS, OPERATOR_PATCH_S = 0, 1, 2
 

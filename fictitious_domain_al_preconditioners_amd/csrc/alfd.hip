@@ -135,6 +135,16 @@ struct DevCsr {
     return (double)(vi_nnz - vi_wide_nnz) * 3.0 + (double)vi_wide_nnz * 4.0 + (double)(nnz - vi_nnz) * 10.0 + vec + meta + (double)vi_dict_total * 8.0 +
            (double)win_nblocks * (8.0 + (vib_tab ? 32.0 * vib_stride + 4.0 : 0.0));
   }
+  // single-precision copy of val (slot A only, alfd_set_preconditioner_values): what the level-0 products inside the
+  // inner preconditioner stream instead of val.  Not in `owned`: dropped with the request, too (a32_release)
+  float *val32 = nullptr;
+  int64_t val32_flushed = 0;   // entries whose binary32 image would be subnormal: stored as signed zeros
+  // ... and the bytes of one launch on it: 4-byte values + 16-bit window columns, or + 32-bit columns
+  double streamed_bytes32() const {
+    const double vec = (double)(n_list + 1) * 8.0 + (double)n_list * 8.0 + (double)ncols * 8.0;
+    if (!win) return (double)nnz * 8.0 + vec;
+    return (double)nnz * 6.0 + vec + (double)win_nblocks * 8.0 + (double)win_nseg * 8.0;
+  }
   double algorithmic_bytes() const {
     // nnz*(8+4) + (nrows+1)*8 + nrows*8 + ncols*8  (x read once)
     return (double)nnz * 12.0 + (double)(n_list + 1) * 8.0 + (double)n_list * 8.0 +
@@ -237,6 +247,13 @@ struct alfd_ctx {
   int64_t diag_n[ALFD_NDIAGS] = {0, 0};
   alfd_config cfg;
   bool configured = false, is_setup = false;
+  // alfd_set_preconditioner_values: a32_reason says why slot A holds no single-precision copy (NONE: it does);
+  // a32_used, decided by alfd_setup: the inner preconditioner applies A through it; a32_view: the launches of slot A
+  // between here and the end of the scope read it (A32Scope)
+  int prec_values = ALFD_PREC_VALUES_FP64, a32_reason = ALFD_PREC_VALUES_NOT_REQUESTED;
+  bool a32_used = false, a32_view = false;
+  int a32_R = 4, a32_U = 16;                  // launch shape of the window kernel on the copy (ALFD_SPMV_PREC32_R / _U)
+  unsigned long long *a32_counts = nullptr;   // device: {flushed to zero, without a finite image} of the last conversion
   // device workspace
   double *sc = nullptr;        // device scalar table
   double *sc_host = nullptr;   // pinned mirror
@@ -534,6 +551,7 @@ static int csr_alloc(alfd_ctx *ctx, DevCsr &m, T **p, int64_t count) {
 }
 static void csr_free(DevCsr &m) {
   for (void *q : m.owned) hipFree(q);
+  if (m.val32) hipFree(m.val32);
   m = DevCsr();
 }
 
@@ -766,6 +784,70 @@ static bool launch_window_RU(alfd_ctx *ctx, const DevCsr &m, const double *x, do
   return false;
 }
 
+// ---- the single-precision copy of slot A (alfd_set_preconditioner_values): the float instantiations
+// of the three kernel families a 64-lane operator with 8-byte values runs on, epilogues 0 and 1 (all that level 0 of the
+// cycle uses).  A kernel loads a float, widens it (exact) and forms the canonical sums, so the shape of the launch does
+// not show in the result: one shape per family, whatever ALFD_SPMV_STREAM_R / _U name for the 8-byte kernels (the window
+// kernel keeps its measured candidates behind ALFD_SPMV_PREC32_R / _U).
+struct A32Scope {   // launches of slot A inside the scope read the copy
+  alfd_ctx *ctx;
+  bool was;
+  A32Scope(alfd_ctx *c, bool on) : ctx(c), was(c->a32_view) { if (on) c->a32_view = true; }
+  ~A32Scope() { ctx->a32_view = was; }
+};
+static inline bool a32_active(const alfd_ctx *ctx, const DevCsr &m) {
+  return ctx->a32_view && &m == &ctx->mat[ALFD_A] && m.val32;
+}
+// 2 window, 1 stream, 0 plain: the family spmv_launch_local's choice for the 8-byte values belongs to
+static inline int a32_family(const alfd_ctx *ctx, const DevCsr &m) { return m.win ? 2 : ctx->spmv_stream_R > 0 ? 1 : 0; }
+
+template <int R, int U>
+static void launch_window32(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha) {
+  const size_t lds = (size_t)m.win_maxW * sizeof(double);
+#define ALFD_WIN32(EPI)                                                                                        \
+  hipLaunchKernelGGL((spmv_window_kernel<R, U, EPI, 0, float>), dim3((unsigned)m.win_nblocks), dim3(kBlock),  \
+                     lds, ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val32, m.blk_seg_begin,       \
+                     m.blk_W, m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha,                        \
+                     (const double *)nullptr, (double *)nullptr, ctx->win_xcd)
+  if (epi == 0) ALFD_WIN32(0);
+  else ALFD_WIN32(1);
+#undef ALFD_WIN32
+}
+
+static int spmv_launch_a32(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha) {
+  if (epi != 0 && epi != 1) return ctx->err = "the single-precision copy of A has epilogues 0 and 1 only", ALFD_E_UNSUPPORTED;
+  const int family = a32_family(ctx, m);
+  if (family == 2) {
+    // (4, 16) is the measured choice (profiles/prec_values/: 0.90 of the 8-byte kernel's time per launch at N = 56, where
+    // (2, 8), the shape of the 8-byte kernel, takes 1.18 of it); the other candidates stay selectable for re-measuring
+    if (ctx->a32_R == 2 && ctx->a32_U == 8) launch_window32<2, 8>(ctx, m, x, y, epi, alpha);
+    else if (ctx->a32_R == 4 && ctx->a32_U == 8) launch_window32<4, 8>(ctx, m, x, y, epi, alpha);
+    else if (ctx->a32_R == 2 && ctx->a32_U == 16) launch_window32<2, 16>(ctx, m, x, y, epi, alpha);
+    else launch_window32<4, 16>(ctx, m, x, y, epi, alpha);
+  } else if (family == 1) {   // grid as launch_stream<2, 8, false>
+    const int64_t nbatches = (m.nrows + 1) / 2;
+    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
+#define ALFD_STREAM32(EPI)                                                                                          \
+  hipLaunchKernelGGL((spmv_stream_kernel<2, 8, EPI, false, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
+                     m.nrows, m.rp, m.col, m.val32, x, m.halo, m.n_local_cols, y, alpha, (const double *)nullptr,    \
+                     (double *)nullptr, NoPair())
+    if (epi == 0) ALFD_STREAM32(0);
+    else ALFD_STREAM32(1);
+#undef ALFD_STREAM32
+  } else {
+    const int grid = grid_for_rows(m.n_list, 64);
+#define ALFD_SPMV32(EPI)                                                                                          \
+  hipLaunchKernelGGL((spmv_kernel<64, EPI, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list,    \
+                     m.rp, m.col, m.val32, m.rows, x, m.halo, m.n_local_cols, y, alpha, (const double *)nullptr,  \
+                     (double *)nullptr)
+    if (epi == 0) ALFD_SPMV32(0);
+    else ALFD_SPMV32(1);
+#undef ALFD_SPMV32
+  }
+  HIPC(hipGetLastError());
+  return ALFD_OK;
+}
+
 
 template <int L>
 static void launch_vss(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
@@ -859,6 +941,11 @@ static int spmv_launch_local(alfd_ctx *ctx, DevCsr &m, const double *x, double *
 static int spmv_m(alfd_ctx *ctx, DevCsr &m, int cls, const double *x, double *y, int epi, double alpha = 0.0,
                   const double *d = nullptr, double *y2 = nullptr) {
   if (!m.present) return ctx->err = "matrix not set", ALFD_E_NOT_SETUP;
+  if (a32_active(ctx, m)) {   // one rank, every row listed: no exchange, no memset
+    if (m.n_list == 0) return ALFD_OK;
+    Timer tm(ctx, cls, m.algorithmic_bytes(), m.streamed_bytes32());
+    return spmv_launch_a32(ctx, m, x, y, epi, alpha);
+  }
   // RCCL send/recv pairs can be skipped by ranks with nothing to exchange; the
   // barrier-based in-process group needs every rank in every exchange.
   const bool exchange = ctx->nranks > 1 && !m.rep && (ctx->local || ctx->host_alltoallv || m.n_halo > 0 || m.send_off.back() > 0);
@@ -963,6 +1050,72 @@ static int pick_short_row_format(alfd_ctx *ctx, DevCsr &m) {
   return ALFD_OK;
 }
 
+// ---- the single-precision copy of slot A: made when the request and the storage form of A allow it, else released
+static void a32_release(alfd_ctx *ctx) {
+  DevCsr &m = ctx->mat[ALFD_A];
+  if (m.val32) hipFree(m.val32);
+  m.val32 = nullptr;
+  m.val32_flushed = 0;
+  ctx->a32_used = false;
+}
+
+// Why slot A holds no copy, as far as the request and the storage form say.  The partition is asked first: every rank
+// gives the same answer whatever its piece of A looks like.
+static int a32_form_reason(const alfd_ctx *ctx) {
+  const DevCsr &m = ctx->mat[ALFD_A];
+  if (ctx->prec_values != ALFD_PREC_VALUES_FP32) return ALFD_PREC_VALUES_NOT_REQUESTED;
+  if (ctx->nranks > 1) return ALFD_PREC_VALUES_PARTITIONED;
+  if (!m.present) return ALFD_PREC_VALUES_NO_MATRIX;
+  if (m.sparse) return ALFD_PREC_VALUES_SPARSE_ROWS;
+  if (m.L != 64) return ALFD_PREC_VALUES_SHORT_ROWS;
+  if (m.vs.on || m.vi) return ALFD_PREC_VALUES_DICTIONARY_FORM;
+  return ALFD_PREC_VALUES_NONE;
+}
+
+// After a change of the request or of slot A: a32_reason, and the copy when nothing speaks against it (converted on the
+// device from the resident values, which also counts the flushed entries and those without a finite image)
+static int a32_sync(alfd_ctx *ctx) {
+  DevCsr &m = ctx->mat[ALFD_A];
+  a32_release(ctx);
+  ctx->a32_reason = a32_form_reason(ctx);
+  if (ctx->a32_reason != ALFD_PREC_VALUES_NONE) return ALFD_OK;
+  if (!ctx->a32_counts) RC(dev_alloc(ctx, &ctx->a32_counts, 2));
+  HIPC(hipMalloc((void **)&m.val32, std::max<int64_t>(m.nnz, 1) * sizeof(float)));
+  HIPC(hipMemsetAsync(ctx->a32_counts, 0, 2 * sizeof(unsigned long long), ctx->stream));
+  if (m.nnz > 0) {
+    const unsigned grid = (unsigned)std::min<int64_t>((m.nnz + 255) / 256, 256 * 16);
+    hipLaunchKernelGGL(round_values_kernel, dim3(grid), dim3(256), 0, ctx->stream, m.nnz, m.val, m.val32, ctx->a32_counts);
+    HIPC(hipGetLastError());
+  }
+  unsigned long long counts[2] = {0, 0};
+  HIPC(hipMemcpyAsync(counts, ctx->a32_counts, sizeof(counts), hipMemcpyDeviceToHost, ctx->stream));
+  HIPC(hipStreamSynchronize(ctx->stream));
+  if (counts[1] > 0) {
+    a32_release(ctx);
+    ctx->a32_reason = ALFD_PREC_VALUES_OUT_OF_RANGE;
+    return ALFD_OK;
+  }
+  m.val32_flushed = (int64_t)counts[0];
+  ctx->a32_reason = ALFD_PREC_VALUES_NOT_APPLIED;   // until a setup says otherwise
+  return ALFD_OK;
+}
+
+// alfd_setup / alfd_setup_coupling succeeded: does the configured inner preconditioner apply slot A?  The multilevel
+// cycle on level 0 of hierarchy 0 (not when that level is the coarsest one with an explicit inverse), the Chebyshev
+// sweep on Aug of the variants whose inner solve runs on the (1,1) block alone.
+static void a32_decide_used(alfd_ctx *ctx) {
+  const alfd_config &c = ctx->cfg;
+  ctx->a32_used = false;
+  if (!ctx->mat[ALFD_A].val32) return;
+  const alfd_ctx::Hierarchy &H = ctx->hier[0];
+  if (c.inner_prec == ALFD_PREC_MULTILEVEL)
+    ctx->a32_used = c.variant != ALFD_RATIONAL && !H.ml.empty() && (H.ml.size() > 1 || !H.inv.present);
+  else if (c.inner_prec == ALFD_PREC_CHEBYSHEV)
+    ctx->a32_used = c.cheb_degree > 1 && (c.variant == ALFD_AL2 || c.variant == ALFD_AL_STOKES ||
+                                          c.variant == ALFD_AL_STOKES_DIAG || c.variant == ALFD_AL_ELL_MODIFIED);
+  ctx->a32_reason = ctx->a32_used ? ALFD_PREC_VALUES_NONE : ALFD_PREC_VALUES_NOT_APPLIED;
+}
+
 static int spmv(alfd_ctx *ctx, int slot, const double *x, double *y, int epi, double alpha = 0.0,
                 const double *d = nullptr, double *y2 = nullptr) {
   DevCsr &m = ctx->mat[slot];
@@ -982,6 +1135,7 @@ static bool tail_form(const DevCsr &m) { return m.present && !m.vs.on && !m.win;
 // which PAIR instantiation spmv_launch_local's choice for A has: 1 batch-major, 2 stream, 0 none
 static int pair_form_A(alfd_ctx *ctx, const DevCsr &A) {
   if (!A.present || A.sparse || A.n_list == 0) return 0;
+  if (a32_active(ctx, A)) return 0;   // the single-precision copy has no PAIR instantiation (speed only)
   if (A.vs.on && ctx->vs_enable && !ctx->vi_off)
     return A.vs.L == 64 && !A.vs.wide && A.vs.NW <= 4 && A.vs.nb > 0 && vs_lds_base_ok(ctx) ? 1 : 0;
   if (A.win) return 0;
@@ -1240,6 +1394,7 @@ static int cheb_sweep(alfd_ctx *ctx, int64_t npad, const double *dinv, double lm
 
 static int cheb_apply(alfd_ctx *ctx, int op, const double *r, double *z, int64_t npad) {
   const int k = ctx->cfg.cheb_degree;
+  const A32Scope a32(ctx, op == OP_AUG && ctx->a32_used);   // the A product of the sweep on Aug
   // SpMV writes rows only: padding of the product vector must be zero
   if (k > 1) HIPC(hipMemsetAsync(ctx->c_tmp, 0, npad * sizeof(double), ctx->stream));
   return cheb_sweep(ctx, npad, op_dinv(ctx, op), ctx->lam_max[op], ctx->cfg.cheb_eig_ratio, k, ctx->c_d, ctx->c_res,
@@ -4204,6 +4359,9 @@ static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
   }
   const LevelView L = level_view(ctx, h, l);
   const AugOp &F = L.op;
+  // level 0 of hierarchy 0: smoother steps and both residuals take slot A through its single-precision copy (the
+  // levels below never name slot A)
+  const A32Scope a32(ctx, h == 0 && l == 0 && ctx->a32_used);
   if (l == last) {
     if (H.inv.present) return spmv_m(ctx, H.inv, ALFD_T_SPMV_OTHER, r, z, 0);   // z = Aug_c^-1 r
     return aug_cheb(ctx, F, c.ml_coarse_degree, c.ml_coarse_ratio, r, z);
@@ -6704,6 +6862,7 @@ static void setup_begin(alfd_ctx *ctx) {
   ctx->upload_since_setup = false;
   ctx->is_setup = false;
   ctx->coupling_ready = false;   // until this setup succeeds
+  ctx->a32_used = false;         // the setup itself runs on the 8-byte values of A
 }
 // a setup of either kind succeeded: what alfd_setup_coupling compares the next call against
 static void setup_done(alfd_ctx *ctx, bool coupling_ready) {
@@ -6713,6 +6872,7 @@ static void setup_done(alfd_ctx *ctx, bool coupling_ready) {
   ctx->needs_full = nullptr;
   ctx->coupling_ready = coupling_ready;
   ctx->is_setup = true;
+  a32_decide_used(ctx);
 }
 
 static int setup(alfd_ctx *ctx) {
@@ -7202,6 +7362,8 @@ int alfd_create(alfd_ctx_t *out, int device_id) {
   alfd_default_config(&ctx->cfg, ALFD_AL_STOKES);
   if (const char *e = std::getenv("ALFD_SPMV_STREAM_R")) ctx->spmv_stream_R = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_STREAM_U")) ctx->spmv_stream_U = std::atoi(e);
+  if (const char *e = std::getenv("ALFD_SPMV_PREC32_R")) ctx->a32_R = std::atoi(e);
+  if (const char *e = std::getenv("ALFD_SPMV_PREC32_U")) ctx->a32_U = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_NT")) ctx->spmv_nt = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_GRID")) ctx->spmv_grid_mult = std::max(1, std::atoi(e));
   if (const char *e = std::getenv("ALFD_SPMV_WINDOW")) ctx->win_enable = std::atoi(e);
@@ -7364,6 +7526,7 @@ int alfd_set_matrix(alfd_ctx_t ctx, int slot, int64_t nrows, int64_t ncols, cons
     }
   } upload_clock{ctx};
   RC(upload_matrix(ctx, slot, nrows, ncols, row_ptr, col, val));
+  if (slot == ALFD_A) RC(a32_sync(ctx));   // the single-precision copy follows the new values (or goes with the old ones)
   if ((slot == ALFD_M || slot == ALFD_KIMM) && nnz <= (int64_t)1 << 26) {
     // the rational preconditioner builds its 21 shifted systems from these on the host
     HostCsr &h = slot == ALFD_M ? ctx->h_M : ctx->h_K;
@@ -8770,6 +8933,82 @@ int alfd_bench_spmv_format(alfd_ctx_t ctx, int slot, int32_t reps, int use_value
   const int rc = alfd_bench_spmv(ctx, slot, reps, ms_per_launch, nullptr);
   ctx->vi_off = was_off;
   if (streamed_bytes) *streamed_bytes = ctx->mat[slot].streamed_bytes(use_value_index != 0, ctx->vs_enable != 0);
+  return rc;
+}
+
+int alfd_set_preconditioner_values(alfd_ctx_t ctx, int kind) {
+  CHECK_CTX();
+  if (kind != ALFD_PREC_VALUES_FP64 && kind != ALFD_PREC_VALUES_FP32)
+    return ctx->err = "alfd_set_preconditioner_values: unknown kind", ALFD_E_INVALID;
+  if (kind == ctx->prec_values) return ALFD_OK;   // nothing changes: the setup stays
+  ctx->prec_values = kind;
+  ctx->is_setup = false;   // as alfd_configure; alfd_setup_coupling answers "needs alfd_setup"
+  ctx->needs_full = "the value type of the preconditioner (alfd_set_preconditioner_values) was set";
+  HIPC(hipStreamSynchronize(ctx->stream));
+  return a32_sync(ctx);
+}
+
+int alfd_get_preconditioner_values(alfd_ctx_t ctx, alfd_prec_values_info *out) {
+  if (!ctx || !out) return ALFD_E_INVALID;
+  const DevCsr &m = ctx->mat[ALFD_A];
+  std::memset(out, 0, sizeof(*out));
+  out->requested = ctx->prec_values == ALFD_PREC_VALUES_FP32 ? 1 : 0;
+  out->stored = m.val32 ? 1 : 0;
+  out->used = m.val32 && ctx->is_setup && ctx->a32_used ? 1 : 0;
+  if (m.val32) {
+    out->reason = out->used ? ALFD_PREC_VALUES_NONE : ALFD_PREC_VALUES_NOT_APPLIED;
+    out->family = a32_family(ctx, m);
+    out->flushed_to_zero = m.val32_flushed;
+    out->copy_bytes = std::max<int64_t>(m.nnz, 1) * (int64_t)sizeof(float);
+    out->streamed_bytes_fp32 = m.streamed_bytes32();
+  } else {
+    const int form = a32_form_reason(ctx);   // an entry out of range is all that the form cannot tell
+    out->reason = form == ALFD_PREC_VALUES_NONE ? ctx->a32_reason : form;
+  }
+  if (m.present) {
+    out->nnz = m.nnz;
+    out->streamed_bytes_fp64 = m.streamed_bytes(!ctx->vi_off, ctx->vs_enable != 0 && !ctx->vi_off);
+  }
+  return ALFD_OK;
+}
+
+int alfd_spmv_preconditioner(alfd_ctx_t ctx, const double *x, double *y, int mode, double alpha) {
+  CHECK_CTX();
+  if (!x || !y || (mode != 0 && mode != 1)) return ALFD_E_INVALID;
+  DevCsr &m = ctx->mat[ALFD_A];
+  if (!m.val32)
+    return ctx->err = "alfd_spmv_preconditioner: slot A holds no single-precision copy (alfd_get_preconditioner_values)",
+           ALFD_E_UNSUPPORTED;
+  double *dx = nullptr, *dy = nullptr;
+  HIPC(hipMalloc((void **)&dx, std::max<int64_t>(m.ncols, 1) * sizeof(double)));
+  HIPC(hipMalloc((void **)&dy, std::max<int64_t>(m.nrows, 1) * sizeof(double)));
+  HIPC(hipMemcpyAsync(dx, x, m.ncols * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  HIPC(hipMemcpyAsync(dy, y, m.nrows * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+  int rc;
+  {
+    const A32Scope a32(ctx, true);
+    rc = spmv(ctx, ALFD_A, dx, dy, mode, alpha);
+  }
+  if (rc == ALFD_OK) {
+    HIPC(hipMemcpyAsync(y, dy, m.nrows * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+    HIPC(hipStreamSynchronize(ctx->stream));
+  }
+  hipFree(dx);
+  hipFree(dy);
+  return rc;
+}
+
+int alfd_bench_spmv_preconditioner(alfd_ctx_t ctx, int32_t reps, double *ms_per_launch, double *streamed_bytes) {
+  CHECK_CTX();
+  if (reps < 1) return ALFD_E_INVALID;
+  if (!ctx->mat[ALFD_A].val32)
+    return ctx->err = "alfd_bench_spmv_preconditioner: slot A holds no single-precision copy", ALFD_E_UNSUPPORTED;
+  int rc;
+  {
+    const A32Scope a32(ctx, true);
+    rc = alfd_bench_spmv(ctx, ALFD_A, reps, ms_per_launch, nullptr);
+  }
+  if (streamed_bytes) *streamed_bytes = ctx->mat[ALFD_A].streamed_bytes32();
   return rc;
 }
 

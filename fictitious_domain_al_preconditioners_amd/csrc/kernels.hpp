@@ -210,10 +210,10 @@ __device__ __forceinline__ double block_reduce_256(double v, double *lds4) {
 // Columns >= n_local read the halo buffer (multi-GPU row partition).
 // The body is shared with the second party of a pair launch (pair_rows below): workgroup `block` of `nblocks`, of BLK
 // threads (a pair launch has the workgroup size of its first party).
-template <int L, int EPI, bool SPARSE, int BLK = kBlock>
+template <int L, int EPI, bool SPARSE, int BLK = kBlock, class VT = double>
 __device__ __forceinline__ void spmv_rows(int64_t block, int64_t nblocks, int64_t nrows,
                                           const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
-                                          const double *__restrict__ val, const int32_t *__restrict__ rows,
+                                          const VT *__restrict__ val, const int32_t *__restrict__ rows,
                                           const double *__restrict__ x, const double *__restrict__ x_halo,
                                           int32_t n_local, double *__restrict__ y, double alpha,
                                           const double *__restrict__ d, double *__restrict__ y2) {
@@ -229,7 +229,7 @@ __device__ __forceinline__ void spmv_rows(int64_t block, int64_t nblocks, int64_
       for (int64_t k = k0 + lane; k < k1; k += L) {
         const int32_t c = col[k];
         const double xv = (c < n_local) ? x[c] : x_halo[c - n_local];
-        acc = fma(val[k], xv, acc);
+        acc = fma((double)val[k], xv, acc);
       }
       acc = group_reduce<L>(acc);
       if (lane == 0) {
@@ -249,17 +249,17 @@ __device__ __forceinline__ void spmv_rows(int64_t block, int64_t nblocks, int64_
   }
 }
 
-template <int L, int EPI, bool SPARSE>
+template <int L, int EPI, bool SPARSE, class VT = double>
 __global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64_t *__restrict__ rp,
                                                       const int32_t *__restrict__ col,
-                                                      const double *__restrict__ val,
+                                                      const VT *__restrict__ val,
                                                       const int32_t *__restrict__ rows,
                                                       const double *__restrict__ x,
                                                       const double *__restrict__ x_halo, int32_t n_local,
                                                       double *__restrict__ y, double alpha,
                                                       const double *__restrict__ d,
                                                       double *__restrict__ y2) {
-  spmv_rows<L, EPI, SPARSE>(blockIdx.x, gridDim.x, nrows, rp, col, val, rows, x, x_halo, n_local, y, alpha, d, y2);
+  spmv_rows<L, EPI, SPARSE, kBlock, VT>(blockIdx.x, gridDim.x, nrows, rp, col, val, rows, x, x_halo, n_local, y, alpha, d, y2);
 }
 
 // --------------------------------------------------------------------------
@@ -311,10 +311,10 @@ using PairArg = typename std::conditional<PAIR, PairC, NoPair>::type;
 // IS one canonical lane partial, rotated by d_i = (k0_i - k_begin) mod 64.  One
 // ds_bpermute un-rotates before the butterfly.
 // PAIR: the grid carries a second party behind its first nA workgroups (pair_rows above).
-template <int R, int U, int EPI, bool NT, bool PAIR = false>
+template <int R, int U, int EPI, bool NT, bool PAIR = false, class VT = double>
 __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
     int64_t nrows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
-    const double *__restrict__ val, const double *__restrict__ x, const double *__restrict__ x_halo,
+    const VT *__restrict__ val, const double *__restrict__ x, const double *__restrict__ x_halo,
     int32_t n_local, double *__restrict__ y, double alpha, const double *__restrict__ d,
     double *__restrict__ y2, PairArg<PAIR> pc) {
   if (pair_rows(pc, x)) return;
@@ -335,10 +335,11 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
 #pragma unroll
     for (int i = 0; i < R; ++i) acc[i] = 0.0;
     const int32_t *cb = col + k_begin;
-    const double *vb = val + k_begin;
+    const VT *vb = val + k_begin;
     for (int32_t base = 0; base < n_batch; base += 64 * U) {
       int32_t c[U];
-      double v[U], xv[U];
+      VT v[U];
+      double xv[U];
 #pragma unroll
       for (int u = 0; u < U; ++u) {
         const int32_t o = base + 64 * u + lane;
@@ -347,7 +348,7 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
           v[u] = NT ? __builtin_nontemporal_load(vb + o) : vb[o];
         } else {
           c[u] = -1;
-          v[u] = 0.0;
+          v[u] = VT(0);
         }
       }
 #pragma unroll
@@ -361,7 +362,7 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
         if (c[u] >= 0) {
 #pragma unroll
           for (int i = 0; i < R; ++i)
-            if (o >= rel[i] && o < rel[i + 1]) acc[i] = fma(v[u], xv[u], acc[i]);
+            if (o >= rel[i] && o < rel[i + 1]) acc[i] = fma((double)v[u], xv[u], acc[i]);
         }
       }
     }
@@ -404,10 +405,10 @@ __global__ __launch_bounds__(kBlock) void spmv_stream_kernel(
 // memory with the original 32-bit columns.
 // TAG only distinguishes instantiations (fine operator = 0, multigrid level matrices = 1)
 // so that profiler summaries report them separately.
-template <int R, int U, int EPI, int TAG = 0>
+template <int R, int U, int EPI, int TAG = 0, class VT = double>
 __global__ __launch_bounds__(kBlock) void spmv_window_kernel(
     int64_t nrows, int32_t RB, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
-    const uint16_t *__restrict__ lcol, const double *__restrict__ val,
+    const uint16_t *__restrict__ lcol, const VT *__restrict__ val,
     const int32_t *__restrict__ blk_seg_begin, const int32_t *__restrict__ blk_W,
     const int32_t *__restrict__ seg_col, const int32_t *__restrict__ seg_off,
     const double *__restrict__ x, const double *__restrict__ x_halo, int32_t n_local,
@@ -452,12 +453,13 @@ __global__ __launch_bounds__(kBlock) void spmv_window_kernel(
     double acc[R];
 #pragma unroll
     for (int i = 0; i < R; ++i) acc[i] = 0.0;
-    const double *vb = val + k_begin;
+    const VT *vb = val + k_begin;
     if (W >= 0) {
       const uint16_t *cb = lcol + k_begin;
       for (int32_t base = 0; base < n_batch; base += 64 * U) {
         int32_t c[U];
-        double v[U], xv[U];
+        VT v[U];
+        double xv[U];
 #pragma unroll
         for (int u = 0; u < U; ++u) {
           const int32_t o = base + 64 * u + lane;
@@ -466,7 +468,7 @@ __global__ __launch_bounds__(kBlock) void spmv_window_kernel(
             v[u] = vb[o];
           } else {
             c[u] = -1;
-            v[u] = 0.0;
+            v[u] = VT(0);
           }
         }
 #pragma unroll
@@ -477,7 +479,7 @@ __global__ __launch_bounds__(kBlock) void spmv_window_kernel(
           if (c[u] >= 0) {
 #pragma unroll
             for (int i = 0; i < R; ++i)
-              if (o >= rel[i] && o < rel[i + 1]) acc[i] = fma(v[u], xv[u], acc[i]);
+              if (o >= rel[i] && o < rel[i + 1]) acc[i] = fma((double)v[u], xv[u], acc[i]);
           }
         }
       }
@@ -490,7 +492,7 @@ __global__ __launch_bounds__(kBlock) void spmv_window_kernel(
           if (o < n_batch) {
             const int32_t c = cb[o];
             const double xv = (c < n_local) ? x[c] : x_halo[c - n_local];
-            const double v = vb[o];
+            const double v = (double)vb[o];
 #pragma unroll
             for (int i = 0; i < R; ++i)
               if (o >= rel[i] && o < rel[i + 1]) acc[i] = fma(v, xv, acc[i]);
@@ -1702,6 +1704,40 @@ __global__ __launch_bounds__(kBlock) void b_combine_kernel(int nseg, int64_t seg
       a.y = a.y + c * v.y;
     }
     st2(out, i, a);
+  }
+}
+
+// out = fl32(val), entry by entry (alfd_set_preconditioner_values): round to nearest even; an image below the smallest
+// normal binary32 is stored as a zero with the sign of the entry.  The cases are decided by compares on the double, so
+// the denormal mode of the conversion instruction never matters:
+//   |a| <  (1 - 2^-24) 2^-126   the image is zero or subnormal (the tie at the bound goes to the even 2^-126);
+//   |a| >  2^-150               ... and not zero (the tie at 2^-150 goes to the even 0): counts[0], "flushed to zero";
+//   |a| >= (2 - 2^-24) 2^127    or a not finite: no finite image (the tie goes to the even infinity): counts[1].
+__global__ __launch_bounds__(256) void round_values_kernel(int64_t nnz, const double *__restrict__ val,
+                                                           float *__restrict__ out,
+                                                           unsigned long long *__restrict__ counts) {
+  const int64_t stride = (int64_t)gridDim.x * 256;
+  unsigned int flushed = 0, bad = 0;
+  for (int64_t k = (int64_t)blockIdx.x * 256 + threadIdx.x; k < nnz; k += stride) {
+    const double a = val[k], m = fabs(a);
+    float f = (float)a;
+    if (m < 0x1.fffffep-127) {
+      f = signbit(a) ? -0.0f : 0.0f;
+      flushed += m > 0x1p-150 ? 1u : 0u;
+    }
+    if (!(m < 0x1.ffffffp127)) {
+      f = 0.0f;
+      bad += 1u;
+    }
+    out[k] = f;
+  }
+  for (int o = 32; o > 0; o >>= 1) {
+    flushed += __shfl_xor(flushed, o, 64);
+    bad += __shfl_xor(bad, o, 64);
+  }
+  if ((threadIdx.x & 63) == 0) {
+    if (flushed) atomicAdd(&counts[0], (unsigned long long)flushed);
+    if (bad) atomicAdd(&counts[1], (unsigned long long)bad);
   }
 }
 

@@ -47,6 +47,8 @@ ABI_SYMBOLS = [
     "alfd_get_matrix_shape", "alfd_get_operator_shape", "alfd_bench_operator", "alfd_host_small_shape",
     "alfd_host_sparse_product", "alfd_sparse_product", "alfd_smoothed_prolongator",
     "alfd_setup_coupling", "alfd_get_setup_counts",
+    "alfd_set_preconditioner_values", "alfd_get_preconditioner_values", "alfd_spmv_preconditioner",
+    "alfd_bench_spmv_preconditioner",
 ]
 
 
@@ -174,6 +176,10 @@ def load_library():
         "alfd_precond_apply_device": (C.c_int, [vp, PP, PP, C.POINTER(_abi.Result), vp]),
         "alfd_system_apply_device": (C.c_int, [vp, PP, PP, vp]),
         "alfd_augment_rhs_device": (C.c_int, [vp, PP, vp]),
+        "alfd_set_preconditioner_values": (C.c_int, [vp, C.c_int]),
+        "alfd_get_preconditioner_values": (C.c_int, [vp, C.POINTER(_abi.PrecValuesInfo)]),
+        "alfd_spmv_preconditioner": (C.c_int, [vp, vp, vp, C.c_int, dbl]),
+        "alfd_bench_spmv_preconditioner": (C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(dbl)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -670,6 +676,39 @@ class Context:
         ms, nbytes = C.c_double(), C.c_double()
         self._ck(self._lib.alfd_bench_spmv_format(self._h, slot, reps, int(value_index), C.byref(ms),
                                                   C.byref(nbytes)))
+        return ms.value, nbytes.value
+
+    # -- single-precision operator values inside the inner preconditioner
+    def set_preconditioner_values(self, kind):
+        """"fp32": the inner preconditioner applies slot A through a binary32 copy of its values where the storage
+        form allows it (preconditioner_values() says whether, and why not); "fp64" (the default): as always.  A call
+        that changes the request un-sets the context up, like configure."""
+        if kind not in _abi.PREC_VALUES_BY_NAME:
+            raise ValueError(f"preconditioner values {kind!r}: 'fp32' or 'fp64'")
+        self._ck(self._lib.alfd_set_preconditioner_values(self._h, _abi.PREC_VALUES_BY_NAME[kind]))
+
+    def preconditioner_values(self):
+        """alfd_get_preconditioner_values as a dict; reason_name / family_name spell the two enums out."""
+        info = _abi.PrecValuesInfo()
+        self._ck(self._lib.alfd_get_preconditioner_values(self._h, C.byref(info)))
+        out = {k: getattr(info, k) for k, _ in info._fields_ if k != "reserved"}
+        out["reason_name"] = _abi.PREC_VALUES_REASON_NAMES[info.reason]
+        out["family_name"] = _abi.PREC_VALUES_FAMILY_NAMES[info.family] if info.stored else None
+        return out
+
+    def spmv_preconditioner(self, x, y, mode=0, alpha=1.0):
+        """y = A~ x (mode 0) or fma(alpha, A~ x, y) (mode 1) on the binary32 copy of slot A, through the dispatch the
+        multigrid cycle uses (alfd_spmv_preconditioner).  y is uploaded as given; returns a copy.  AlfdError with
+        status E_UNSUPPORTED when no copy is stored."""
+        x = np.ascontiguousarray(x, np.float64)
+        y = np.ascontiguousarray(y, np.float64).copy()
+        self._ck(self._lib.alfd_spmv_preconditioner(self._h, x.ctypes.data, y.ctypes.data, int(mode), float(alpha)))
+        return y
+
+    def bench_spmv_preconditioner(self, reps=20):
+        """(ms per launch, bytes streamed by format) of y = A~ x, as bench_spmv."""
+        ms, nbytes = C.c_double(), C.c_double()
+        self._ck(self._lib.alfd_bench_spmv_preconditioner(self._h, reps, C.byref(ms), C.byref(nbytes)))
         return ms.value, nbytes.value
 
     def matrix_info(self, slot):

@@ -862,6 +862,75 @@ int alfd_host_stream_plan_short(int64_t nrows, const int64_t *row_ptr, const int
  * matrix through the 10 B/nnz window kernel); streamed_bytes as in alfd_matrix_info. */
 int alfd_bench_spmv_format(alfd_ctx_t ctx, int slot, int32_t reps, int use_value_index,
                            double *ms_per_launch, double *streamed_bytes);
+/* ---------------------------------------- single-precision operator values inside the inner preconditioner
+ * (DESIGN.md section 6).  Opt-in, default ALFD_PREC_VALUES_FP64: nothing changes until the setter is called.
+ *
+ * With ALFD_PREC_VALUES_FP32 the library keeps, next to the 8-byte values of slot ALFD_A, the operator
+ *   A~ = fl32(A) entry by entry: round to nearest even to IEEE binary32; an image that would be subnormal
+ *   (0 < |fl32(a)| < 2^-126) is stored as a zero with the sign of a; an entry without a finite image (|a| beyond
+ *   FLT_MAX, or a not finite) makes the whole copy ineligible and nothing is stored.
+ * A kernel on A~ loads a float, widens it (exact) and forms the fma chains of the 8-byte kernels in the canonical
+ * order, so A~ x has, bit for bit, the value alfd_spmv gives on a matrix that holds the rounded values.  The copy costs
+ * 4 B per entry of device memory and is made on the device from the resident values (no second upload).  Row pointers,
+ * columns and window tables are shared; one launch streams 6 instead of 10 B per entry on the window kernel, 8
+ * instead of 12 on the streaming and plain kernels.
+ *
+ * The copy exists ("stored") when the request is on and slot ALFD_A uses 64 lanes per row, is not in the sparse-row
+ * form, holds no dictionary-coded entries (batch-major or value-indexed: those stream fewer bytes already and stay
+ * exact), lives on a single-rank context, and every image is finite.  It is made at alfd_set_matrix(ALFD_A), or by the
+ * setter when A is resident, and released when the request is dropped or A is replaced.
+ *
+ * It is "used", decided at alfd_setup, when it is stored and alfd_config::inner_prec is
+ *   ALFD_PREC_MULTILEVEL: every application of the level-0 operator of the block-0 hierarchy inside the cycle (smoother
+ *     steps, the residual before the restriction, the residual before the post-smoothing), also as the block-0 half
+ *     of AL_ELL_IDEAL's block-diagonal preconditioner;
+ *   ALFD_PREC_CHEBYSHEV on the augmented (1,1) block (cheb_degree > 1): the A product inside the sweep.
+ * Everything else stays as it is: alfd_setup computes what it computes without the option (diagonals, every
+ * lambda_max -- alfd_result::lambda_max is bit-equal -- and all Galerkin products come from the 8-byte values); the
+ * patch operators, the levels >= 1, A2 and its hierarchy, C, Ct, B, Bt, M, Mp, the operator of the inner CG and the
+ * outer system keep their 8-byte values.  The inner preconditioner stays a fixed symmetric linear operator
+ * (fl32(a_ij) = fl32(a_ji)); the residuals and the Krylov vectors are those of the exact operator, so the accuracy of
+ * the solve is unchanged -- only iteration counts may move.  Caveat: A~ differs from A by up to 2^-24 relative per
+ * entry; for an A whose condition number approaches 1e7 the smoother's operator may lose definiteness in its lowest
+ * modes.  The option is meant for operators well below that (the finite-element blocks here: 1e4 .. 1e5).
+ *
+ * alfd_set_preconditioner_values: an unknown kind is ALFD_E_INVALID.  A call that changes the request on a set-up
+ *   context un-sets it up like alfd_configure (solves answer ALFD_E_NOT_SETUP, alfd_setup_coupling ALFD_E_INVALID with
+ *   "needs alfd_setup"); a call that changes nothing leaves the setup alone.  On a partitioned context the request is
+ *   accepted and stays ineligible (PARTITIONED): decided locally, the same answer on every rank, no exchange.
+ * alfd_get_preconditioner_values: see the struct.  alfd_setup_coupling keeps the copy, like the rest of slot A.
+ * alfd_spmv_preconditioner: y = A~ x (mode 0) or y = fma(alpha, A~ x, y) (mode 1) on host data through the dispatch the
+ *   cycle uses; needs no setup.  ALFD_E_UNSUPPORTED, y untouched, when the copy is not stored.
+ * alfd_bench_spmv_preconditioner: alfd_bench_spmv on the copy; streamed_bytes = streamed_bytes_fp32 of the struct.
+ * Null ctx, out, x or y: ALFD_E_INVALID. */
+enum alfd_prec_values { ALFD_PREC_VALUES_FP64 = 0, ALFD_PREC_VALUES_FP32 = 1 };
+enum alfd_prec_values_reason {
+  ALFD_PREC_VALUES_NONE = 0,            /* stored and used */
+  ALFD_PREC_VALUES_NOT_REQUESTED = 1,
+  ALFD_PREC_VALUES_NO_MATRIX = 2,       /* slot A not set yet */
+  ALFD_PREC_VALUES_SHORT_ROWS = 3,      /* fewer than 64 lanes per row */
+  ALFD_PREC_VALUES_SPARSE_ROWS = 4,
+  ALFD_PREC_VALUES_DICTIONARY_FORM = 5, /* batch-major or value-indexed entries */
+  ALFD_PREC_VALUES_PARTITIONED = 6,
+  ALFD_PREC_VALUES_OUT_OF_RANGE = 7,    /* an entry without a finite binary32 image */
+  ALFD_PREC_VALUES_NOT_APPLIED = 8      /* stored, but the configured variant / inner_prec never applies slot A inside
+                                         * the inner preconditioner; also before a setup */
+};
+typedef struct alfd_prec_values_info {
+  int32_t requested, stored, used;
+  int32_t reason;                       /* alfd_prec_values_reason */
+  int32_t family;                       /* kernel family of the copy: 0 plain, 1 stream, 2 window (stored only) */
+  int32_t reserved;
+  int64_t nnz;                          /* of slot A (0 without a matrix) */
+  int64_t flushed_to_zero;              /* entries whose image would be subnormal */
+  int64_t copy_bytes;                   /* device memory of the copy */
+  double streamed_bytes_fp64, streamed_bytes_fp32;   /* format bytes of one launch on the 8-byte values / on the copy */
+} alfd_prec_values_info;
+int alfd_set_preconditioner_values(alfd_ctx_t ctx, int kind);
+int alfd_get_preconditioner_values(alfd_ctx_t ctx, alfd_prec_values_info *out);
+int alfd_spmv_preconditioner(alfd_ctx_t ctx, const double *x, double *y, int mode, double alpha);
+int alfd_bench_spmv_preconditioner(alfd_ctx_t ctx, int32_t reps, double *ms_per_launch, double *streamed_bytes);
+
 /* Row-block hint for the batch-major SpMV format of a long-row matrix (tunable "batch_major" = 1):
  * a partition of the rows of `slot` into blocks of at most 250 rows -- rows[block_ptr[b] .. block_ptr[b+1])
  * -- whose columns are close together, e.g. bricks of the mesh (all components of the nodes of a

@@ -232,6 +232,10 @@ class System {
     set_matrix(ALFD_M, mass_matrix);
     w_inverse_ = mode;
   }
+  // Single-precision operator values inside the inner preconditioner (alfd_set_preconditioner_values; alfd.h has the
+  // contract and the caveat): ALFD_PREC_VALUES_FP32 before set_matrix(ALFD_A, ...) or after it, before setup().  For a
+  // matrix with general values (locally refined meshes, variable coefficients); dictionary-coded operators ignore it.
+  void set_preconditioner_values(int kind) { check(alfd_set_preconditioner_values(ctx_, kind)); }
   // multi-GPU: one System per rank (alfd.h: alfd_comm_init / alfd_set_partition), before any set_matrix
   void comm_init(int rank, int nranks, const void *unique_id, size_t bytes) {
     check(alfd_comm_init(ctx_, rank, nranks, unique_id, bytes));
