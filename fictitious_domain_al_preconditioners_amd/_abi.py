@@ -109,6 +109,26 @@ class MatrixInfo(C.Structure):
     ]
 
 
+# enum alfd_spmv_family (alfd_get_last_spmv_launch)
+SPMV_PLAIN, SPMV_SPARSE_ROWS, SPMV_STREAM, SPMV_WINDOW, SPMV_WINDOW_VI, SPMV_WINDOW_VIB, SPMV_WINDOW_GROUP, \
+    SPMV_BATCH_MAJOR, SPMV_BATCH_MAJOR_SHORT, SPMV_PLAIN_F32, SPMV_STREAM_F32, SPMV_WINDOW_F32 = range(12)
+SPMV_NFAMILIES = 12
+SPMV_FAMILY_NAMES = ("plain", "sparse_rows", "stream", "window", "window_vi", "window_vib", "window_group",
+                     "batch_major", "batch_major_short", "plain_f32", "stream_f32", "window_f32")
+
+
+class SpmvLaunch(C.Structure):
+    """alfd_spmv_launch: what the last SpMV launch of a context instantiated."""
+    _fields_ = [
+        ("family", C.c_int32), ("lanes", C.c_int32), ("R", C.c_int32), ("U", C.c_int32), ("nontemporal", C.c_int32),
+        ("epilogue", C.c_int32), ("xcd_order", C.c_int32),
+        ("grid", C.c_int64), ("lds_bytes", C.c_int64),
+    ]
+
+    def as_dict(self):
+        return {k: getattr(self, k) for k, _ in self._fields_}
+
+
 class BatchMajorShape(C.Structure):
     _fields_ = [
         ("batch_major", C.c_int32), ("lanes", C.c_int32),

@@ -36,7 +36,7 @@ ABI_SYMBOLS = [
     "alfd_host_numbering_from_points", "alfd_host_brick_blocks_from_points", "alfd_host_permute_csr",
     "alfd_build_smoothed_aggregation", "alfd_get_prolongator", "alfd_host_smoothed_prolongator",
     "alfd_build_smoothed_aggregation_truncated", "alfd_host_truncate_prolongator",
-    "alfd_inner_prec_apply", "alfd_spmv_scaled", "alfd_spmv_pair",
+    "alfd_inner_prec_apply", "alfd_spmv_scaled", "alfd_spmv_pair", "alfd_get_last_spmv_launch",
     "alfd_estimate_spectrum", "alfd_get_cg_coefficients", "alfd_host_tridiagonal_extremes",
     "alfd_constraint_residual",
     "alfd_set_prolongator_block", "alfd_build_smoothed_aggregation_block", "alfd_get_prolongator_block",
@@ -103,6 +103,7 @@ def load_library():
         "alfd_spmv": (C.c_int, [vp, C.c_int, vp, vp, C.c_int, dbl]),
         "alfd_spmv_scaled": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "alfd_spmv_pair": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
+        "alfd_get_last_spmv_launch": (C.c_int, [vp, C.POINTER(_abi.SpmvLaunch)]),
         "alfd_dot": (C.c_int, [vp, i64, vp, vp, C.POINTER(dbl)]),
         "alfd_inner_prec_apply": (C.c_int, [vp, C.c_int, vp, vp]),
         "alfd_matrix_lanes": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
@@ -612,6 +613,15 @@ class Context:
         self._ck(self._lib.alfd_spmv_pair(self._h, slot_a, slot_c, x.ctypes.data, d.ctypes.data, y.ctypes.data,
                                           t.ctypes.data))
         return y, t
+
+    def last_spmv_launch(self):
+        """What the last SpMV launch of this context instantiated (alfd_get_last_spmv_launch), as a dict with the
+        family's name beside its number; AlfdError with status E_NOT_SETUP before the first launch."""
+        rec = _abi.SpmvLaunch()
+        self._ck(self._lib.alfd_get_last_spmv_launch(self._h, C.byref(rec)))
+        out = rec.as_dict()
+        out["family_name"] = _abi.SPMV_FAMILY_NAMES[rec.family]
+        return out
 
     def dot(self, x, y):
         x = np.ascontiguousarray(x, np.float64)

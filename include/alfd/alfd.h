@@ -712,6 +712,41 @@ int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d,
  * w_inverse != diagonal, aug_assembled, grad_div_in_A = 0.  ALFD_E_INVALID for a null ctx, x, d, y or t, an unset
  * slot, and t == y. */
 int alfd_spmv_pair(alfd_ctx_t ctx, int slot_a, int slot_c, const double *x, const double *d, double *y, double *t);
+/* What the last SpMV launch of this context instantiated: written on the host beside every kernel launch of the SpMV
+ * launchers, from the template arguments of that launch (not from the settings that chose it), so that a test or a
+ * measuring session can tell which kernel a setting reached -- a shape no dispatch list names falls through to another
+ * family without a word ("Launch shapes from the environment").  The split launch of a partitioned
+ * long-row batch-major operator records its second half; a pair launch records A's family.  A call that launches
+ * nothing (no entries on this rank) leaves the record as it was.
+ *   lanes        lanes per row (64 for the long-row families)
+ *   R, U         rows per batch and 64-entry chunks in flight of the stream / window / group kernels; R and J of
+ *                WINDOW_VI; BATCH_MAJOR: R = waves per workgroup, U = 1 with wide codes; else 0
+ *   nontemporal  1: the stream kernel with non-temporal loads
+ *   epilogue     0 y = s, 1 y = fma(alpha, s, y), 2 y = d .* s, 3 y = s and y2 = d .* s
+ *   xcd_order    the block-order argument the window / class-batched / batch-major kernel was launched with; else 0
+ *   grid         workgroups launched (a pair launch: both parties); lds_bytes: dynamic LDS of one workgroup
+ * ALFD_E_NOT_SETUP before the first SpMV launch of the context, ALFD_E_INVALID for a null ctx or out. */
+enum alfd_spmv_family {
+  ALFD_SPMV_PLAIN = 0,              /* spmv_kernel<L>: one row per group of L lanes */
+  ALFD_SPMV_SPARSE_ROWS = 1,        /* the same on the list of non-empty rows */
+  ALFD_SPMV_STREAM = 2,             /* spmv_stream_kernel<R, U> */
+  ALFD_SPMV_WINDOW = 3,             /* spmv_window_kernel<R, U> */
+  ALFD_SPMV_WINDOW_VI = 4,          /* spmv_window_vi_kernel<R, J>: dictionary-coded values, in-order batches */
+  ALFD_SPMV_WINDOW_VIB = 5,         /* spmv_window_vib_kernel: dictionary-coded values, class-sorted batches */
+  ALFD_SPMV_WINDOW_GROUP = 6,       /* spmv_window_group_kernel<L, R, U>: short rows */
+  ALFD_SPMV_BATCH_MAJOR = 7,        /* spmv_vs_kernel: long rows */
+  ALFD_SPMV_BATCH_MAJOR_SHORT = 8,  /* spmv_vss_kernel<L>: short rows */
+  ALFD_SPMV_PLAIN_F32 = 9,          /* the single-precision copy of slot A on the three families it has */
+  ALFD_SPMV_STREAM_F32 = 10,
+  ALFD_SPMV_WINDOW_F32 = 11,
+  ALFD_SPMV_NFAMILIES = 12
+};
+typedef struct alfd_spmv_launch {
+  int32_t family;   /* enum alfd_spmv_family */
+  int32_t lanes, R, U, nontemporal, epilogue, xcd_order;
+  int64_t grid, lds_bytes;
+} alfd_spmv_launch;
+int alfd_get_last_spmv_launch(alfd_ctx_t ctx, alfd_spmv_launch *out);
 int alfd_dot(alfd_ctx_t ctx, int64_t n, const double *x, const double *y, double *result);
 /* z = M^-1 r: ONE application of the preconditioner of the inner CG, with no CG around it -- exactly the operator
  * the configured variant's inner solve calls once per iteration (alfd_config::inner_prec: identity, Jacobi, the
