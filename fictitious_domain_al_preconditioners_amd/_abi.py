@@ -129,6 +129,23 @@ class SpmvLaunch(C.Structure):
         return {k: getattr(self, k) for k, _ in self._fields_}
 
 
+# modes of alfd_tail_step
+TAIL_STEP, TAIL_LAST, TAIL_LAST_ADD, TAIL_RES, TAIL_RES_INIT, TAIL_RES_INIT_ADD = range(6)
+
+
+class TailStep(C.Structure):
+    """alfd_tail_step: one smoother step of a factored operator for alfd_spmv_tail_step."""
+    _fields_ = [
+        ("mode", C.c_int32), ("store_res", C.c_int32), ("slot_c", C.c_int32), ("reserved", C.c_int32),
+        ("gamma", C.c_double), ("c1", C.c_double), ("c2", C.c_double),
+        ("ct_nrows", C.c_int64), ("ct_ncols", C.c_int64),
+        ("ct_rp", C.c_void_p), ("ct_col", C.c_void_p), ("ct_val", C.c_void_p),
+        ("x", C.c_void_p), ("w", C.c_void_p), ("t", C.c_void_p),
+        ("dinv", C.c_void_p), ("rin", C.c_void_p), ("din", C.c_void_p), ("zin", C.c_void_p),
+        ("y", C.c_void_p), ("res", C.c_void_p), ("d", C.c_void_p), ("z", C.c_void_p), ("zout", C.c_void_p),
+    ]
+
+
 class BatchMajorShape(C.Structure):
     _fields_ = [
         ("batch_major", C.c_int32), ("lanes", C.c_int32),

@@ -104,6 +104,7 @@ struct DevCsr {
     bool on = false, bricks = false;
     int64_t nb = 0, nseg = 0, stream_bytes = 0, nbatch = 0, dict_total = 0, shared_nnz = 0;
     int32_t stride = 0, maxW = 0;
+    int32_t tail_lds = 0;          // long rows: max over the blocks of vs_tail_lds_need, the LDS behind the dictionary region that a launch with the block-end epilogue asks for
     int32_t L = 64, tab_u64 = 16;  // lanes per row of the format; descriptor words per batch
     int32_t wide = 0;              // 10-bit codes / 11-bit window columns (VsFmt<1>)
     int32_t RB = 0, NW = 4;        // long rows: rows per block the plan was made with, waves per workgroup of its launches
@@ -181,6 +182,7 @@ struct MlLevel {
   LevelStore loc, rep;
   double lmax = 0;
   uint8_t *tail_mask = nullptr;   // loc.npad bytes, 1 = row listed in Ct (aug_tail_kernel); null: this level runs unfused
+  double *tail_z2 = nullptr, *tail_d2 = nullptr;   // second iterate / direction vector of a sweep whose tails run inside the A launch (build_tail_vectors); null: they do not
   bool P_global_cols = false;     // loc.P addresses the replicated coarse vector by GLOBAL ids (CSR prolongators)
   // the all-gather of the restricted residual from loc.r into rep.r (first replicated level)
   std::vector<int64_t> offs;      // rank offsets of this level's unknowns (size nranks + 1)
@@ -342,6 +344,8 @@ struct alfd_ctx {
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
   int ml_fuse = 2;                            // fused smoother steps: aug_tail_kernel, pair launches ("ml_fuse", ALFD_ML_FUSE)
+  int ml_tail_in_spmv = 1;                    // "ml_tail_in_spmv", ALFD_ML_TAIL_IN_SPMV: the element-wise tails at the block end of the batch-major A launch
+  int64_t fused_tail_launches = 0;            // launches of that form since alfd_create (alfd_get_fused_tail_launches)
   int ml_tail_rows = 0;                       // "ml_tail_rows": levels >= 1 of hierarchy 1 with at most this many unknowns
                                               // run in one launch (ml_tail_kernel); 0 = off (the measured default)
   int ml_gpu_galerkin = 1;                    // Galerkin products of CSR-prolongator levels on the device (ALFD_ML_GPU_GALERKIN)
@@ -944,7 +948,7 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
   const unsigned grid = (unsigned)n_blocks;
   const int32_t base = (int32_t)first_block;
 #define ALFD_VS_ARGS \
-  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->vs_xcd, base, NoPair()
+  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->vs_xcd, base, NoPair(), NoTail()
 #define ALFD_VS(EPI, NWV)                                                                                        \
   do {                                                                                                           \
     if (v.wide) { /* 10-bit codes: one instantiation per epilogue (4 waves) */                                  \
@@ -1227,7 +1231,7 @@ static int launch_pair(alfd_ctx *ctx, int form, const DevCsr &A, int clsA, const
     note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, NWV, 0, false, 0, ctx->vs_xcd, (int64_t)pc.nA + pc.nC, lds);                   \
     hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, NWV, 0, true>), dim3(pc.nA + pc.nC), dim3(64 * NWV), lds, ctx->stream,       \
                        v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0,  \
-                       (const double *)nullptr, (double *)nullptr, ctx->vs_xcd, 0, pc);                                      \
+                       (const double *)nullptr, (double *)nullptr, ctx->vs_xcd, 0, pc, NoTail());                            \
   } while (0)
 #define ALFD_VS_PAIR_T(TAG)              \
   do {                                   \
@@ -3501,7 +3505,7 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
   v.small = small;
   // block headers and the fixed-stride segment table (the kernel reads one segment past a block's last, and its first
   // round of 8 x 4 segments unconditionally; the descriptor table is read up to 16 batches past a block's last)
-  int32_t max_nseg = 0;
+  int32_t max_nseg = 0, tail_lds = 0, tail_W = 0, tail_cnt = 0, tail_nd = 0;
   for (int64_t b = 0; b < pl.nb; ++b) max_nseg = std::max(max_nseg, pl.seg_begin[b + 1] - pl.seg_begin[b]);
   const int32_t S = std::max(max_nseg + 1, 33);
   if ((double)pl.nb * S * 8.0 > 2.0e9) return ALFD_OK;   // a block with thousands of window pieces: not this format
@@ -3516,6 +3520,8 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
     h[4] = pl.doff[b];
     h[5] = (int32_t)(uint32_t)((uint64_t)pl.sb[b] & 0xffffffffull);
     h[6] = (int32_t)((uint64_t)pl.sb[b] >> 32);
+    const int32_t need = vs_tail_lds_need(pl.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff, pl.dn[b], pl.blkW[b], pl.cnt[b]);
+    if (need > tail_lds) tail_lds = need, tail_W = pl.blkW[b], tail_cnt = pl.cnt[b], tail_nd = pl.dn[b];
     for (int32_t q = 0; q < ns; ++q) {
       segx[((size_t)b * S + q) * 2] = pl.seg_col[s0 + q];
       segx[((size_t)b * S + q) * 2 + 1] = pl.seg_off[s0 + q];
@@ -3538,9 +3544,15 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
   v.dict_total = (int64_t)pl.dict.size();
   v.stride = pl.stride;
   v.maxW = pl.maxW;
+  v.tail_lds = tail_lds;
   v.wide = pl.wide;
   v.bricks = hint;
   v.on = true;
+  if (ctx->cfg.log_level > 0 || std::getenv("ALFD_LOG_UPLOAD"))
+    std::fprintf(stderr, "[alfd] batch-major format, %lld rows: with the row buffer of the block-end epilogue the largest block asks for "
+                 "%d bytes of LDS (dictionary region %d with %d values, %d window slots, %d batches)\n", (long long)m.nrows,
+                 (pl.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + tail_lds, pl.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff,
+                 tail_nd, tail_W, tail_cnt);
   if (ctx->cfg.log_level > 0)
     std::fprintf(stderr,
                  "[alfd] batch-major format%s: %lld blocks (%s), %lld batches, window <= %d slots, %.2f B/nnz, %.1f %% of the "
@@ -4128,6 +4140,7 @@ struct AugOp {   // the operands of one factored operator and the sweep vectors 
   int64_t npad = 0;
   const double *dinv = nullptr;
   double *cd = nullptr, *cres = nullptr, *ctmp = nullptr;
+  double *cd2 = nullptr, *z2 = nullptr;   // levels whose tails may run inside the A launch: the ping-pong partners of cd and of the sweep's iterate
   double lmax = 0;
 };
 
@@ -4160,6 +4173,7 @@ static LevelView level_view(alfd_ctx *ctx, int h, int l) {
   F.npad = S.npad;
   F.dinv = S.dinv;
   F.cd = S.cd, F.cres = S.cres, F.ctmp = S.ctmp;
+  F.cd2 = rep ? nullptr : L.tail_d2, F.z2 = rep ? nullptr : L.tail_z2;
   F.lmax = L.lmax;
   V.r = S.r, V.z = S.z, V.t = S.t;
   if (l + 1 < (int)ctx->hier[h].ml.size()) {
@@ -4228,11 +4242,121 @@ static bool fused_ok(const alfd_ctx *ctx, const AugOp &F) {
          ctx->cfg.w_inverse == ALFD_W_DIAGONAL && F.mask && F.A->present && F.C->present && plain_form(ctx, *F.Ct);
 }
 
-// p.y += gamma Ct tlam, then the element-wise operation of the mode; vec_bytes: per element, of the kernel(s) replaced
-static int aug_tail(alfd_ctx *ctx, const AugOp &F, int mode, const AugTailArgs &p, double vec_bytes) {
+// ---- the tails inside the A launch ("ml_tail_in_spmv").  For a row that Ct does not list the tail is
+// an element-wise expression of the A x value its workgroup has just formed: the batch-major kernel applies it at its
+// block end (TM instantiations of spmv_vs_kernel), the tail launch shrinks to its rows party.
+
+// the LDS per workgroup that keeps eight of them resident on a CU (160 KB), DESIGN section 5
+constexpr size_t kVsTailLdsLimit = 20 * 1024;
+
+// Does A run the instantiations that have the epilogue, within the LDS bound, with fewer than half of its rows in Ct?
+static bool tail_in_form(alfd_ctx *ctx, const DevCsr &A, const DevCsr &Ct, int64_t npad) {
+  if (!A.present || A.sparse || A.n_list == 0 || A.nrows > npad || A.nrows > INT32_MAX) return false;
+  if (!(A.vs.on && ctx->vs_enable && !ctx->vi_off) || A.vs.L != 64 || A.vs.NW != 4 || A.vs.nb <= 0) return false;
+  if ((size_t)(A.vs.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)A.vs.tail_lds > kVsTailLdsLimit) return false;
+  if (!Ct.present || 2 * Ct.n_list >= A.nrows) return false;   // e.g. the patch operator: every row is Ct's, nothing to gain
+  return vs_lds_base_ok(ctx);
+}
+
+static bool tail_in_ok(alfd_ctx *ctx, const AugOp &F) {
+  return ctx->ml_tail_in_spmv && fused_ok(ctx, F) && F.cd2 && F.z2 && !a32_active(ctx, *F.A) &&
+         tail_in_form(ctx, *F.A, *F.Ct, F.npad);
+}
+
+// the vectors mode stores (beside y, which the rows of Ct get)
+static int tail_outputs(int mode, const AugTailArgs &p, const double *out[3]) {
+  int n = 0;
+  if (mode == TAIL_STEP || mode == TAIL_RES || (mode == TAIL_RES_INIT && p.store_res)) out[n++] = p.res;
+  if (mode == TAIL_STEP) out[n++] = p.d;
+  if (mode == TAIL_STEP || mode == TAIL_LAST || mode == TAIL_RES_INIT) out[n++] = p.z;
+  if (mode == TAIL_LAST_ADD || mode == TAIL_RES_INIT_ADD) out[n++] = p.zout;
+  return n;
+}
+static bool tail_writes(int mode, const AugTailArgs &p, const double *y, const double *x) {
+  const double *out[3];
+  const int n = tail_outputs(mode, p, out);
+  bool hit = y == x;
+  for (int i = 0; i < n; ++i) hit = hit || out[i] == x;
+  return hit;
+}
+
+// y = A x with the tail of `mode` on the rows Ct does not list, tlam = w .* (C x) beside it (the second party of the
+// launch where the pair launch applies, a launch of its own where it does not).  Inside the launch other workgroups
+// still stage x while the first ones store: an output that is x would be a race, and is refused here.
+// vec_bytes: per element, of the element-wise kernel(s) the tail stands for (they read y back: 8 of them are not moved,
+// nor are the 8 of the y store).
+static int launch_vs_tail(alfd_ctx *ctx, const AugOp &F, const double *x, double *y, int mode, AugTailArgs p, double vec_bytes) {
+  const DevCsr &A = *F.A;
+  if (mode < TAIL_STEP || mode > TAIL_RES_INIT) return ctx->err = "tail mode without a block-end epilogue", ALFD_E_INVALID;
+  if (!tail_in_form(ctx, A, *F.Ct, F.npad) || !F.mask) return ctx->err = "operator without the block-end epilogue", ALFD_E_UNSUPPORTED;
+  if (!p.zin) p.zin = p.z;
+  if (tail_writes(mode, p, y, x))
+    return ctx->err = "block-end epilogue: an output vector is the vector the product reads", ALFD_E_INVALID;
+  const DevCsr::Vs &v = A.vs;
+  const bool pair = F.C && !v.wide && pair_ok(ctx, A, *F.C) == 1;
+  const bool vi = !ctx->vi_off, vs = ctx->vs_enable != 0 && !ctx->vi_off;
+  const double ew = (vec_bytes - 16.0) * (double)A.nrows;
+  const size_t lds = (size_t)(v.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)v.tail_lds;
+  VsTail ta;
+  ta.p = p;
+  ta.mask = F.mask;
+  {
+    Timer tm(ctx, F.clsA, A.algorithmic_bytes() + (pair ? F.C->algorithmic_bytes() : 0.0) + ew,
+             A.streamed_bytes(vi, vs) + (pair ? F.C->streamed_bytes(vi, vs) : 0.0) + ew);
+    PairC pc{};
+    if (pair) {   // as launch_pair
+      const DevCsr &C = *F.C;
+      pc.nrows = C.n_list, pc.rp = C.rp, pc.col = C.col, pc.val = C.val, pc.x_halo = C.halo, pc.d = F.w, pc.t = F.tlam;
+      pc.n_local = C.n_local_cols, pc.L = C.L;
+      pc.nA = (uint32_t)v.nb;
+      const int64_t rpb = 256 / C.L;
+      pc.nC = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((C.n_list + rpb - 1) / rpb, 256 * 8));
+    }
+    const unsigned grid = (unsigned)v.nb + (pair ? pc.nC : 0u);
+    note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, 4, v.wide ? 1 : 0, false, 0, ctx->vs_xcd, grid, lds);
+#define ALFD_VS_TAIL_ARGS \
+  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0, (const double *)nullptr, \
+      (double *)nullptr, ctx->vs_xcd, 0
+#define ALFD_VS_TAIL(TAG, TM)                                                                                               \
+  do {                                                                                                                      \
+    if (v.wide)                                                                                                             \
+      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 1, false, TM>), dim3(grid), dim3(256), lds, ctx->stream,                \
+                         ALFD_VS_TAIL_ARGS, NoPair(), ta);                                                                  \
+    else if (pair)                                                                                                          \
+      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, true, TM>), dim3(grid), dim3(256), lds, ctx->stream,                 \
+                         ALFD_VS_TAIL_ARGS, pc, ta);                                                                        \
+    else                                                                                                                    \
+      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, false, TM>), dim3(grid), dim3(256), lds, ctx->stream,                \
+                         ALFD_VS_TAIL_ARGS, NoPair(), ta);                                                                  \
+  } while (0)
+#define ALFD_VS_TAIL_M(TAG)                                             \
+  switch (mode) {                                                       \
+    case TAIL_STEP: ALFD_VS_TAIL(TAG, TAIL_STEP); break;                \
+    case TAIL_LAST: ALFD_VS_TAIL(TAG, TAIL_LAST); break;                \
+    case TAIL_LAST_ADD: ALFD_VS_TAIL(TAG, TAIL_LAST_ADD); break;        \
+    case TAIL_RES: ALFD_VS_TAIL(TAG, TAIL_RES); break;                  \
+    default: ALFD_VS_TAIL(TAG, TAIL_RES_INIT); break;                   \
+  }
+    if (A.tag == 0) ALFD_VS_TAIL_M(0)
+    else ALFD_VS_TAIL_M(1)
+#undef ALFD_VS_TAIL_M
+#undef ALFD_VS_TAIL
+#undef ALFD_VS_TAIL_ARGS
+    HIPC(hipGetLastError());
+    ++ctx->fused_tail_launches;
+    if (pair || !F.C) return ALFD_OK;
+  }
+  return spmv_m(ctx, *F.C, ALFD_T_SPMV_OTHER, x, F.tlam, 2, 0.0, F.w);
+}
+
+// p.y += gamma Ct tlam, then the element-wise operation of the mode; vec_bytes: per element, of the kernel(s) replaced.
+// rows_only: the rows of Ct alone -- every other row had its tail at the block end of the A launch (launch_vs_tail)
+static int aug_tail(alfd_ctx *ctx, const AugOp &F, int mode, AugTailArgs p, double vec_bytes, bool rows_only = false) {
   const DevCsr &m = *F.Ct;
+  if (!p.zin) p.zin = p.z;
+  if (rows_only) vec_bytes = 0.0;
   const int nb_rows = m.n_list > 0 ? grid_for_rows(m.n_list, m.L) : 0;
-  const unsigned grid = (unsigned)nb_rows + (unsigned)(F.npad / kChunk);
+  const unsigned grid = (unsigned)nb_rows + (rows_only ? 0u : (unsigned)(F.npad / kChunk));
   if (grid == 0) return ALFD_OK;
   Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes() + vec_bytes * (double)F.npad,
            m.streamed_bytes(false) + vec_bytes * (double)F.npad);
@@ -4261,6 +4385,21 @@ static int aug_tail(alfd_ctx *ctx, const AugOp &F, int mode, const AugTailArgs &
   return ALFD_OK;
 }
 
+// One application of F inside a sweep or a residual: y = A x, tlam = w .* (C x), then the tail of `mode` with p.y = y.
+// x null: y and tlam hold the products already.  Where the level qualifies (tail_in_ok) and no output of the tail is x,
+// the tail of the rows outside Ct runs inside the A launch; a step that must deliver into the vector its own product
+// reads keeps the two launches (no copy pass is added for it).
+static int aug_op_tail(alfd_ctx *ctx, const AugOp &F, const double *x, double *y, int mode, AugTailArgs p, double vec_bytes) {
+  p.y = y;
+  if (!p.zin) p.zin = p.z;
+  if (x && mode <= TAIL_RES_INIT && tail_in_ok(ctx, F) && !tail_writes(mode, p, y, x)) {
+    RC(launch_vs_tail(ctx, F, x, y, mode, p, vec_bytes));
+    return aug_tail(ctx, F, mode, p, vec_bytes, true);
+  }
+  if (x) RC(fused_AC(ctx, F, x, y));
+  return aug_tail(ctx, F, mode, p, vec_bytes);
+}
+
 // The Chebyshev sweep of cheb_sweep on the operands of F.  have_init: z already holds the first
 // direction inv_theta * (dinv .* r) (fused_correct wrote it).  zout: the result is added to zout, z is scratch.
 // The first step reads its direction from z and its residual from r, the last stores neither: after a sweep
@@ -4269,15 +4408,22 @@ static int cheb_fused(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, c
                       bool have_init) {
   ChebCoef k(F.lmax, ratio);
   if (!have_init) VEC_LAUNCH(cheb_init_z_kernel, F.npad, 24, 1.0 / k.theta, F.dinv, r, z);
+  // Where the tails run inside the A launch no step may store into the vector its product reads: the direction
+  // alternates between cd and cd2, and the first step, which multiplies the iterate itself, leaves the new iterate in
+  // z2; later steps read it from there and store it where the caller wants it.  Same expressions, other addresses.
+  const bool pingpong = tail_in_ok(ctx, F);
+  const double *zc = z, *dc = z;   // where the iterate and the direction are (the first direction is the iterate)
   for (int j = 1; j < degree; ++j) {
-    RC(fused_AC(ctx, F, j == 1 ? z : F.cd, F.ctmp));
     AugTailArgs p;
     k.step(p.c1, p.c2);
     p.gamma = F.gamma;
-    p.dinv = F.dinv, p.y = F.ctmp, p.rin = j == 1 ? r : F.cres, p.din = j == 1 ? z : F.cd;
-    p.res = F.cres, p.d = F.cd, p.z = z, p.zout = zout;
     const bool last = j == degree - 1;
-    RC(aug_tail(ctx, F, !last ? TAIL_STEP : zout ? TAIL_LAST_ADD : TAIL_LAST, p, last && zout ? 88.0 : 64.0));
+    p.dinv = F.dinv, p.rin = j == 1 ? r : F.cres, p.din = dc, p.zin = zc;
+    p.res = F.cres, p.zout = zout;
+    p.d = pingpong && dc == F.cd ? F.cd2 : F.cd;
+    p.z = pingpong && !last && dc == z ? F.z2 : z;
+    RC(aug_op_tail(ctx, F, dc, F.ctmp, !last ? TAIL_STEP : zout ? TAIL_LAST_ADD : TAIL_LAST, p, last && zout ? 88.0 : 64.0));
+    dc = p.d, zc = p.z;
   }
   HIPC(hipGetLastError());
   return ALFD_OK;
@@ -4290,23 +4436,38 @@ static int aug_cheb(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, con
                     [&](const double *x, double *y) { return aug_apply(ctx, F, x, y); });
 }
 
-// t = r - Aug x, where t holds A x and tlam holds invW .* (C x)
-static int fused_residual(alfd_ctx *ctx, const AugOp &F, const double *r, double *t) {
+// t = r - Aug x (x null: t holds A x and tlam holds invW .* (C x))
+static int fused_residual(alfd_ctx *ctx, const AugOp &F, const double *x, const double *r, double *t) {
   AugTailArgs p;
-  p.gamma = F.gamma, p.y = t, p.rin = r, p.res = t;
-  return aug_tail(ctx, F, TAIL_RES, p, 24.0);
+  p.gamma = F.gamma, p.rin = r, p.res = t;
+  return aug_op_tail(ctx, F, x, t, TAIL_RES, p, 24.0);
 }
 
 // The residual t = r - Aug x as above and the sweep on it: zc = q(t), or zout += q(t) with zc as scratch
-static int fused_correct(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *r, double *t, double *zc,
-                         double *zout) {
+static int fused_correct(alfd_ctx *ctx, const AugOp &F, int degree, double ratio, const double *x, const double *r, double *t,
+                         double *zc, double *zout) {
   AugTailArgs p;
   p.gamma = F.gamma, p.c1 = 1.0 / ChebCoef(F.lmax, ratio).theta;
-  p.dinv = F.dinv, p.y = t, p.rin = r, p.res = t, p.z = zc, p.zout = zout;
+  p.dinv = F.dinv, p.rin = r, p.res = t, p.z = zc, p.zout = zout;
   p.store_res = degree > 1;
-  if (degree <= 1 && zout) return aug_tail(ctx, F, TAIL_RES_INIT_ADD, p, 24.0 + 32.0 + 24.0);
-  RC(aug_tail(ctx, F, TAIL_RES_INIT, p, 24.0 + (degree > 1 ? 40.0 : 32.0)));
+  if (degree <= 1 && zout) return aug_op_tail(ctx, F, x, t, TAIL_RES_INIT_ADD, p, 24.0 + 32.0 + 24.0);
+  RC(aug_op_tail(ctx, F, x, t, TAIL_RES_INIT, p, 24.0 + (degree > 1 ? 40.0 : 32.0)));
   return cheb_fused(ctx, F, degree, ratio, t, zc, zout, true);
+}
+
+// the ping-pong vectors of level l of hierarchy h, where its operator can run the tails inside the A launch (coupling
+// workspace, as the mask the answer depends on)
+static int build_tail_vectors(alfd_ctx *ctx, int h, int l) {
+  MlLevel &L = ctx->hier[h].ml[l];
+  L.tail_z2 = L.tail_d2 = nullptr;
+  const AugOp F = level_view(ctx, h, l).op;
+  const bool form = L.tail_mask && ctx->nranks == 1 && tail_in_form(ctx, *F.A, *F.Ct, F.npad);
+  if (ctx->cfg.log_level > 0 || std::getenv("ALFD_LOG_UPLOAD"))
+    std::fprintf(stderr, "[alfd] hierarchy %d level %d (%lld rows, %lld in Ct): tails inside the A launch %s\n", h, l,
+                 (long long)F.A->nrows, (long long)F.Ct->n_list, form ? "possible" : "not possible");
+  if (!form) return ALFD_OK;
+  RC(cp_alloc_zero(ctx, h, &L.tail_z2, F.npad));
+  return cp_alloc_zero(ctx, h, &L.tail_d2, F.npad);
 }
 
 // the mask of aug_tail_kernel for the operator of hierarchy h whose Ct is m (coupling workspace: released with it)
@@ -4423,8 +4584,7 @@ static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
   const bool fuse = fused_ok(ctx, F);
   RC(aug_cheb(ctx, F, sdeg, c.ml_smooth_ratio, r, z));                       // pre-smoothing from zero
   if (fuse) {
-    RC(fused_AC(ctx, F, z, L.t));
-    RC(fused_residual(ctx, F, r, L.t));
+    RC(fused_residual(ctx, F, z, r, L.t));
   } else {
     RC(aug_apply(ctx, F, z, L.t));
     VEC_LAUNCH(sub_from_kernel, F.npad, 24, r, L.t);                         // t = r - Aug z
@@ -4442,8 +4602,7 @@ static int ml_cycle(alfd_ctx *ctx, int h, int l, const double *r, double *z) {
     RC(spmv_m(ctx, *L.P, ALFD_T_SPMV_OTHER, L.zc, z, 1, 1.0));               // z += P e_c
   }
   if (fuse) {
-    RC(fused_AC(ctx, F, z, L.t));
-    RC(fused_correct(ctx, F, sdeg, c.ml_smooth_ratio, r, L.t, L.r, z));      // z += post-smoothing of r - Aug z
+    RC(fused_correct(ctx, F, sdeg, c.ml_smooth_ratio, z, r, L.t, L.r, z));   // z += post-smoothing of r - Aug z
     return ALFD_OK;
   }
   RC(aug_apply(ctx, F, z, L.t));
@@ -4516,7 +4675,7 @@ static int ml_apply(alfd_ctx *ctx, const double *r, double *z) {
   if (pen) RC(spmv_AC(ctx, Q.As, ALFD_T_SPMV_OTHER, ctx->mat[ALFD_C], w, z, Q.uS, ctx->t_lam));   // (Aug z) on S
   else RC(spmv_m(ctx, Q.As, ALFD_T_SPMV_OTHER, z, Q.uS, 0));
   if (fused_ok(ctx, F)) {
-    RC(fused_correct(ctx, F, pdeg, pratio, Q.rS, Q.uS, Q.eS, nullptr));
+    RC(fused_correct(ctx, F, pdeg, pratio, nullptr, Q.rS, Q.uS, Q.eS, nullptr));
   } else {
     if (pen) RC(spmv_m(ctx, Q.Cts, ALFD_T_SPMV_OTHER, ctx->t_lam, Q.uS, 1, ctx->cfg.gamma));
     VEC_LAUNCH(sub_from_kernel, Q.mpad, 24, Q.rS, Q.uS);                          // uS = r_S - (Aug z)_S
@@ -6775,7 +6934,10 @@ static int ml_setup(alfd_ctx *ctx, bool full, bool c_changed) {
     ctx->ml_rep_level = rep_from;
   }
   for (int l = 0; l <= nlev; ++l)
+  {
     RC(build_tail_mask(ctx, 0, l == 0 ? ctx->mat[ALFD_CT] : ctx->hier[0].ml[l].loc.Ct, ctx->hier[0].ml[l].loc.npad, &ctx->hier[0].ml[l].tail_mask));
+    RC(build_tail_vectors(ctx, 0, l));
+  }
   return ALFD_OK;
 }
 
@@ -6829,7 +6991,10 @@ static int ml_setup_immersed(alfd_ctx *ctx, bool full, bool c_changed) {
     RC(coarse_inverse(ctx, H.coarse_A, H.coarse_C, H.coarse_Ct, w, c.gamma2, H.inv));
   }
   for (int l = 0; l <= nlev; ++l)
+  {
     RC(build_tail_mask(ctx, 1, l == 0 ? ctx->mat[ALFD_M] : H.ml[l].loc.Ct, H.ml[l].loc.npad, &H.ml[l].tail_mask));
+    RC(build_tail_vectors(ctx, 1, l));
+  }
   return build_tail_table(ctx);
 }
 
@@ -7427,6 +7592,7 @@ int alfd_create(alfd_ctx_t *out, int device_id) {
   if (const char *e = std::getenv("ALFD_ML_REPLICATE")) ctx->ml_rep_threshold = std::atoll(e);
   if (const char *e = std::getenv("ALFD_ML_GPU_GALERKIN")) ctx->ml_gpu_galerkin = std::atoi(e);
   if (const char *e = std::getenv("ALFD_ML_FUSE")) ctx->ml_fuse = std::max(0, std::min(3, std::atoi(e)));
+  if (const char *e = std::getenv("ALFD_ML_TAIL_IN_SPMV")) ctx->ml_tail_in_spmv = std::atoi(e) != 0 ? 1 : 0;
   if (const char *e = std::getenv("ALFD_SPMV_VI_LEVELS")) ctx->vi_levels = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR")) ctx->vs_enable = std::atoi(e);
   if (const char *e = std::getenv("ALFD_SPMV_BATCH_MAJOR_ROWS")) ctx->vs_RB = std::max(4, std::min(kVsMaxRows, std::atoi(e)));
@@ -8846,6 +9012,108 @@ int alfd_spmv_pair(alfd_ctx_t ctx, int slot_a, int slot_c, const double *x, cons
   return rc;
 }
 
+int alfd_get_fused_tail_launches(alfd_ctx_t ctx, int64_t *count) {
+  CHECK_CTX();
+  if (!count) return ALFD_E_INVALID;
+  *count = ctx->fused_tail_launches;
+  return ALFD_OK;
+}
+
+int alfd_spmv_tail_step(alfd_ctx_t ctx, int slot_a, int form, const alfd_tail_step *s) {
+  CHECK_CTX();
+  if (!s || (form != 0 && form != 1) || slot_a < 0 || slot_a >= ALFD_NSLOTS || !ctx->mat[slot_a].present) return ALFD_E_INVALID;
+  if (s->slot_c >= ALFD_NSLOTS || (s->slot_c >= 0 && (!ctx->mat[s->slot_c].present || !s->w))) return ALFD_E_INVALID;
+  if (s->mode < TAIL_STEP || s->mode > TAIL_RES_INIT_ADD || !s->x || !s->y || !s->t || !s->rin || !s->ct_rp) return ALFD_E_INVALID;
+  DevCsr &A = ctx->mat[slot_a];
+  DevCsr *Cm = s->slot_c >= 0 ? &ctx->mat[s->slot_c] : nullptr;
+  const int64_t n = A.nrows, nt = s->ct_ncols;
+  if (s->ct_nrows != n || nt < 1 || (Cm && (Cm->nrows != nt || Cm->ncols != A.ncols))) return ALFD_E_INVALID;
+  const int mode = s->mode;
+  const bool step = mode <= TAIL_LAST_ADD, add = mode == TAIL_LAST_ADD || mode == TAIL_RES_INIT_ADD;
+  const double *outs[3];
+  AugTailArgs hp;   // the caller's (host) vectors in the fields the mode uses
+  hp.dinv = s->dinv, hp.rin = s->rin, hp.din = s->din, hp.zin = s->zin;
+  hp.res = s->res, hp.d = s->d, hp.z = s->z, hp.zout = s->zout, hp.store_res = s->store_res;
+  const int nout = tail_outputs(mode, hp, outs);
+  for (int i = 0; i < nout; ++i)
+    if (!outs[i]) return ALFD_E_INVALID;
+  if ((mode != TAIL_RES && !s->dinv) || (step && (!s->din || !s->zin))) return ALFD_E_INVALID;
+  if (ctx->nranks != 1 || ctx->cfg.w_inverse != ALFD_W_DIAGONAL || ctx->cfg.aug_assembled || gd_nested(ctx))
+    return ctx->err = "alfd_spmv_tail_step: one rank, the diagonal W^-1 and the factored operator", ALFD_E_UNSUPPORTED;
+  static const int32_t no_col = 0;
+  static const double no_val = 0;
+  const bool empty = s->ct_rp[n] == 0;
+  RC(upload_matrix(ctx, kScratchSlot, n, nt, s->ct_rp, empty ? &no_col : s->ct_col, empty ? &no_val : s->ct_val));
+  DevCsr Ct = std::move(ctx->mat[kScratchSlot]);
+  ctx->mat[kScratchSlot] = DevCsr();
+  // the device images: npad entries for the vectors over the rows of A (the sweep of aug_tail_kernel covers the padding),
+  // one image per distinct host address, so that an output passed at x's address IS x on the device
+  const int64_t npad = pad_chunk(n);
+  struct Img { const double *h; double *d; int64_t len; bool out; };
+  std::vector<Img> img;
+  int rc = ALFD_OK;
+  auto dev = [&](const double *h, int64_t len, bool out) -> double * {
+    if (!h) return nullptr;
+    for (Img &g : img)
+      if (g.h == h) return g.out = g.out || out, g.d;
+    const int64_t cap = std::max<int64_t>(std::max(len, npad), 1);
+    double *d = nullptr;
+    if (hipMalloc((void **)&d, cap * sizeof(double)) != hipSuccess) return rc = ALFD_E_HIP, nullptr;
+    hipMemsetAsync(d, 0, cap * sizeof(double), ctx->stream);
+    hipMemcpyAsync(d, h, len * sizeof(double), hipMemcpyHostToDevice, ctx->stream);
+    img.push_back(Img{h, d, len, out});
+    return d;
+  };
+  AugOp F;
+  F.A = &A, F.C = Cm, F.Ct = &Ct;
+  F.clsA = slot_a == ALFD_A ? ALFD_T_SPMV_A : ALFD_T_SPMV_OTHER;
+  F.gamma = s->gamma, F.npad = npad;
+  const double *dx = dev(s->x, A.ncols, false);
+  double *dy = dev(s->y, n, true);
+  F.tlam = dev(s->t, nt, Cm != nullptr);
+  F.w = Cm ? dev(s->w, nt, false) : nullptr;
+  AugTailArgs p;
+  p.gamma = s->gamma, p.c1 = s->c1, p.c2 = s->c2, p.store_res = s->store_res;
+  p.rin = dev(s->rin, n, false);
+  if (mode != TAIL_RES) p.dinv = dev(s->dinv, n, false);
+  if (step) p.din = dev(s->din, n, false), p.zin = dev(s->zin, n, false);
+  // every output vector the caller names is staged and written back, stored by the mode or not: a store that should
+  // not be there shows
+  p.res = dev(s->res, n, true), p.d = dev(s->d, n, true), p.z = dev(s->z, n, true), p.zout = dev(s->zout, n, true);
+  p.y = dy;
+  uint8_t *mask = nullptr;
+  if (rc == ALFD_OK && hipMalloc((void **)&mask, (size_t)npad) != hipSuccess) rc = ALFD_E_HIP;
+  if (rc == ALFD_OK) {
+    hipMemsetAsync(mask, 0, (size_t)npad, ctx->stream);
+    if (Ct.n_list > 0)
+      hipLaunchKernelGGL(mark_rows_kernel, dim3((unsigned)((Ct.n_list + 255) / 256)), dim3(256), 0, ctx->stream, Ct.n_list,
+                         Ct.sparse ? Ct.rows : (const int32_t *)nullptr, mask);
+    F.mask = mask;
+    if (!plain_form(ctx, Ct))
+      rc = (ctx->err = "alfd_spmv_tail_step: Ct is not resident as plain CSR rows", ALFD_E_UNSUPPORTED);
+  }
+  if (rc == ALFD_OK) {
+    if (form == 0) {   // (a): the A launch with the block-end epilogue, then the rows party of the tail
+      rc = launch_vs_tail(ctx, F, dx, dy, mode, p, 0.0);
+      if (rc == ALFD_OK) rc = aug_tail(ctx, F, mode, p, 0.0, true);
+    } else {           // (b): y = A x (with C: the solver's pair launch or its two launches), then the whole tail
+      rc = Cm ? spmv_AC(ctx, A, F.clsA, *Cm, F.w, dx, dy, F.tlam) : spmv_m(ctx, A, F.clsA, dx, dy, 0);
+      if (rc == ALFD_OK) rc = aug_tail(ctx, F, mode, p, 0.0);
+    }
+  }
+  if (rc == ALFD_OK) {
+    for (const Img &g : img)
+      if (g.out) hipMemcpyAsync(const_cast<double *>(g.h), g.d, g.len * sizeof(double), hipMemcpyDeviceToHost, ctx->stream);
+    if (hipStreamSynchronize(ctx->stream) != hipSuccess) rc = ALFD_E_HIP;
+  } else {
+    hipStreamSynchronize(ctx->stream);
+  }
+  for (const Img &g : img) hipFree(g.d);
+  hipFree(mask);
+  csr_free(Ct);
+  return rc;
+}
+
 int alfd_inner_prec_apply(alfd_ctx_t ctx, int op, const double *r, double *z) {
   CHECK_CTX();
   CHECK_SETUP();
@@ -9700,6 +9968,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "ml_fuse") == 0) {   // 0: separate launches; 1: aug_tail; 2: + pair launches; 3: + on the fine level
     ctx->ml_fuse = std::max(0, std::min(3, value));   // as ALFD_ML_FUSE: values outside 0..3 take the nearest level
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "ml_tail_in_spmv") == 0) {   // 1: the element-wise tails of the fused smoother steps at the block end of the A launch
+    if (value != 0 && value != 1) return ctx->err = "ml_tail_in_spmv: 0 or 1", ALFD_E_INVALID;
+    ctx->ml_tail_in_spmv = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "ml_gpu_galerkin") == 0) {   // 0: every Galerkin product of the setup / the builder on the host (next alfd_setup / build)

@@ -1339,11 +1339,13 @@ __global__ __launch_bounds__(kBlock) void cheb_init_z_kernel(double inv_theta, c
 //   TAIL_RES            res = rin - y                                                   stores res
 //   TAIL_RES_INIT       res = rin - y; z = c1 * (dinv .* res)   (c1 = 1 / theta)        stores z (res: store_res)
 //   TAIL_RES_INIT_ADD   the same, then zout = fma(1, z, zout)                           stores zout
-// rin / din may be the arrays res / d / z themselves (every element is read and written by one thread only).
+// rin / din / zin may be the arrays res / d / z themselves (every element is read and written by one thread only); zin is
+// where the step modes read the iterate, z where they store it (the hosts of this file set zin = z unless a sweep
+// ping-pongs the two, see cheb_fused in alfd.hip).
 enum { TAIL_STEP = 0, TAIL_LAST = 1, TAIL_LAST_ADD = 2, TAIL_RES = 3, TAIL_RES_INIT = 4, TAIL_RES_INIT_ADD = 5 };
 struct AugTailArgs {
   double gamma = 0, c1 = 0, c2 = 0;
-  const double *dinv = nullptr, *y = nullptr, *rin = nullptr, *din = nullptr;
+  const double *dinv = nullptr, *y = nullptr, *rin = nullptr, *din = nullptr, *zin = nullptr;
   double *res = nullptr, *d = nullptr, *z = nullptr, *zout = nullptr;
   int store_res = 0;
 };
@@ -1367,7 +1369,7 @@ template <int MODE>
 __device__ __forceinline__ void aug_tail_elem(const AugTailArgs &p, int64_t i, double y) {
   constexpr bool kStep = MODE <= TAIL_LAST_ADD, kAdd = MODE == TAIL_LAST_ADD || MODE == TAIL_RES_INIT_ADD;
   const double dinv = MODE != TAIL_RES ? p.dinv[i] : 0.0, rin = p.rin[i];
-  const double din = kStep ? p.din[i] : 0.0, zin = kStep ? p.z[i] : 0.0, zo = kAdd ? p.zout[i] : 0.0;
+  const double din = kStep ? p.din[i] : 0.0, zin = kStep ? p.zin[i] : 0.0, zo = kAdd ? p.zout[i] : 0.0;
   double res, d = 0.0, z = 0.0, zout = 0.0;
   aug_tail_math<MODE>(p, y, dinv, rin, din, zin, zo, res, d, z, zout);
   if (MODE == TAIL_STEP || MODE == TAIL_RES || (MODE == TAIL_RES_INIT && p.store_res)) p.res[i] = res;
@@ -1422,7 +1424,7 @@ __global__ __launch_bounds__(kBlock) void aug_tail_kernel(int64_t n_list, const 
     const double2 zero = {0.0, 0.0};
     const double2 yv = ld2(p.y, i), rv = ld2(p.rin, i);
     const double2 dv = MODE != TAIL_RES ? ld2(p.dinv, i) : zero;
-    const double2 dd = kStep ? ld2(p.din, i) : zero, zi = kStep ? ld2(p.z, i) : zero;
+    const double2 dd = kStep ? ld2(p.din, i) : zero, zi = kStep ? ld2(p.zin, i) : zero;
     const double2 zo = kAdd ? ld2(p.zout, i) : zero;
     double2 res, d = zero, z = zero, zout = zero;
     aug_tail_math<MODE>(p, yv.x, dv.x, rv.x, dd.x, zi.x, zo.x, res.x, d.x, z.x, zout.x);

@@ -192,16 +192,50 @@ __device__ __forceinline__ void vs_shared(int32_t rem, const int32_t (&sh)[R], i
   }
 }
 
+// The block-end epilogue of the fused smoother steps ("ml_tail_in_spmv"): the element-wise tail of
+// aug_tail_kernel for the rows Ct does not list, inside the launch that forms their A x.
+struct VsTail {
+  AugTailArgs p;
+  const uint8_t *mask;   // 1: a row of Ct -- its y is stored, the rows party of aug_tail_kernel finishes it
+};
+struct NoTail {};
+// LDS behind the dictionary region that a block with nd dictionary entries, W window slots and nbatch batches needs with
+// the row buffer (host and device agree on this split)
+inline __host__ __device__ int32_t vs_tail_lds_need(int32_t dict_region, int32_t nd, int32_t W, int32_t nbatch) {
+  const int32_t gap = (dict_region - 8 * nd) >> 7;
+  return 8 * W + 128 * (nbatch > gap ? nbatch - gap : 0);
+}
+template <int TM>
+using TailArg = typename std::conditional<(TM >= 0), VsTail, NoTail>::type;
+
+__device__ __forceinline__ void vs_lds_store_f64(uint32_t byte_off, double v) {
+  *(__attribute__((address_space(3))) double *)(uintptr_t)byte_off = v;
+}
+template <int TM>
+__device__ __forceinline__ void vs_tail_row(const NoTail &, int32_t, double, double *) {}
+// row r with the operator value v: no output of p may be the vector the launch multiplies (the host refuses that)
+template <int TM>
+__device__ __forceinline__ void vs_tail_row(const VsTail &t, int32_t r, double v, double *y) {
+  if (t.mask[r]) y[r] = v;
+  else aug_tail_elem<TM>(t.p, r, v);
+}
+
 // PAIR (NW = 1, 2 or 4: the second party takes its rows in groups of 64 NW threads): the grid carries a second party behind
 // its first nA workgroups, pair_rows in kernels.hpp.  It owns no LDS, so the absolute LDS offsets of the first party stay right.
-template <int EPI, int TAG, int NW, int WD = 0, bool PAIR = false>
+// TM >= 0 (a TAIL_* mode, EPI 0): the batch loop leaves a row's sum in an LDS row buffer behind the block's window -- slot
+// 16 * (batch of the block) + (row of the batch), 8 bytes each, where it stored y -- and after the loop the workgroup
+// walks the slots: a row Ct lists gets its y stored, every other row goes through aug_tail_elem<TM> and y is NOT stored.
+// The buffer starts in what the block's dictionary leaves of its region and goes on behind the window; the launch asks
+// for the LDS of the block that needs most (DevCsr::Vs::tail_lds, vs_tail_lds_need).
+template <int EPI, int TAG, int NW, int WD = 0, bool PAIR = false, int TM = -1>
 __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8))) void spmv_vs_kernel(
     const uint8_t *__restrict__ stream, const uint64_t *__restrict__ tab, int32_t stride,
     const int32_t *__restrict__ hdrb, const int32_t *__restrict__ segx, int32_t seg_stride,
     const double *__restrict__ dict, const double *__restrict__ x, const double *__restrict__ x_halo,
     int32_t n_local, double *__restrict__ y, double alpha, const double *__restrict__ d, double *__restrict__ y2,
-    int xcd_remap, int32_t block_base, PairArg<PAIR> pc) {
+    int xcd_remap, int32_t block_base, PairArg<PAIR> pc, TailArg<TM> ta) {
   static_assert(!PAIR || NW <= 4, "the second party needs a lane group of 64 within 64 NW <= kBlock threads");
+  static_assert(TM < 0 || EPI == 0, "the block-end epilogue consumes y = A x");
   if (pair_rows<64 * NW>(pc, x)) return;
   extern __shared__ double xs[];
   char *sm = (char *)xs;
@@ -274,9 +308,15 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
   // smaller batch does not have are fillers, -1) instead of selecting it out of the descriptor's scalars.
   const int q16 = lane >> 4;
   const int rsel = 4 * (2 * ((((q16 & 1) << 1) | (q16 >> 1)) + 4 * ((lane >> 3) & 1) + 8 * ((lane >> 2) & 1)) + 1);   // ds_bpermute address of that dword
-  auto store = [&](double s, int32_t r, bool mine) {
+  // TM >= 0: the row buffer, 128 bytes per batch.  The dictionary region is kWinOff bytes whatever the block's dictionary
+  // holds: the first rgap batches use what it leaves free, the others follow the block's window (scalar arithmetic)
+  const int32_t rgap = (VsFmt<WD>::kWinOff - 8 * nd) >> 7;
+  const uint32_t rlow = 8u * (uint32_t)nd, rhigh = VsFmt<WD>::kWinOff + 8u * (uint32_t)W - 128u * (uint32_t)rgap;
+  auto store = [&](double s, int32_t r, bool mine, int32_t bi) {
     if (mine && r >= 0) {
-      if (EPI == 0)
+      if (TM >= 0)   // slot 16 bi + batch row: rsel is 8 (batch row) + 4
+        vs_lds_store_f64((bi < rgap ? rlow : rhigh) + 128u * (uint32_t)bi + (uint32_t)rsel - 4u, s);
+      else if (EPI == 0)
         y[r] = s;
       else if (EPI == 1)
         y[r] = fma(alpha, s, y[r]);
@@ -381,7 +421,7 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
       // the store's acknowledgement, and only then would the next batch's loads go out (two round trips in a row)
       n0 = hdr(hn, 0);
       n1 = hdr(hn, 1);
-      store(reduce_rows4(acc[0], acc[1], acc[2], acc[3]), (int32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hc), (lane & 15) == 0);
+      store(reduce_rows4(acc[0], acc[1], acc[2], acc[3]), (int32_t)__builtin_amdgcn_ds_bpermute(rsel, (int)hc), (lane & 15) == 0, bi);
       mstep = 0;
     }
     // the stream words of the wave's next shared batch (the ONE place of the loop that writes w: no copies of loaded
@@ -397,12 +437,27 @@ __global__ __launch_bounds__(64 * NW) __attribute__((amdgpu_waves_per_eu(8, 8)))
     }
     if (bi + NW < nbatch && (int32_t)n1 < 0) vs_shared_fetch(n0, sbase, lane, w);
     hc = hdr_load(bi + 2 * NW);
-    if (mstep) store(sres, rid, (lane & (mstep - 1)) == 0);
+    if (mstep) store(sres, rid, (lane & (mstep - 1)) == 0, bi);
   };
   for (int32_t bi = wave; bi < nbatch; bi += 2 * NW) {
     batch(hv1, hv2, bi);
     if (bi + NW >= nbatch) break;
     batch(hv2, hv1, bi + NW);
+  }
+  if constexpr (TM >= 0) {
+    // Block end.  Every register of the batch loop is dead here, so the operand loads of the tail cost no occupancy.
+    // Slot s belongs to the row named by dword 2 (s % 16) + 1 of descriptor s / 16 (fillers < 0; bit 31 of row 0 is
+    // the shared-batch flag), which is what the lane that wrote the slot read with ds_bpermute.
+    __syncthreads();
+    // the thread's first slot, made opaque here: left to the compiler, this walk's addresses are formed in front of the
+    // batch loop and one of them lives through it, the register the fine instantiation does not have (12 bytes of scratch)
+    int32_t s0 = 64 * wave + lane;
+    asm volatile("" : "+v"(s0));
+    for (int32_t s = s0; s < 16 * nbatch; s += 64 * NW) {
+      const uint32_t rd = tb[2 * s + 1];
+      const int32_t r = (s & 15) ? (int32_t)rd : (int32_t)(rd & 0x7fffffffu);
+      if (r >= 0) vs_tail_row<TM>(ta, r, vs_lds_f64(((s >> 4) < rgap ? rlow : rhigh) + 8u * (uint32_t)s), y);
+    }
   }
 }
 

@@ -49,6 +49,7 @@ ABI_SYMBOLS = [
     "alfd_setup_coupling", "alfd_get_setup_counts",
     "alfd_set_preconditioner_values", "alfd_get_preconditioner_values", "alfd_spmv_preconditioner",
     "alfd_bench_spmv_preconditioner",
+    "alfd_spmv_tail_step", "alfd_get_fused_tail_launches",
 ]
 
 
@@ -104,6 +105,8 @@ def load_library():
         "alfd_spmv_scaled": (C.c_int, [vp, C.c_int, vp, vp, vp, vp]),
         "alfd_spmv_pair": (C.c_int, [vp, C.c_int, C.c_int, vp, vp, vp, vp]),
         "alfd_get_last_spmv_launch": (C.c_int, [vp, C.POINTER(_abi.SpmvLaunch)]),
+        "alfd_spmv_tail_step": (C.c_int, [vp, C.c_int, C.c_int, C.POINTER(_abi.TailStep)]),
+        "alfd_get_fused_tail_launches": (C.c_int, [vp, C.POINTER(C.c_int64)]),
         "alfd_dot": (C.c_int, [vp, i64, vp, vp, C.POINTER(dbl)]),
         "alfd_inner_prec_apply": (C.c_int, [vp, C.c_int, vp, vp]),
         "alfd_matrix_lanes": (C.c_int, [vp, C.c_int, C.POINTER(i32)]),
@@ -613,6 +616,58 @@ class Context:
         self._ck(self._lib.alfd_spmv_pair(self._h, slot_a, slot_c, x.ctypes.data, d.ctypes.data, y.ctypes.data,
                                           t.ctypes.data))
         return y, t
+
+    def fused_tail_launches(self):
+        """A launches with the block-end epilogue ("ml_tail_in_spmv") since the context was created."""
+        out = C.c_int64()
+        self._ck(self._lib.alfd_get_fused_tail_launches(self._h, C.byref(out)))
+        return out.value
+
+    def spmv_tail_step(self, slot_a, form, mode, ct, x, t, *, gamma=0.0, c1=0.0, c2=0.0, store_res=0, slot_c=-1,
+                       w=None, **vecs):
+        """One smoother step of A + gamma Ct invW C (alfd_spmv_tail_step).  form 0: the A launch with the block-end
+        epilogue, then the rows party of the tail; form 1: y = A x, then the whole tail launch.  ct = (rp, col, val,
+        ncols), the caller's Ct over the rows of slot_a.  vecs: the arrays dinv, rin, din, zin, y, res, d, z, zout the
+        mode uses; an argument given as the string "x", or as the name of a vector earlier in that list, is passed at that
+        vector's address.  Returns a dict with the vectors the
+        call may have written (y, res, d, z, zout as given, and t when slot_c >= 0), as copies."""
+        rp, col, val, ncols = ct
+        rp = np.ascontiguousarray(rp, np.int64)
+        col = np.ascontiguousarray(col, np.int32)
+        val = np.ascontiguousarray(val, np.float64)
+        x = np.ascontiguousarray(x, np.float64).copy()
+        t = np.ascontiguousarray(t, np.float64).copy()
+        s = _abi.TailStep()
+        s.mode, s.store_res, s.slot_c = int(mode), int(store_res), int(slot_c)
+        s.gamma, s.c1, s.c2 = float(gamma), float(c1), float(c2)
+        s.ct_nrows, s.ct_ncols = rp.size - 1, int(ncols)
+        s.ct_rp, s.ct_col, s.ct_val = rp.ctypes.data, col.ctypes.data, val.ctypes.data
+        s.x, s.t = x.ctypes.data, t.ctypes.data
+        keep = [rp, col, val, x, t]
+        if w is not None:
+            w = np.ascontiguousarray(w, np.float64)
+            keep.append(w)
+            s.w = w.ctypes.data
+        out, named = {}, {}
+        for name in ("dinv", "rin", "din", "zin", "y", "res", "d", "z", "zout"):
+            v = vecs.pop(name, None)
+            if v is None:
+                continue
+            if isinstance(v, str):   # "x", or a vector named earlier in the list above: one address, one device vector
+                a = x if v == "x" else named[v]
+            else:
+                a = np.ascontiguousarray(v, np.float64).copy()
+            keep.append(a)
+            named[name] = a
+            setattr(s, name, a.ctypes.data)
+            if name in ("y", "res", "d", "z", "zout"):
+                out[name] = a
+        if vecs:
+            raise TypeError(f"unknown vectors {sorted(vecs)}")
+        self._ck(self._lib.alfd_spmv_tail_step(self._h, int(slot_a), int(form), C.byref(s)))
+        if slot_c >= 0:
+            out["t"] = t
+        return out
 
     def last_spmv_launch(self):
         """What the last SpMV launch of this context instantiated (alfd_get_last_spmv_launch), as a dict with the

@@ -712,6 +712,39 @@ int alfd_spmv_scaled(alfd_ctx_t ctx, int slot, const double *x, const double *d,
  * w_inverse != diagonal, aug_assembled, grad_div_in_A = 0.  ALFD_E_INVALID for a null ctx, x, d, y or t, an unset
  * slot, and t == y. */
 int alfd_spmv_pair(alfd_ctx_t ctx, int slot_a, int slot_c, const double *x, const double *d, double *y, double *t);
+/* One smoother step of a factored operator A + gamma Ct invW C on host data, in either of its two forms (tunable
+ * "ml_tail_in_spmv" below), so that the block-end epilogue of the batch-major kernel can be run at shapes no solver
+ * case reaches.  mode: 0 STEP (res = rin - y, d = fma(c1, din, c2 (dinv res)), z = zin + d; stores res, d, z), 1 LAST
+ * (stores z), 2 LAST_ADD (stores zout = fma(1, z, zout)), 3 RES (stores res), 4 RES_INIT (z = c1 (dinv res); stores z,
+ * and res when store_res), 5 RES_INIT_ADD (stores zout); y stands for A x + gamma Ct t of the row.  Ct is the caller's
+ * CSR (ct_nrows = rows of slot_a, ct_ncols >= 1 columns; it may have no entries), t has ct_ncols entries.  slot_c < 0:
+ * t is read.  slot_c >= 0: t = w .* (C x) is formed beside A x (w, t: the slot's row count = ct_ncols) and returned.
+ * Vectors a mode does not use may be null; all others have the row count of slot_a (x: its column count).  Every vector
+ * is staged on the device once per distinct address, so vectors passed at one address are one device vector.
+ * Outputs are uploaded as given and written back; y receives A x on the rows Ct lists, and on the others only in
+ * form 1 (form 0 never stores it there). */
+typedef struct alfd_tail_step {
+  int32_t mode, store_res, slot_c, reserved;
+  double gamma, c1, c2;
+  int64_t ct_nrows, ct_ncols;
+  const int64_t *ct_rp;
+  const int32_t *ct_col;
+  const double *ct_val;
+  const double *x, *w;
+  double *t;
+  const double *dinv, *rin, *din, *zin;
+  double *y, *res, *d, *z, *zout;
+} alfd_tail_step;
+/* form 0: the A launch with the block-end epilogue, then the rows party of the tail launch.  form 1: y = A x (with
+ * slot_c: the solver's pair launch or its two launches), then the whole tail launch.  Same bits.  Form 0 does not ask
+ * the tunable; it returns ALFD_E_UNSUPPORTED when slot_a has no epilogue instantiation (not on the long-row batch-major
+ * kernel with 4 waves, its largest block beyond 20 KB of LDS with the row buffer, half or more of the rows in Ct, or
+ * mode 5), and ALFD_E_INVALID, with nothing launched, when a vector the mode stores (y included) was passed at x's
+ * address: inside one launch that would be a race.  Both forms: ALFD_E_UNSUPPORTED on a partitioned context, with
+ * w_inverse != diagonal, aug_assembled, grad_div_in_A = 0, or a Ct that does not stay plain CSR rows. */
+int alfd_spmv_tail_step(alfd_ctx_t ctx, int slot_a, int form, const alfd_tail_step *s);
+/* The number of A launches with the block-end epilogue since alfd_create (solver and alfd_spmv_tail_step alike). */
+int alfd_get_fused_tail_launches(alfd_ctx_t ctx, int64_t *count);
 /* What the last SpMV launch of this context instantiated: written on the host beside every kernel launch of the SpMV
  * launchers, from the template arguments of that launch (not from the settings that chose it), so that a test or a
  * measuring session can tell which kernel a setting reached -- a shape no dispatch list names falls through to another
@@ -1042,6 +1075,18 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  and in the environment (before the levels, every non-zero value meant 1).  The first step needs Ct in the plain
  *                  row-per-lane-group form, the second the forms alfd_spmv_pair names; partitioned contexts,
  *                  grad_div_in_A = 0, w_inverse != diagonal and aug_assembled always use the separate launches.
+ *   "ml_tail_in_spmv" (0/1, default 1; environment ALFD_ML_TAIL_IN_SPMV, read at alfd_create, where every non-zero
+ *                  value means 1; here other values are refused with ALFD_E_INVALID): with "ml_fuse" >= 1, the
+ *                  element-wise part of aug_tail_kernel for the rows Ct does NOT list runs at the block end of the
+ *                  launch that forms y = A x (spmv_vs_kernel keeps the row sums of a block in LDS and applies the tail
+ *                  to them; y is neither stored nor read back for those rows), and the tail launch shrinks to the rows
+ *                  of Ct.  Same bits either way; takes effect at the next apply.  Used on a level only when A runs the
+ *                  long-row batch-major kernel with 4 waves, dictionary + window + row buffer of its largest block
+ *                  stay within 20 KB of LDS, and fewer than half of the rows are in Ct; never with the
+ *                  single-precision values of the preconditioner, nor where "ml_fuse" keeps the separate launches.
+ *                  A sweep step that has to deliver into the vector its own product reads (the only step of a
+ *                  degree-2 sweep without a target to add to) keeps the two launches.  Costs two more vectors per
+ *                  level that qualifies.
  *   "ml_gpu_galerkin" (0/1, default 1; environment ALFD_ML_GPU_GALERKIN, read at alfd_create): the Galerkin products of
  *                  alfd_setup with CSR prolongators and of the builders run on the device (alfd_sparse_product; inside
  *                  the builders and on replicated levels only for operators with more than 200 000 entries).  0: all
