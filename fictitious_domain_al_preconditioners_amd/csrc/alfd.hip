@@ -33,7 +33,9 @@
 #include <mutex>
 #include <string>
 #include <thread>
+#include <type_traits>
 #include <unordered_set>
+#include <utility>
 #include <vector>
 
 #include "alfd/alfd.h"
@@ -624,9 +626,55 @@ static void flush_timers(alfd_ctx *ctx) {
 }
 
 // ------------------------------------------------------------------- SpMV
-// The record of alfd_get_last_spmv_launch: every launch macro below calls this beside its hipLaunchKernelGGL with the
-// template arguments it instantiates there and the grid / LDS / block-order arguments it passes, so that the record cannot
-// disagree with the launch.  Host side, a few stores.
+// ---- a run-time value as a template argument.  with_const<Vs...>(v, f) hands f the one of Vs... that v equals, as a
+// std::integral_constant (f reads it as decltype(c)::value), and answers whether there was one.  with_const_or_last gives
+// whatever is not listed to the last listed value: the `else` / `default:` of a hand-written ladder.  Every launcher
+// turns its epilogue, matrix tag, lane count, wave count and tail mode into template arguments with these.
+template <int... Vs, class F>
+static inline bool with_const(int v, F &&f) {
+  return ((v == Vs ? (f(std::integral_constant<int, Vs>()), true) : false) || ...);
+}
+template <int V, int... Vs, class F>
+static inline void with_const_or_last(int v, F &&f) {
+  if constexpr (sizeof...(Vs) == 0) f(std::integral_constant<int, V>());
+  else if (v == V) f(std::integral_constant<int, V>());
+  else with_const_or_last<Vs...>(v, f);
+}
+template <class F> static inline void with_epi(int epi, F &&f) { with_const_or_last<0, 1, 2, 3>(epi, f); }
+template <class F> static inline void with_flag(int flag, F &&f) { with_const_or_last<0, 1>(flag, f); }   // matrix tag, bool
+template <class F> static inline void with_lanes(int L, F &&f) { with_const_or_last<4, 8, 16, 32, 64>(L, f); }
+
+// ---- the (R, U) launch shapes the ALFD_SPMV_* variables select ("Launch shapes from the environment"):
+// each list once, in the order it is searched.  with_shape looks (R, U) up in one of them and hands f the pair as two
+// constants.  A pair the list lacks answers false, and the caller falls through to the next kernel family; with or_last
+// it runs the last entry instead.
+struct Shape { int R, U; };
+constexpr Shape kStreamShapes[] = {{2, 2}, {2, 4}, {4, 2}, {4, 4}, {4, 8}, {8, 4}, {8, 8}, {1, 4}, {2, 8}, {8, 2}};
+constexpr Shape kWindowShapes[] = {{1, 4}, {2, 4}, {2, 8}, {4, 2}, {4, 4}, {4, 8}, {8, 4}, {1, 8}, {1, 16}, {2, 16}};
+constexpr Shape kGroupShapes[] = {{4, 4}, {2, 4}, {4, 2}, {8, 4}, {8, 2}};
+// (R, J) of the in-order value-indexed kernel; the last one is the default
+constexpr Shape kViShapes[] = {{4, 3}, {2, 4}, {4, 4}, {4, 2}};
+// the window kernel on the single-precision copy of A.  (4, 16), the last, is the measured choice (profiles/prec_values/:
+// 0.90 of the 8-byte kernel's time per launch at N = 56, where (2, 8), the shape of the 8-byte kernel, takes 1.18 of it);
+// the other candidates stay selectable for re-measuring
+constexpr Shape kWindow32Shapes[] = {{2, 8}, {4, 8}, {2, 16}, {4, 16}};
+
+template <const auto &Tab, class F, size_t... I>
+static inline bool with_shape_at(size_t i, F &&f, std::index_sequence<I...>) {
+  return ((i == I ? (f(std::integral_constant<int, Tab[I].R>(), std::integral_constant<int, Tab[I].U>()), true) : false) || ...);
+}
+template <const auto &Tab, class F>
+static inline bool with_shape(int R, int U, bool or_last, F &&f) {
+  constexpr size_t N = sizeof(Tab) / sizeof(Shape);
+  size_t i = 0;
+  while (i < N && (Tab[i].R != R || Tab[i].U != U)) ++i;
+  if (i == N && or_last) i = N - 1;
+  return with_shape_at<Tab>(i, f, std::make_index_sequence<N>());
+}
+
+// The record of alfd_get_last_spmv_launch: every launcher below calls this beside its hipLaunchKernelGGL, inside the lambda
+// that holds the template arguments as constants, with those constants and the grid / LDS / block-order arguments it
+// passes, so that the record cannot disagree with the launch.  Host side, a few stores.
 static inline void note_spmv(alfd_ctx *ctx, int family, int lanes, int R, int U, bool nt, int epi, int xcd, int64_t grid,
                              size_t lds) {
   ctx->last_spmv = alfd_spmv_launch{family, lanes, R, U, nt ? 1 : 0, epi, xcd, grid, (int64_t)lds};
@@ -637,186 +685,109 @@ template <int L>
 static void launch_spmv_L(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
                           const double *d, double *y2) {
   const int grid = grid_for_rows(m.n_list, L);
-  const double *xh = m.halo;
-#define ALFD_SPMV(EPI, SP)                                                                            \
-  do {                                                                                                \
-    note_spmv(ctx, SP ? ALFD_SPMV_SPARSE_ROWS : ALFD_SPMV_PLAIN, L, 0, 0, false, EPI, 0, grid, 0);    \
-    hipLaunchKernelGGL((spmv_kernel<L, EPI, SP>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, \
-                       m.rp, m.col, m.val, m.rows, x, xh, m.n_local_cols, y, alpha, d, y2);           \
-  } while (0)
-  if (m.sparse) {
-    if (epi == 0) ALFD_SPMV(0, true);
-    else if (epi == 1) ALFD_SPMV(1, true);
-    else if (epi == 2) ALFD_SPMV(2, true);
-    else ALFD_SPMV(3, true);
-  } else {
-    if (epi == 0) ALFD_SPMV(0, false);
-    else if (epi == 1) ALFD_SPMV(1, false);
-    else if (epi == 2) ALFD_SPMV(2, false);
-    else ALFD_SPMV(3, false);
-  }
-#undef ALFD_SPMV
+  with_epi(epi, [&](auto e) {
+    with_flag(m.sparse, [&](auto sp) {
+      constexpr int EPI = decltype(e)::value;
+      constexpr bool SP = decltype(sp)::value != 0;
+      note_spmv(ctx, SP ? ALFD_SPMV_SPARSE_ROWS : ALFD_SPMV_PLAIN, L, 0, 0, false, EPI, 0, grid, 0);
+      hipLaunchKernelGGL((spmv_kernel<L, EPI, SP>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp, m.col, m.val,
+                         m.rows, x, m.halo, m.n_local_cols, y, alpha, d, y2);
+    });
+  });
+}
+// spmv_kernel at the lane count of m, whatever other forms m has
+static void launch_spmv(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha, const double *d,
+                        double *y2) {
+  with_lanes(m.L, [&](auto l) { launch_spmv_L<decltype(l)::value>(ctx, m, x, y, epi, alpha, d, y2); });
 }
 
-template <int R, int U, bool NT>
-static void launch_stream(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
-                          const double *d, double *y2) {
-  const int64_t nbatches = (m.nrows + R - 1) / R;
-  const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
-#define ALFD_STREAM(EPI)                                                                                 \
-  do {                                                                                                   \
-    note_spmv(ctx, ALFD_SPMV_STREAM, 64, R, U, NT, EPI, 0, grid, 0);                                     \
-    hipLaunchKernelGGL((spmv_stream_kernel<R, U, EPI, NT>), dim3(grid), dim3(kBlock), 0, ctx->stream,    \
-                       m.nrows, m.rp, m.col, m.val, x, m.halo, m.n_local_cols, y, alpha, d, y2, NoPair()); \
-  } while (0)
-  if (epi == 0) ALFD_STREAM(0);
-  else if (epi == 1) ALFD_STREAM(1);
-  else if (epi == 2) ALFD_STREAM(2);
-  else ALFD_STREAM(3);
-#undef ALFD_STREAM
+// workgroups of the stream kernel: 4 waves, a batch of R rows per wave and pass
+static inline int stream_grid(const alfd_ctx *ctx, int64_t nrows, int R) {
+  const int64_t nbatches = (nrows + R - 1) / R;
+  return (int)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
 }
 
 template <bool NT>
 static bool launch_stream_RU(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi,
                              double alpha, const double *d, double *y2) {
-  const int R = ctx->spmv_stream_R, U = ctx->spmv_stream_U;
-#define ALFD_RU(RR, UU) \
-  if (R == RR && U == UU) return launch_stream<RR, UU, NT>(ctx, m, x, y, epi, alpha, d, y2), true
-  ALFD_RU(2, 2); ALFD_RU(2, 4); ALFD_RU(4, 2); ALFD_RU(4, 4); ALFD_RU(4, 8); ALFD_RU(8, 4); ALFD_RU(8, 8);
-  ALFD_RU(1, 4); ALFD_RU(2, 8); ALFD_RU(8, 2);
-#undef ALFD_RU
-  return false;
+  return with_shape<kStreamShapes>(ctx->spmv_stream_R, ctx->spmv_stream_U, false, [&](auto r, auto u) {
+    with_epi(epi, [&](auto e) {
+      constexpr int R = decltype(r)::value, U = decltype(u)::value, EPI = decltype(e)::value;
+      const int grid = stream_grid(ctx, m.nrows, R);
+      note_spmv(ctx, ALFD_SPMV_STREAM, 64, R, U, NT, EPI, 0, grid, 0);
+      hipLaunchKernelGGL((spmv_stream_kernel<R, U, EPI, NT>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.nrows, m.rp,
+                         m.col, m.val, x, m.halo, m.n_local_cols, y, alpha, d, y2, NoPair());
+    });
+  });
 }
 
+// the windowed 64-lane kernels: class-batched value-indexed, in-order value-indexed, general
 template <int R, int U>
 static void launch_window(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
                           const double *d, double *y2) {
-  const size_t lds = (size_t)(m.win_maxW + (m.vi && !ctx->vi_off ? kDictMaxEntries : 0)) * sizeof(double);
-#define ALFD_WIN(EPI, TAG)                                                                                \
-  do {                                                                                                    \
-    note_spmv(ctx, ALFD_SPMV_WINDOW, 64, R, U, false, EPI, ctx->win_xcd, m.win_nblocks, lds);             \
-    hipLaunchKernelGGL((spmv_window_kernel<R, U, EPI, TAG>), dim3((unsigned)m.win_nblocks), dim3(kBlock), \
-                       lds, ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val, m.blk_seg_begin,   \
-                       m.blk_W, m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->win_xcd); \
-  } while (0)
   const bool vi = m.vi && !ctx->vi_off;
-  if (vi && ctx->vi_batched && m.vib_tab) {
-#define ALFD_VIB(EPI, TAG)                                                                                      \
-  do {                                                                                                          \
-    note_spmv(ctx, ALFD_SPMV_WINDOW_VIB, 64, 0, 0, false, EPI, ctx->vi_xcd, m.win_nblocks, lds);                \
-    hipLaunchKernelGGL((spmv_window_vib_kernel<EPI, TAG>), dim3((unsigned)m.win_nblocks), dim3(kBlock), lds,   \
-                       ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W,    \
-                       m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha, d, y2, m.vidx, m.vidw,        \
-                       m.blk_dict_off, m.blk_dict_n, m.dict, m.win_maxW, m.vib_tab, m.vib_cnt, m.vib_stride,    \
-                       ctx->vi_xcd);                                                                            \
-  } while (0)
-    if (m.tag == 0) {
-      if (epi == 0) ALFD_VIB(0, 0);
-      else if (epi == 1) ALFD_VIB(1, 0);
-      else if (epi == 2) ALFD_VIB(2, 0);
-      else ALFD_VIB(3, 0);
+  const size_t lds = (size_t)(m.win_maxW + (vi ? kDictMaxEntries : 0)) * sizeof(double);
+  const dim3 grid((unsigned)m.win_nblocks);
+  with_epi(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (vi && ctx->vi_batched && m.vib_tab) {
+      with_flag(m.tag, [&](auto t) {
+        constexpr int TAG = decltype(t)::value;
+        note_spmv(ctx, ALFD_SPMV_WINDOW_VIB, 64, 0, 0, false, EPI, ctx->vi_xcd, m.win_nblocks, lds);
+        hipLaunchKernelGGL((spmv_window_vib_kernel<EPI, TAG>), grid, dim3(kBlock), lds, ctx->stream, m.nrows, m.win_RB,
+                           m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W, m.seg_col, m.seg_off, x, m.halo,
+                           m.n_local_cols, y, alpha, d, y2, m.vidx, m.vidw, m.blk_dict_off, m.blk_dict_n, m.dict,
+                           m.win_maxW, m.vib_tab, m.vib_cnt, m.vib_stride, ctx->vi_xcd);
+      });
+    } else if (vi && ctx->vi_rows_R > 0) {
+      with_shape<kViShapes>(ctx->vi_rows_R, ctx->vi_rows_J, true, [&](auto rv, auto jv) {
+        constexpr int RV = decltype(rv)::value, JV = decltype(jv)::value;
+        note_spmv(ctx, ALFD_SPMV_WINDOW_VI, 64, RV, JV, false, EPI, 0, m.win_nblocks, lds);
+        hipLaunchKernelGGL((spmv_window_vi_kernel<RV, JV, EPI>), grid, dim3(kBlock), lds, ctx->stream, m.nrows, m.win_RB,
+                           m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W, m.seg_col, m.seg_off, x, m.halo,
+                           m.n_local_cols, y, alpha, d, y2, m.vidx, m.vidw, m.blk_dict_off, m.blk_dict_n, m.dict,
+                           m.win_maxW);
+      });
     } else {
-      if (epi == 0) ALFD_VIB(0, 1);
-      else if (epi == 1) ALFD_VIB(1, 1);
-      else if (epi == 2) ALFD_VIB(2, 1);
-      else ALFD_VIB(3, 1);
+      with_flag(m.tag, [&](auto t) {
+        constexpr int TAG = decltype(t)::value;
+        note_spmv(ctx, ALFD_SPMV_WINDOW, 64, R, U, false, EPI, ctx->win_xcd, m.win_nblocks, lds);
+        hipLaunchKernelGGL((spmv_window_kernel<R, U, EPI, TAG>), grid, dim3(kBlock), lds, ctx->stream, m.nrows, m.win_RB,
+                           m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W, m.seg_col, m.seg_off, x, m.halo,
+                           m.n_local_cols, y, alpha, d, y2, ctx->win_xcd);
+      });
     }
-#undef ALFD_VIB
-    return;
-  }
-  if (vi && ctx->vi_rows_R > 0) {
-    const int RR = ctx->vi_rows_R, JJ = ctx->vi_rows_J;
-#define ALFD_VI(RV, JV, EPI)                                                                                    \
-  do {                                                                                                          \
-    note_spmv(ctx, ALFD_SPMV_WINDOW_VI, 64, RV, JV, false, EPI, 0, m.win_nblocks, lds);                         \
-    hipLaunchKernelGGL((spmv_window_vi_kernel<RV, JV, EPI>), dim3((unsigned)m.win_nblocks), dim3(kBlock), lds,  \
-                       ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W,     \
-                       m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha, d, y2, m.vidx, m.vidw,         \
-                       m.blk_dict_off, m.blk_dict_n, m.dict, m.win_maxW);                                        \
-  } while (0)
-#define ALFD_VI_E(RV, JV)              \
-  if (RR == RV && JJ == JV) {          \
-    if (epi == 0) ALFD_VI(RV, JV, 0);  \
-    else if (epi == 1) ALFD_VI(RV, JV, 1); \
-    else if (epi == 2) ALFD_VI(RV, JV, 2); \
-    else ALFD_VI(RV, JV, 3);           \
-    return;                            \
-  }
-    ALFD_VI_E(4, 3) ALFD_VI_E(2, 4) ALFD_VI_E(4, 4)
-    if (epi == 0) ALFD_VI(4, 2, 0);  // default shape
-    else if (epi == 1) ALFD_VI(4, 2, 1);
-    else if (epi == 2) ALFD_VI(4, 2, 2);
-    else ALFD_VI(4, 2, 3);
-    return;
-#undef ALFD_VI_E
-#undef ALFD_VI
-  }
-  if (m.tag == 0) {
-    if (epi == 0) ALFD_WIN(0, 0);
-    else if (epi == 1) ALFD_WIN(1, 0);
-    else if (epi == 2) ALFD_WIN(2, 0);
-    else ALFD_WIN(3, 0);
-  } else {
-    if (epi == 0) ALFD_WIN(0, 1);
-    else if (epi == 1) ALFD_WIN(1, 1);
-    else if (epi == 2) ALFD_WIN(2, 1);
-    else ALFD_WIN(3, 1);
-  }
-#undef ALFD_WIN
+  });
 }
 
-template <int L, int R, int U>
-static void launch_window_group(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi,
-                                double alpha, const double *d, double *y2) {
-  const size_t lds = (size_t)m.win_maxW * sizeof(double);
-#define ALFD_WING(EPI, TAG)                                                                                 \
-  do {                                                                                                      \
-    note_spmv(ctx, ALFD_SPMV_WINDOW_GROUP, L, R, U, false, EPI, 0, m.win_nblocks, lds);                     \
-    hipLaunchKernelGGL((spmv_window_group_kernel<L, R, U, EPI, TAG>), dim3((unsigned)m.win_nblocks),       \
-                       dim3(kBlock), lds, ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val,        \
-                       m.blk_seg_begin, m.blk_W, m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha, \
-                       d, y2);                                                                              \
-  } while (0)
-  if (m.tag == 0) {
-    if (epi == 0) ALFD_WING(0, 0);
-    else if (epi == 1) ALFD_WING(1, 0);
-    else if (epi == 2) ALFD_WING(2, 0);
-    else ALFD_WING(3, 0);
-  } else {
-    if (epi == 0) ALFD_WING(0, 1);
-    else if (epi == 1) ALFD_WING(1, 1);
-    else if (epi == 2) ALFD_WING(2, 1);
-    else ALFD_WING(3, 1);
-  }
-#undef ALFD_WING
-}
-
+// the windowed kernel of L-lane rows, L < 64
 template <int L>
 static bool launch_window_group_RU(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi,
                                    double alpha, const double *d, double *y2) {
-  const int R = ctx->spmv_group_R, U = ctx->spmv_group_U;
-#define ALFD_RU(RR, UU) \
-  if (R == RR && U == UU) return launch_window_group<L, RR, UU>(ctx, m, x, y, epi, alpha, d, y2), true
-  ALFD_RU(4, 4); ALFD_RU(2, 4); ALFD_RU(4, 2); ALFD_RU(8, 4); ALFD_RU(8, 2);
-#undef ALFD_RU
-  return false;
+  const size_t lds = (size_t)m.win_maxW * sizeof(double);
+  return with_shape<kGroupShapes>(ctx->spmv_group_R, ctx->spmv_group_U, false, [&](auto r, auto u) {
+    with_epi(epi, [&](auto e) {
+      with_flag(m.tag, [&](auto t) {
+        constexpr int R = decltype(r)::value, U = decltype(u)::value, EPI = decltype(e)::value, TAG = decltype(t)::value;
+        note_spmv(ctx, ALFD_SPMV_WINDOW_GROUP, L, R, U, false, EPI, 0, m.win_nblocks, lds);
+        hipLaunchKernelGGL((spmv_window_group_kernel<L, R, U, EPI, TAG>), dim3((unsigned)m.win_nblocks), dim3(kBlock), lds,
+                           ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val, m.blk_seg_begin, m.blk_W, m.seg_col,
+                           m.seg_off, x, m.halo, m.n_local_cols, y, alpha, d, y2);
+      });
+    });
+  });
 }
 
 static bool launch_window_RU(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi,
                              double alpha, const double *d, double *y2) {
-  if (m.L == 32) return launch_window_group_RU<32>(ctx, m, x, y, epi, alpha, d, y2);
-  if (m.L == 16) return launch_window_group_RU<16>(ctx, m, x, y, epi, alpha, d, y2);
-  if (m.L == 8) return launch_window_group_RU<8>(ctx, m, x, y, epi, alpha, d, y2);
+  bool ok = false;
+  if (with_const<32, 16, 8>(m.L, [&](auto l) { ok = launch_window_group_RU<decltype(l)::value>(ctx, m, x, y, epi, alpha, d, y2); }))
+    return ok;
   if (m.L != 64) return false;
-  const int R = ctx->spmv_stream_R, U = ctx->spmv_stream_U;
-#define ALFD_RU(RR, UU) \
-  if (R == RR && U == UU) return launch_window<RR, UU>(ctx, m, x, y, epi, alpha, d, y2), true
-  ALFD_RU(1, 4); ALFD_RU(2, 4); ALFD_RU(2, 8); ALFD_RU(4, 2); ALFD_RU(4, 4); ALFD_RU(4, 8); ALFD_RU(8, 4);
-  ALFD_RU(1, 8); ALFD_RU(1, 16); ALFD_RU(2, 16);
-#undef ALFD_RU
-  return false;
+  return with_shape<kWindowShapes>(ctx->spmv_stream_R, ctx->spmv_stream_U, false, [&](auto r, auto u) {
+    launch_window<decltype(r)::value, decltype(u)::value>(ctx, m, x, y, epi, alpha, d, y2);
+  });
 }
-
 // ---- the single-precision copy of slot A (alfd_set_preconditioner_values): the float instantiations
 // of the three kernel families a 64-lane operator with 8-byte values runs on, epilogues 0 and 1 (all that level 0 of the
 // cycle uses).  A kernel loads a float, widens it (exact) and forms the canonical sums, so the shape of the launch does
@@ -834,87 +805,52 @@ static inline bool a32_active(const alfd_ctx *ctx, const DevCsr &m) {
 // 2 window, 1 stream, 0 plain: the family spmv_launch_local's choice for the 8-byte values belongs to
 static inline int a32_family(const alfd_ctx *ctx, const DevCsr &m) { return m.win ? 2 : ctx->spmv_stream_R > 0 ? 1 : 0; }
 
-template <int R, int U>
-static void launch_window32(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha) {
-  const size_t lds = (size_t)m.win_maxW * sizeof(double);
-#define ALFD_WIN32(EPI)                                                                                          \
-  do {                                                                                                           \
-    note_spmv(ctx, ALFD_SPMV_WINDOW_F32, 64, R, U, false, EPI, ctx->win_xcd, m.win_nblocks, lds);                \
-    hipLaunchKernelGGL((spmv_window_kernel<R, U, EPI, 0, float>), dim3((unsigned)m.win_nblocks), dim3(kBlock),  \
-                       lds, ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val32, m.blk_seg_begin,       \
-                       m.blk_W, m.seg_col, m.seg_off, x, m.halo, m.n_local_cols, y, alpha,                        \
-                       (const double *)nullptr, (double *)nullptr, ctx->win_xcd);                                 \
-  } while (0)
-  if (epi == 0) ALFD_WIN32(0);
-  else ALFD_WIN32(1);
-#undef ALFD_WIN32
-}
-
 static int spmv_launch_a32(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha) {
   if (epi != 0 && epi != 1) return ctx->err = "the single-precision copy of A has epilogues 0 and 1 only", ALFD_E_UNSUPPORTED;
   const int family = a32_family(ctx, m);
-  if (family == 2) {
-    // (4, 16) is the measured choice (profiles/prec_values/: 0.90 of the 8-byte kernel's time per launch at N = 56, where
-    // (2, 8), the shape of the 8-byte kernel, takes 1.18 of it); the other candidates stay selectable for re-measuring
-    if (ctx->a32_R == 2 && ctx->a32_U == 8) launch_window32<2, 8>(ctx, m, x, y, epi, alpha);
-    else if (ctx->a32_R == 4 && ctx->a32_U == 8) launch_window32<4, 8>(ctx, m, x, y, epi, alpha);
-    else if (ctx->a32_R == 2 && ctx->a32_U == 16) launch_window32<2, 16>(ctx, m, x, y, epi, alpha);
-    else launch_window32<4, 16>(ctx, m, x, y, epi, alpha);
-  } else if (family == 1) {   // grid as launch_stream<2, 8, false>
-    const int64_t nbatches = (m.nrows + 1) / 2;
-    const int grid = (int)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
-#define ALFD_STREAM32(EPI)                                                                                            \
-  do {                                                                                                                \
-    note_spmv(ctx, ALFD_SPMV_STREAM_F32, 64, 2, 8, false, EPI, 0, grid, 0);                                           \
-    hipLaunchKernelGGL((spmv_stream_kernel<2, 8, EPI, false, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream, \
-                       m.nrows, m.rp, m.col, m.val32, x, m.halo, m.n_local_cols, y, alpha, (const double *)nullptr,    \
-                       (double *)nullptr, NoPair());                                                                   \
-  } while (0)
-    if (epi == 0) ALFD_STREAM32(0);
-    else ALFD_STREAM32(1);
-#undef ALFD_STREAM32
-  } else {
-    const int grid = grid_for_rows(m.n_list, 64);
-#define ALFD_SPMV32(EPI)                                                                                            \
-  do {                                                                                                              \
-    note_spmv(ctx, ALFD_SPMV_PLAIN_F32, 64, 0, 0, false, EPI, 0, grid, 0);                                          \
-    hipLaunchKernelGGL((spmv_kernel<64, EPI, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list,    \
-                       m.rp, m.col, m.val32, m.rows, x, m.halo, m.n_local_cols, y, alpha, (const double *)nullptr,  \
-                       (double *)nullptr);                                                                          \
-  } while (0)
-    if (epi == 0) ALFD_SPMV32(0);
-    else ALFD_SPMV32(1);
-#undef ALFD_SPMV32
-  }
+  const double *no_d = nullptr;
+  double *no_y2 = nullptr;
+  with_flag(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (family == 2) {
+      const size_t lds = (size_t)m.win_maxW * sizeof(double);
+      with_shape<kWindow32Shapes>(ctx->a32_R, ctx->a32_U, true, [&](auto r, auto u) {
+        constexpr int R = decltype(r)::value, U = decltype(u)::value;
+        note_spmv(ctx, ALFD_SPMV_WINDOW_F32, 64, R, U, false, EPI, ctx->win_xcd, m.win_nblocks, lds);
+        hipLaunchKernelGGL((spmv_window_kernel<R, U, EPI, 0, float>), dim3((unsigned)m.win_nblocks), dim3(kBlock), lds,
+                           ctx->stream, m.nrows, m.win_RB, m.rp, m.col, m.lcol, m.val32, m.blk_seg_begin, m.blk_W, m.seg_col,
+                           m.seg_off, x, m.halo, m.n_local_cols, y, alpha, no_d, no_y2, ctx->win_xcd);
+      });
+    } else if (family == 1) {   // one shape, (2, 8)
+      const int grid = stream_grid(ctx, m.nrows, 2);
+      note_spmv(ctx, ALFD_SPMV_STREAM_F32, 64, 2, 8, false, EPI, 0, grid, 0);
+      hipLaunchKernelGGL((spmv_stream_kernel<2, 8, EPI, false, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream,
+                         m.nrows, m.rp, m.col, m.val32, x, m.halo, m.n_local_cols, y, alpha, no_d, no_y2, NoPair());
+    } else {
+      const int grid = grid_for_rows(m.n_list, 64);
+      note_spmv(ctx, ALFD_SPMV_PLAIN_F32, 64, 0, 0, false, EPI, 0, grid, 0);
+      hipLaunchKernelGGL((spmv_kernel<64, EPI, false, float>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp,
+                         m.col, m.val32, m.rows, x, m.halo, m.n_local_cols, y, alpha, no_d, no_y2);
+    }
+  });
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
-
 
 template <int L>
 static void launch_vss(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
                        const double *d, double *y2) {
   const DevCsr::Vs &v = m.vs;
   const size_t lds = (size_t)kVsWinOff + (size_t)v.maxW * sizeof(double);
-#define ALFD_VSS(EPI, TAG)                                                                                            \
-  do {                                                                                                                \
-    note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR_SHORT, L, 0, 0, false, EPI, 0, v.nb, lds);                                   \
-    hipLaunchKernelGGL((spmv_vss_kernel<L, EPI, TAG>), dim3((unsigned)v.nb), dim3(256), lds, ctx->stream, v.stream, \
-                       v.sb, v.tab, v.cnt, v.stride, v.seg_begin, v.blkW, v.seg_col, v.seg_off, v.doff, v.dn, v.dict, \
-                       x, m.halo, m.n_local_cols, y, alpha, d, y2);                                                   \
-  } while (0)
-  if (m.tag == 0) {
-    if (epi == 0) ALFD_VSS(0, 0);
-    else if (epi == 1) ALFD_VSS(1, 0);
-    else if (epi == 2) ALFD_VSS(2, 0);
-    else ALFD_VSS(3, 0);
-  } else {
-    if (epi == 0) ALFD_VSS(0, 1);
-    else if (epi == 1) ALFD_VSS(1, 1);
-    else if (epi == 2) ALFD_VSS(2, 1);
-    else ALFD_VSS(3, 1);
-  }
-#undef ALFD_VSS
+  with_epi(epi, [&](auto e) {
+    with_flag(m.tag, [&](auto t) {
+      constexpr int EPI = decltype(e)::value, TAG = decltype(t)::value;
+      note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR_SHORT, L, 0, 0, false, EPI, 0, v.nb, lds);
+      hipLaunchKernelGGL((spmv_vss_kernel<L, EPI, TAG>), dim3((unsigned)v.nb), dim3(256), lds, ctx->stream, v.stream, v.sb,
+                         v.tab, v.cnt, v.stride, v.seg_begin, v.blkW, v.seg_col, v.seg_off, v.doff, v.dn, v.dict, x, m.halo,
+                         m.n_local_cols, y, alpha, d, y2);
+    });
+  });
 }
 
 // does dynamic LDS start at offset 0 (vs_lds_base_probe_kernel)?  Asked once per context, at its first batch-major launch
@@ -934,51 +870,46 @@ static bool vs_lds_base_ok(alfd_ctx *ctx) {
   return ctx->vs_lds_base_ok != 0;
 }
 
+// ---- the one launch of spmv_vs_kernel, for the plain product (launch_vs), the pair launch (launch_pair) and the launch
+// with the block-end tail (launch_vs_tail): its argument list, its dynamic LDS and its record.
+// LDS: the x window of the widest block behind the dictionary region; with the tail, what the neediest block takes for
+// window and row buffer (DevCsr::Vs::tail_lds)
+static inline size_t vs_lds(const DevCsr::Vs &v, bool tail) {
+  return (size_t)(v.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (tail ? (size_t)v.tail_lds : (size_t)v.maxW * sizeof(double));
+}
+// grid: the workgroups of both parties; base: the first row block of this launch.  The record has R = waves, U = wide codes.
+template <int EPI, int TAG, int NW, int WD = 0, bool PAIR = false, int TM = -1>
+static void launch_vs_kernel(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, double alpha, const double *d,
+                             double *y2, unsigned grid, int32_t base, PairArg<PAIR> pc = {}, TailArg<TM> ta = {}) {
+  const DevCsr::Vs &v = m.vs;
+  const size_t lds = vs_lds(v, TM >= 0);
+  note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, NW, WD, false, EPI, ctx->vs_xcd, grid, lds);
+  hipLaunchKernelGGL((spmv_vs_kernel<EPI, TAG, NW, WD, PAIR, TM>), dim3(grid), dim3(64 * NW), lds, ctx->stream, v.stream,
+                     v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2,
+                     ctx->vs_xcd, base, pc, ta);
+}
+
 static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
                       const double *d, double *y2, int64_t first_block = 0, int64_t n_blocks = -1) {
   const DevCsr::Vs &v = m.vs;
   if (!vs_lds_base_ok(ctx)) return false;
-  if (v.L == 32) return launch_vss<32>(ctx, m, x, y, epi, alpha, d, y2), true;
-  if (v.L == 16) return launch_vss<16>(ctx, m, x, y, epi, alpha, d, y2), true;
-  if (v.L == 8) return launch_vss<8>(ctx, m, x, y, epi, alpha, d, y2), true;
-  const int NW = v.NW;
-  const size_t lds = (size_t)(v.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)v.maxW * sizeof(double);
+  if (with_const<32, 16, 8>(v.L, [&](auto l) { launch_vss<decltype(l)::value>(ctx, m, x, y, epi, alpha, d, y2); })) return true;
   if (n_blocks < 0) n_blocks = v.nb - first_block;
   if (n_blocks <= 0) return true;
   const unsigned grid = (unsigned)n_blocks;
   const int32_t base = (int32_t)first_block;
-#define ALFD_VS_ARGS \
-  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, m.halo, m.n_local_cols, y, alpha, d, y2, ctx->vs_xcd, base, NoPair(), NoTail()
-#define ALFD_VS(EPI, NWV)                                                                                        \
-  do {                                                                                                           \
-    if (v.wide) { /* 10-bit codes: one instantiation per epilogue (4 waves) */                                  \
-      note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, 4, 1, false, EPI, ctx->vs_xcd, grid, lds);                       \
-      hipLaunchKernelGGL((spmv_vs_kernel<EPI, 0, 4, 1>), dim3(grid), dim3(256), lds, ctx->stream,     \
-                         ALFD_VS_ARGS);                                                                          \
-    } else if (m.tag == 0) {                                                                                     \
-      note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, NWV, 0, false, EPI, ctx->vs_xcd, grid, lds);                     \
-      hipLaunchKernelGGL((spmv_vs_kernel<EPI, 0, NWV>), dim3(grid), dim3(64 * NWV), lds, ctx->stream, \
-                         ALFD_VS_ARGS);                                                                          \
-    } else { /* multigrid level matrix: its own instantiation, so that profiles keep the two apart (8 waves: 4) */  \
-      note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, (NWV > 4 ? 4 : NWV), 0, false, EPI, ctx->vs_xcd, grid, lds);     \
-      hipLaunchKernelGGL((spmv_vs_kernel<EPI, 1, (NWV > 4 ? 4 : NWV)>), dim3(grid), dim3(64 * (NWV > 4 ? 4 : NWV)), lds, \
-                         ctx->stream, ALFD_VS_ARGS);                                                             \
-    }                                                                                                            \
-  } while (0)
-#define ALFD_VS_E(NWV)                  \
-  do {                                  \
-    if (epi == 0) ALFD_VS(0, NWV);      \
-    else if (epi == 1) ALFD_VS(1, NWV); \
-    else if (epi == 2) ALFD_VS(2, NWV); \
-    else ALFD_VS(3, NWV);               \
-  } while (0)
-  if (NW == 8) ALFD_VS_E(8);
-  else if (NW == 2) ALFD_VS_E(2);
-  else if (NW == 1) ALFD_VS_E(1);
-  else ALFD_VS_E(4);
-#undef ALFD_VS_E
-#undef ALFD_VS
-#undef ALFD_VS_ARGS
+  with_epi(epi, [&](auto e) {
+    constexpr int EPI = decltype(e)::value;
+    if (v.wide)   // 10-bit codes: one instantiation per epilogue (4 waves, tag 0)
+      return launch_vs_kernel<EPI, 0, 4, 1>(ctx, m, x, y, alpha, d, y2, grid, base);
+    with_const_or_last<8, 2, 1, 4>(v.NW, [&](auto nw) {
+      with_flag(m.tag, [&](auto t) {
+        // tag 1, a multigrid level matrix: its own instantiation, so that profiles keep the two apart (8 waves: 4)
+        constexpr int TAG = decltype(t)::value, NW = TAG && decltype(nw)::value > 4 ? 4 : decltype(nw)::value;
+        launch_vs_kernel<EPI, TAG, NW>(ctx, m, x, y, alpha, d, y2, grid, base);
+      });
+    });
+  });
   return true;
 }
 
@@ -1046,13 +977,7 @@ static int spmv_launch_local(alfd_ctx *ctx, DevCsr &m, const double *x, double *
       return ALFD_OK;
     }
   }
-  switch (m.L) {
-    case 4: launch_spmv_L<4>(ctx, m, x, y, epi, alpha, d, y2); break;
-    case 8: launch_spmv_L<8>(ctx, m, x, y, epi, alpha, d, y2); break;
-    case 16: launch_spmv_L<16>(ctx, m, x, y, epi, alpha, d, y2); break;
-    case 32: launch_spmv_L<32>(ctx, m, x, y, epi, alpha, d, y2); break;
-    default: launch_spmv_L<64>(ctx, m, x, y, epi, alpha, d, y2); break;
-  }
+  launch_spmv(ctx, m, x, y, epi, alpha, d, y2);
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
@@ -1210,42 +1135,34 @@ static int pair_ok(alfd_ctx *ctx, const DevCsr &A, const DevCsr &C) {
   return ctx->ml_fuse >= (fine ? 3 : 2) ? pair_forms(ctx, A, C) : 0;
 }
 
+// The second party t = w .* (C x) behind the nA workgroups of A, in workgroups of `threads` threads (64 NW of the
+// batch-major kernel, kBlock of the stream kernel): threads / L rows per pass, as many workgroups as cover its rows once,
+// grid-stride beyond.  The launch with the block-end tail always has 4 waves, 256 threads.
+static PairC pair_c(const DevCsr &C, const double *w, double *t, uint32_t nA, int threads) {
+  PairC pc{};
+  pc.nrows = C.n_list, pc.rp = C.rp, pc.col = C.col, pc.val = C.val, pc.x_halo = C.halo, pc.d = w, pc.t = t;
+  pc.n_local = C.n_local_cols, pc.L = C.L;
+  const int64_t rpb = threads / C.L;
+  pc.nA = nA;
+  pc.nC = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((C.n_list + rpb - 1) / rpb, 256 * 8));
+  return pc;
+}
+
 // form: what pair_forms(ctx, A, C) answered, not 0
 static int launch_pair(alfd_ctx *ctx, int form, const DevCsr &A, int clsA, const DevCsr &C, const double *w,
                        const double *x, double *y, double *t) {
   const bool vi = !ctx->vi_off, vs = ctx->vs_enable != 0 && !ctx->vi_off;
   Timer tm(ctx, clsA, A.algorithmic_bytes() + C.algorithmic_bytes(), A.streamed_bytes(vi, vs) + C.streamed_bytes(vi, vs));
-  PairC pc;
-  pc.nrows = C.n_list, pc.rp = C.rp, pc.col = C.col, pc.val = C.val, pc.x_halo = C.halo, pc.d = w, pc.t = t;
-  pc.n_local = C.n_local_cols, pc.L = C.L;
-  pc.nC = (uint32_t)grid_for_rows(C.n_list, C.L);
   if (form == 1) {
-    const DevCsr::Vs &v = A.vs;
-    const size_t lds = (size_t)VsFmt<0>::kWinOff + (size_t)v.maxW * sizeof(double);
-    pc.nA = (uint32_t)v.nb;
-    // the second party works in groups of 64 NW threads: as many workgroups as cover its rows once, grid-stride beyond
-    const int64_t rpb = 64 * v.NW / C.L;
-    pc.nC = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((C.n_list + rpb - 1) / rpb, 256 * 8));
-#define ALFD_VS_PAIR(TAG, NWV)                                                                                               \
-  do {                                                                                                                       \
-    note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, NWV, 0, false, 0, ctx->vs_xcd, (int64_t)pc.nA + pc.nC, lds);                   \
-    hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, NWV, 0, true>), dim3(pc.nA + pc.nC), dim3(64 * NWV), lds, ctx->stream,       \
-                       v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0,  \
-                       (const double *)nullptr, (double *)nullptr, ctx->vs_xcd, 0, pc, NoTail());                            \
-  } while (0)
-#define ALFD_VS_PAIR_T(TAG)              \
-  do {                                   \
-    if (v.NW == 1) ALFD_VS_PAIR(TAG, 1); \
-    else if (v.NW == 2) ALFD_VS_PAIR(TAG, 2); \
-    else ALFD_VS_PAIR(TAG, 4);           \
-  } while (0)
-    if (A.tag == 0) ALFD_VS_PAIR_T(0);
-    else ALFD_VS_PAIR_T(1);
-#undef ALFD_VS_PAIR_T
-#undef ALFD_VS_PAIR
-  } else {   // as launch_stream<2, 8, false>
-    const int64_t nbatches = (A.nrows + 1) / 2;
-    pc.nA = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((nbatches + 3) / 4, 256 * ctx->spmv_grid_mult));
+    const PairC pc = pair_c(C, w, t, (uint32_t)A.vs.nb, 64 * A.vs.NW);
+    with_flag(A.tag, [&](auto tg) {
+      with_const_or_last<1, 2, 4>(A.vs.NW, [&](auto nw) {
+        launch_vs_kernel<0, decltype(tg)::value, decltype(nw)::value, 0, true>(ctx, A, x, y, 0.0, nullptr, nullptr,
+                                                                                 pc.nA + pc.nC, 0, pc);
+      });
+    });
+  } else {   // the stream kernel at (2, 8), kBlock threads
+    const PairC pc = pair_c(C, w, t, (uint32_t)stream_grid(ctx, A.nrows, 2), kBlock);
     note_spmv(ctx, ALFD_SPMV_STREAM, 64, 2, 8, false, 0, 0, (int64_t)pc.nA + pc.nC, 0);
     hipLaunchKernelGGL((spmv_stream_kernel<2, 8, 0, false, true>), dim3(pc.nA + pc.nC), dim3(kBlock), 0, ctx->stream,
                        A.nrows, A.rp, A.col, A.val, x, A.halo, A.n_local_cols, y, 0.0, (const double *)nullptr,
@@ -1644,17 +1561,10 @@ static int pcg_mp_device(alfd_ctx *ctx, const double *b, double *x, int *its_out
       }
       {
         Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes());
-#define ALFD_NMP_S(LL)                                                                                          \
-  hipLaunchKernelGGL((nmp_spmv_kernel<LL>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows, m.rp, m.col, \
-                     m.val, p, Ap)
-        switch (m.L) {
-          case 4: ALFD_NMP_S(4); break;
-          case 8: ALFD_NMP_S(8); break;
-          case 16: ALFD_NMP_S(16); break;
-          case 32: ALFD_NMP_S(32); break;
-          default: ALFD_NMP_S(64); break;
-        }
-#undef ALFD_NMP_S
+        with_lanes(m.L, [&](auto l) {
+          hipLaunchKernelGGL((nmp_spmv_kernel<decltype(l)::value>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows,
+                             m.rp, m.col, m.val, p, Ap);
+        });
       }
       {
         Timer tm(ctx, ALFD_T_DOT, 16.0 * npad);
@@ -1794,16 +1704,7 @@ static int rational_apply(alfd_ctx *ctx, const double *u1, double *v1) {
                        ctx->rt_scb, (int)FIN_RZ);
     hipLaunchKernelGGL(b_p_update_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->rt_scb, cps,
                        it == 1 ? 1 : 0, ctx->rt_z, ctx->rt_p);
-    {
-      const DevCsr &m = ctx->rat_mat;
-      switch (m.L) {
-        case 4: launch_spmv_L<4>(ctx, m, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr); break;
-        case 8: launch_spmv_L<8>(ctx, m, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr); break;
-        case 16: launch_spmv_L<16>(ctx, m, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr); break;
-        case 32: launch_spmv_L<32>(ctx, m, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr); break;
-        default: launch_spmv_L<64>(ctx, m, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr); break;
-      }
-    }
+    launch_spmv(ctx, ctx->rat_mat, ctx->rt_p, ctx->rt_Ap, 0, 0.0, nullptr, nullptr);
     hipLaunchKernelGGL(dot_partial_kernel, dim3(grid), dim3(kBlock), 0, ctx->stream, ctx->rt_p, ctx->rt_Ap,
                        ctx->rt_partial);
     hipLaunchKernelGGL(b_final_kernel, dim3(kRatSystems), dim3(kBlock), 0, ctx->stream, ctx->rt_partial, cps,
@@ -3823,6 +3724,14 @@ static void cp_release(alfd_ctx *ctx, int h) {
 // (w = ALFD_INVW).  The general form takes the weight w, starts from ctx->dA instead of diag(A) when A is
 // null, and with invert = false leaves the sum itself in dinv (which may be ctx->dA): chained calls add
 // several such terms in a fixed order.
+// ctx->dA = diag(A) on the rows of A (the caller zeroes what lies beyond them where it matters)
+static void extract_diag(alfd_ctx *ctx, const DevCsr &A) {
+  const int grid = grid_for_rows(A.nrows, A.L);
+  with_lanes(A.L, [&](auto l) {
+    hipLaunchKernelGGL((extract_diag_kernel<decltype(l)::value>), dim3(grid), dim3(kBlock), 0, ctx->stream, A.nrows, A.rp,
+                       A.col, A.val, ctx->dA);
+  });
+}
 static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *w, double g, int64_t n, double *dinv,
                        bool invert);
 static int diag_plus_m(alfd_ctx *ctx, const DevCsr &A, DevCsr &R, double g, int64_t n, double *dinv) {
@@ -3841,20 +3750,7 @@ static int diag_plus_m(alfd_ctx *ctx, const DevCsr *A, DevCsr &R, const double *
   }
   if (A) HIPC(hipMemsetAsync(ctx->dA, 0, pad_chunk(n) * sizeof(double), ctx->stream));
   HIPC(hipMemsetAsync(ctx->s_aug, 0, pad_chunk(n) * sizeof(double), ctx->stream));
-  if (A) {
-    const int grid = grid_for_rows(A->nrows, A->L);
-#define ALFD_DIAG(LL)                                                                                      \
-  hipLaunchKernelGGL((extract_diag_kernel<LL>), dim3(grid), dim3(kBlock), 0, ctx->stream, A->nrows, A->rp, \
-                     A->col, A->val, ctx->dA)
-    switch (A->L) {
-      case 4: ALFD_DIAG(4); break;
-      case 8: ALFD_DIAG(8); break;
-      case 16: ALFD_DIAG(16); break;
-      case 32: ALFD_DIAG(32); break;
-      default: ALFD_DIAG(64); break;
-    }
-#undef ALFD_DIAG
-  }
+  if (A) extract_diag(ctx, *A);
   // a rank with no rows of R of its own may still own W entries its peers need
   if (ctx->nranks > 1 && (ctx->local || ctx->host_alltoallv || R.n_halo > 0 || R.send_off.back() > 0))
     RC(halo_exchange(ctx, R, w));
@@ -4296,52 +4192,22 @@ static int launch_vs_tail(alfd_ctx *ctx, const AugOp &F, const double *x, double
   const bool pair = F.C && !v.wide && pair_ok(ctx, A, *F.C) == 1;
   const bool vi = !ctx->vi_off, vs = ctx->vs_enable != 0 && !ctx->vi_off;
   const double ew = (vec_bytes - 16.0) * (double)A.nrows;
-  const size_t lds = (size_t)(v.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)v.tail_lds;
   VsTail ta;
   ta.p = p;
   ta.mask = F.mask;
   {
     Timer tm(ctx, F.clsA, A.algorithmic_bytes() + (pair ? F.C->algorithmic_bytes() : 0.0) + ew,
              A.streamed_bytes(vi, vs) + (pair ? F.C->streamed_bytes(vi, vs) : 0.0) + ew);
-    PairC pc{};
-    if (pair) {   // as launch_pair
-      const DevCsr &C = *F.C;
-      pc.nrows = C.n_list, pc.rp = C.rp, pc.col = C.col, pc.val = C.val, pc.x_halo = C.halo, pc.d = F.w, pc.t = F.tlam;
-      pc.n_local = C.n_local_cols, pc.L = C.L;
-      pc.nA = (uint32_t)v.nb;
-      const int64_t rpb = 256 / C.L;
-      pc.nC = (uint32_t)std::max<int64_t>(1, std::min<int64_t>((C.n_list + rpb - 1) / rpb, 256 * 8));
-    }
+    const PairC pc = pair ? pair_c(*F.C, F.w, F.tlam, (uint32_t)v.nb, 256) : PairC{};   // 4 waves (tail_in_form)
     const unsigned grid = (unsigned)v.nb + (pair ? pc.nC : 0u);
-    note_spmv(ctx, ALFD_SPMV_BATCH_MAJOR, 64, 4, v.wide ? 1 : 0, false, 0, ctx->vs_xcd, grid, lds);
-#define ALFD_VS_TAIL_ARGS \
-  v.stream, v.tab, v.stride, v.hdrb, v.segx, v.seg_stride, v.dict, x, A.halo, A.n_local_cols, y, 0.0, (const double *)nullptr, \
-      (double *)nullptr, ctx->vs_xcd, 0
-#define ALFD_VS_TAIL(TAG, TM)                                                                                               \
-  do {                                                                                                                      \
-    if (v.wide)                                                                                                             \
-      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 1, false, TM>), dim3(grid), dim3(256), lds, ctx->stream,                \
-                         ALFD_VS_TAIL_ARGS, NoPair(), ta);                                                                  \
-    else if (pair)                                                                                                          \
-      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, true, TM>), dim3(grid), dim3(256), lds, ctx->stream,                 \
-                         ALFD_VS_TAIL_ARGS, pc, ta);                                                                        \
-    else                                                                                                                    \
-      hipLaunchKernelGGL((spmv_vs_kernel<0, TAG, 4, 0, false, TM>), dim3(grid), dim3(256), lds, ctx->stream,                \
-                         ALFD_VS_TAIL_ARGS, NoPair(), ta);                                                                  \
-  } while (0)
-#define ALFD_VS_TAIL_M(TAG)                                             \
-  switch (mode) {                                                       \
-    case TAIL_STEP: ALFD_VS_TAIL(TAG, TAIL_STEP); break;                \
-    case TAIL_LAST: ALFD_VS_TAIL(TAG, TAIL_LAST); break;                \
-    case TAIL_LAST_ADD: ALFD_VS_TAIL(TAG, TAIL_LAST_ADD); break;        \
-    case TAIL_RES: ALFD_VS_TAIL(TAG, TAIL_RES); break;                  \
-    default: ALFD_VS_TAIL(TAG, TAIL_RES_INIT); break;                   \
-  }
-    if (A.tag == 0) ALFD_VS_TAIL_M(0)
-    else ALFD_VS_TAIL_M(1)
-#undef ALFD_VS_TAIL_M
-#undef ALFD_VS_TAIL
-#undef ALFD_VS_TAIL_ARGS
+    with_flag(A.tag, [&](auto tg) {
+      with_const_or_last<TAIL_STEP, TAIL_LAST, TAIL_LAST_ADD, TAIL_RES, TAIL_RES_INIT>(mode, [&](auto tm_) {
+        constexpr int TAG = decltype(tg)::value, TM = decltype(tm_)::value;
+        if (v.wide) launch_vs_kernel<0, TAG, 4, 1, false, TM>(ctx, A, x, y, 0.0, nullptr, nullptr, grid, 0, NoPair(), ta);
+        else if (pair) launch_vs_kernel<0, TAG, 4, 0, true, TM>(ctx, A, x, y, 0.0, nullptr, nullptr, grid, 0, pc, ta);
+        else launch_vs_kernel<0, TAG, 4, 0, false, TM>(ctx, A, x, y, 0.0, nullptr, nullptr, grid, 0, NoPair(), ta);
+      });
+    });
     HIPC(hipGetLastError());
     ++ctx->fused_tail_launches;
     if (pair || !F.C) return ALFD_OK;
@@ -4360,27 +4226,13 @@ static int aug_tail(alfd_ctx *ctx, const AugOp &F, int mode, AugTailArgs p, doub
   if (grid == 0) return ALFD_OK;
   Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes() + vec_bytes * (double)F.npad,
            m.streamed_bytes(false) + vec_bytes * (double)F.npad);
-#define ALFD_TAIL(LL, MM)                                                                                         \
-  hipLaunchKernelGGL((aug_tail_kernel<LL, MM>), dim3(grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp, m.col,  \
-                     m.val, m.sparse ? m.rows : (const int32_t *)nullptr, F.tlam, nb_rows, F.mask, p)
-#define ALFD_TAIL_L(LL)                                      \
-  switch (mode) {                                            \
-    case TAIL_STEP: ALFD_TAIL(LL, TAIL_STEP); break;         \
-    case TAIL_LAST: ALFD_TAIL(LL, TAIL_LAST); break;         \
-    case TAIL_LAST_ADD: ALFD_TAIL(LL, TAIL_LAST_ADD); break; \
-    case TAIL_RES: ALFD_TAIL(LL, TAIL_RES); break;           \
-    case TAIL_RES_INIT: ALFD_TAIL(LL, TAIL_RES_INIT); break; \
-    default: ALFD_TAIL(LL, TAIL_RES_INIT_ADD); break;        \
-  }
-  switch (m.L) {   // as spmv_launch_local
-    case 4: ALFD_TAIL_L(4) break;
-    case 8: ALFD_TAIL_L(8) break;
-    case 16: ALFD_TAIL_L(16) break;
-    case 32: ALFD_TAIL_L(32) break;
-    default: ALFD_TAIL_L(64) break;
-  }
-#undef ALFD_TAIL_L
-#undef ALFD_TAIL
+  with_lanes(m.L, [&](auto l) {   // as spmv_launch_local
+    with_const_or_last<TAIL_STEP, TAIL_LAST, TAIL_LAST_ADD, TAIL_RES, TAIL_RES_INIT, TAIL_RES_INIT_ADD>(mode, [&](auto md) {
+      hipLaunchKernelGGL((aug_tail_kernel<decltype(l)::value, decltype(md)::value>), dim3(grid), dim3(kBlock), 0, ctx->stream,
+                         m.n_list, m.rp, m.col, m.val, m.sparse ? m.rows : (const int32_t *)nullptr, F.tlam, nb_rows, F.mask,
+                         p);
+    });
+  });
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
@@ -5062,17 +4914,10 @@ static int pcg_cct_device(alfd_ctx *ctx, const alfd_control &ctrl, int *its_out,
   auto product = [&](const DevCsr &m, const double *in, double *out) {
     Timer tm(ctx, ALFD_T_SPMV_OTHER, m.algorithmic_bytes());
     const int sgrid = grid_for_rows(m.nrows, m.L);
-#define ALFD_SPC_S(LL)                                                                                          \
-  hipLaunchKernelGGL((nmp_spmv_kernel<LL>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows, m.rp, m.col, \
-                     m.val, in, out)
-    switch (m.L) {
-      case 4: ALFD_SPC_S(4); break;
-      case 8: ALFD_SPC_S(8); break;
-      case 16: ALFD_SPC_S(16); break;
-      case 32: ALFD_SPC_S(32); break;
-      default: ALFD_SPC_S(64); break;
-    }
-#undef ALFD_SPC_S
+    with_lanes(m.L, [&](auto l) {
+      hipLaunchKernelGGL((nmp_spmv_kernel<decltype(l)::value>), dim3(sgrid), dim3(kBlock), 0, ctx->stream, sc, m.nrows, m.rp,
+                         m.col, m.val, in, out);
+    });
   };
   update(1);
   finish(0);
@@ -7221,23 +7066,9 @@ static int setup(alfd_ctx *ctx) {
   if (rat) {
     // K_inv: Jacobi / Chebyshev-Jacobi CG on K itself
     RC(ws_alloc_zero(ctx, &ctx->dinv_k, n0p));
-    {
-      const DevCsr &A = ctx->mat[ALFD_A];
-      const int grid = grid_for_rows(A.nrows, A.L);
-#define ALFD_DIAG(LL)                                                                                   \
-  hipLaunchKernelGGL((extract_diag_kernel<LL>), dim3(grid), dim3(kBlock), 0, ctx->stream, A.nrows, A.rp, \
-                     A.col, A.val, ctx->dA)
-      switch (A.L) {
-        case 4: ALFD_DIAG(4); break;
-        case 8: ALFD_DIAG(8); break;
-        case 16: ALFD_DIAG(16); break;
-        case 32: ALFD_DIAG(32); break;
-        default: ALFD_DIAG(64); break;
-      }
-#undef ALFD_DIAG
-      hipLaunchKernelGGL(inv_diag_kernel, dim3((unsigned)std::max<int64_t>(1, (ctx->n[0] + 255) / 256)), dim3(256), 0, ctx->stream,
-                         ctx->n[0], ctx->dA, ctx->dinv_k);
-    }
+    extract_diag(ctx, ctx->mat[ALFD_A]);
+    hipLaunchKernelGGL(inv_diag_kernel, dim3((unsigned)std::max<int64_t>(1, (ctx->n[0] + 255) / 256)), dim3(256), 0, ctx->stream,
+                       ctx->n[0], ctx->dA, ctx->dinv_k);
     if (cheb) RC(power_iteration(ctx, OP_K));
     // block-diagonal matrix of the 21 immersed systems, segment s at rows/cols s*npl
     const HostCsr &K = ctx->h_K, &M = ctx->h_M;

@@ -351,24 +351,34 @@ def _function_body(text, head):
     return text[at:text.index("\n}\n", at)]
 
 
-def _pairs(body, macro):
-    return [(int(a), int(b)) for a, b in re.findall(macro + r"\((\d+), (\d+)\)", body)]
+def _table(text, name):
+    """The pairs of `constexpr Shape name[] = {...};`, which the source must define exactly once."""
+    found = re.findall(r"^constexpr Shape " + name + r"\[\] = \{(.*?)\};", text, re.M | re.S)
+    assert len(found) == 1, (name, found)
+    pairs = re.findall(r"\{(\d+), (\d+)\}", found[0])
+    assert "{" + "}, {".join(f"{a}, {b}" for a, b in pairs) + "}" == found[0], (name, found[0])   # nothing but pairs
+    return [(int(a), int(b)) for a, b in pairs]
 
 
 def test_tables_match_the_dispatch_lists_of_the_source():
-    """The (R, U) / (R, J) lists of launch_stream_RU, launch_window_RU, launch_window_group_RU and launch_window, read out
-    of alfd.hip: a shape added there (or dropped) shows here."""
+    """The (R, U) / (R, J) lists that launch_stream_RU, launch_window_RU, launch_window_group_RU and launch_window look
+    their shape up in, read out of alfd.hip: a shape added there (or dropped) shows here.  Each launcher must name its
+    own list, the value-indexed one with its last entry as the default."""
     with open(SOURCE) as f:
         text = f.read()
-    assert _pairs(_function_body(text, "static bool launch_stream_RU("), "ALFD_RU") == STREAM_SHAPES
-    assert _pairs(_function_body(text, "static bool launch_window_RU("), "ALFD_RU") == WINDOW_SHAPES
-    assert _pairs(_function_body(text, "static bool launch_window_group_RU("), "ALFD_RU") == GROUP_SHAPES
-    body = _function_body(text, "static void launch_window(")
-    listed = _pairs(body, "ALFD_VI_E")
-    spelt = {(int(a), int(b)) for a, b in re.findall(r"ALFD_VI\((\d+), (\d+), \d\)", body)}
-    default = sorted(spelt - set(listed))                              # the chain's last resort, spelt out per epilogue
-    assert listed + default == VI_SHAPES
+    assert _table(text, "kStreamShapes") == STREAM_SHAPES
+    assert _table(text, "kWindowShapes") == WINDOW_SHAPES
+    assert _table(text, "kGroupShapes") == GROUP_SHAPES
+    assert _table(text, "kViShapes") == VI_SHAPES                      # default last
+    for head, lookup in (("static bool launch_stream_RU(", "with_shape<kStreamShapes>(ctx->spmv_stream_R, ctx->spmv_stream_U, false,"),
+                         ("static bool launch_window_RU(", "with_shape<kWindowShapes>(ctx->spmv_stream_R, ctx->spmv_stream_U, false,"),
+                         ("static bool launch_window_group_RU(", "with_shape<kGroupShapes>(ctx->spmv_group_R, ctx->spmv_group_U, false,"),
+                         ("static void launch_window(", "with_shape<kViShapes>(ctx->vi_rows_R, ctx->vi_rows_J, true,")):
+        body = _function_body(text, head)
+        assert re.findall(r"with_shape<\w+>\([^\[]*", body) == [lookup + " "], (head, body)
     for shapes in (STREAM_SHAPES, WINDOW_SHAPES, GROUP_SHAPES, VI_SHAPES):
         assert len(set(shapes)) == len(shapes)
-    # the group launcher is reached for exactly these lane counts
-    assert re.findall(r"if \(m\.L == (\d+)\) return launch_window_group_RU<\1>", text) == ["32", "16", "8"]
+    # the group launcher is reached for exactly these lane counts, in this order, and from nowhere else
+    reached = re.findall(r"with_const<([\d, ]+)>\(m\.L, \[&\]\(auto l\) \{ ok = launch_window_group_RU<decltype\(l\)::value>\(", text)
+    assert [[int(v) for v in r.split(", ")] for r in reached] == [[32, 16, 8]]
+    assert text.count("launch_window_group_RU<") == 1

@@ -8,6 +8,8 @@ arithmetic of an element is the same expression under the same compiler flags, o
     the rows party of the tail) against form 1 (y = A x, then the whole tail), every mode the kernel instantiates, on
     the planted operators of launch_shape_cases.py (480 .. 3 365 rows) with the rows of Ct -- the rows the epilogue
     must leave to the tail launch -- placed where a block begins and ends;
+  * the tail launch itself, aug_tail_kernel<L, MODE> at every lane count and mode, against the oracle and the header
+    comment of the kernel (form 1 alone: no other test chooses which of the 30 instantiations runs);
   * an output vector at the address of x is refused before anything is launched;
   * the epilogue together with the second party of a pair launch.
 
@@ -130,11 +132,11 @@ def test_tunable_and_environment_variable(built):
 class Step:
     """Inputs of one step on an n-row operator: computed once per (n, seed), read-only."""
 
-    def __init__(self, n, seed):
+    def __init__(self, n, seed, nt=NT):
         rng = np.random.default_rng(seed)
         self.n = n
         self.x = rng.uniform(-1.0, 1.0, n)
-        self.t = rng.uniform(-1.0, 1.0, NT)
+        self.t = rng.uniform(-1.0, 1.0, nt)
         self.dinv = rng.uniform(0.5, 2.0, n)
         self.rin, self.din, self.zin, self.zout = (rng.uniform(-1.0, 1.0, n) for _ in range(4))
         self.fill = FILL + np.arange(n, dtype=np.float64)
@@ -299,6 +301,77 @@ def test_mode_without_an_epilogue_and_operator_without_one(ctx):
         assert e.value.status in (_abi.E_INVALID, _abi.E_UNSUPPORTED)
         assert ctx.fused_tail_launches() == before
         _run(ctx, 1, mode, st, ct)
+
+
+# ---------------------------------------------------------------- the tail launch itself: aug_tail_kernel<L, MODE>
+LANE_ROWS = {4: (1, 6), 8: (7, 12), 16: (13, 24), 32: (25, 48), 64: (49, 96)}   # lanes: row lengths of Ct, uniform
+NT_LANES = 96
+ALL_MODES = MODES + [_abi.TAIL_RES_INIT_ADD]
+
+
+def _tail_reference(mode, store_res, y, st, c1, c2):
+    """The vectors `mode` stores, from the header comment of aug_tail_kernel (kernels.hpp): res = rin - y;
+    step modes d = fma(c1, din, c2 * (dinv .* res)), z = zin + d; init modes z = c1 * (dinv .* res);
+    the ADD modes zout = fma(1, z, zout)."""
+    from sparse_product_reference import fma
+    res = st.rin - y
+    out = {}
+    if mode in (_abi.TAIL_STEP, _abi.TAIL_LAST, _abi.TAIL_LAST_ADD):
+        prod = c2 * (st.dinv * res)
+        d = np.array([fma(c1, float(a), float(b)) for a, b in zip(st.din, prod)])
+        z = st.zin + d
+    elif mode != _abi.TAIL_RES:
+        z = c1 * (st.dinv * res)
+    if mode in (_abi.TAIL_STEP, _abi.TAIL_RES) or (mode == _abi.TAIL_RES_INIT and store_res):
+        out["res"] = res
+    if mode == _abi.TAIL_STEP:
+        out["d"] = d
+    if mode in (_abi.TAIL_STEP, _abi.TAIL_LAST, _abi.TAIL_RES_INIT):
+        out["z"] = z
+    if mode in (_abi.TAIL_LAST_ADD, _abi.TAIL_RES_INIT_ADD):
+        out["zout"] = np.array([fma(1.0, float(a), float(b)) for a, b in zip(z, st.zout)])
+    return out
+
+
+def test_tail_launch_every_lane_count_and_mode(built, monkeypatch):
+    """aug_tail_kernel<L, MODE> for L = 4, 8, 16, 32, 64 and the six modes, Ct in full and in row-list form, through form 1
+    of alfd_spmv_tail_step on 480 rows against the oracle, bit for bit: y = A x, y = fma(gamma, Ct t, y) at the lane
+    count the row lengths of Ct give (asserted from the oracle's answer), then the element-wise expressions of the mode.
+    A full-form Ct of 64-lane rows counts as plain CSR rows only where the stream kernel is off: ALFD_SPMV_STREAM_R = 0
+    for this context (A then runs on spmv_kernel<64>; the canonical sums do not depend on that)."""
+    from oracle import oracle
+    monkeypatch.setenv("ALFD_SPMV_STREAM_R", "0")
+    n, gamma, c1, c2 = 480, 3.5, 0.625, -1.75
+    A = lc.long_rows(n, "few", 384)
+    st = Step(n, 68, NT_LANES)
+    ax, _ = oracle.spmv(A, st.x, None, mode=0)
+    ctx = solver.Context(0)
+    try:
+        ctx.set_matrix(_abi.A, A)
+        for L, (lo, hi) in LANE_ROWS.items():
+            for form, rows in (("full", np.arange(n)), ("row list", np.arange(0, n, 4))):
+                rng = np.random.default_rng(100 + L + len(rows))
+                cnt = np.zeros(n, np.int64)
+                cnt[rows] = rng.integers(lo, hi + 1, len(rows))
+                rp = np.concatenate([[0], np.cumsum(cnt)]).astype(np.int64)
+                col = np.concatenate([np.sort(rng.choice(NT_LANES, int(k), replace=False)) for k in cnt if k]).astype(np.int32)
+                val = rng.uniform(-1.0, 1.0, col.size)
+                y, used = oracle.spmv(problems.Csr(n, NT_LANES, rp, col, val), st.t, ax, mode=1, alpha=gamma, lanes=0)
+                assert used == L, (L, form, used)
+                assert not np.array_equal(y[rows], ax[rows])
+                for mode in ALL_MODES:
+                    for store_res in ((0, 1) if mode == _abi.TAIL_RES_INIT else (1,)):
+                        tag = (L, form, mode, store_res)
+                        got = _run(ctx, 1, mode, st, (rp, col, val, NT_LANES), store_res=store_res)
+                        want = _tail_reference(mode, store_res, y, st, c1, c2)
+                        assert np.array_equal(got["y"], ax), (tag, "y")     # the tail consumes y + gamma Ct t, stores it nowhere
+                        for k, fill in (("res", st.fill + 0.25), ("d", st.fill + 0.5), ("z", st.fill + 0.75), ("zout", st.zout)):
+                            bad = np.flatnonzero(~(got[k] == want.get(k, fill)))
+                            assert bad.size == 0, (tag, k, "stored" if k in want else "kept", int(bad.size), int(bad[0]))
+                            if k in want:
+                                assert not np.any(got[k] == fill), (tag, k, "not stored")
+    finally:
+        ctx.close()
 
 
 def test_epilogue_beside_the_second_party_of_a_pair_launch(ctx):
