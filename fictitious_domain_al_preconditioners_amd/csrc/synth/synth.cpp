@@ -13,6 +13,10 @@
 //               (node-major interleaved components -- SURVEY.md 8(e)),
 //               homogeneous Dirichlet rows replaced by identity and Dirichlet
 //               columns eliminated (what AffineConstraints does).
+//               local_refine = 1 (synth.h) leaves the tensor grid: the cells near the immersed body are split once,
+//               the unknowns are numbered over the lattice points that carry a node, and every background
+//               operator is summed cell by cell with the hanging-node constraints condensed on the way in
+//               (build_refined below; stokes_immersed_boundary.cc:468-482).
 //   Stokes:     A = (grad u, grad v) + gamma_gd (div u, div v)
 //               (stokes_immersed_boundary.cc:725-732), B = -(div u, q) with q in
 //               Q_{p-1}, Mp = pressure mass.
@@ -246,6 +250,7 @@ struct Params {
   double box_lo[3] = {-0.65, -0.3, -0.4}, box_hi[3] = {0.65, 0.3, 0.4};
   int box_cells[3] = {2, 2, 2};
   int sym_grad = 0;   // 2 eps(u):eps(v) velocity block (alfd_synth_params::sym_grad)
+  int local_refine = 0;   // one layer of local refinement near the immersed body (alfd_synth_params::local_refine)
   // row ranges of this process (multi-GPU row partition); -1 = everything.
   // u/p ranges are in NODES (z-slabs of the lexicographic numbering), l in dofs.
   int64_t u_node0 = -1, u_node1 = -1, p_node0 = -1, p_node1 = -1, l0 = -1, l1 = -1;
@@ -726,6 +731,470 @@ Immersed make_box_2d(const Params &P) {
   return im;
 }
 
+// ---- locally refined background mesh (Params::local_refine == 1, synth.h) ------------------------------------
+// Base mesh N^dim; flagged base cells are replaced by their 2^dim children, once.  A leaf cell is a base cell
+// (fine = 0, coordinates on the N grid) or a child (fine = 1, coordinates on the 2N grid); the leaves are kept in
+// Morton order of the 2N-grid coordinates of their first child, so children are visited in place of their parent.
+struct Leaf {
+  int c[3];
+  int fine;
+};
+struct RefinedMesh {
+  int dim = 2, N = 0;
+  double lo = 0, h = 0;
+  std::vector<char> flagged;   // N^dim, axis 0 fastest
+  std::vector<Leaf> leaves;
+  bool in_range(const int *c) const {
+    for (int a = 0; a < dim; ++a)
+      if (c[a] < 0 || c[a] >= N) return false;
+    return true;
+  }
+  int64_t cell(const int *c) const {
+    int64_t r = 0;
+    for (int a = dim - 1; a >= 0; --a) r = r * N + c[a];
+    return r;
+  }
+};
+
+// Lower cell on a tie: the cell index of coordinate s (in cells) on a grid of n cells.
+inline int cell_of(double s, int n) {
+  int c = (int)std::floor(s);
+  if ((double)c == s) --c;
+  return std::max(0, std::min(n - 1, c));
+}
+
+RefinedMesh make_refined_mesh(const Params &P, const Immersed &im) {
+  RefinedMesh m;
+  m.dim = P.dim;
+  m.N = P.n_cells;
+  m.lo = P.lo;
+  m.h = (P.hi - P.lo) / P.n_cells;
+  int64_t ncell = 1;
+  for (int a = 0; a < m.dim; ++a) ncell *= m.N;
+  std::vector<char> holds(ncell, 0);
+  for (int64_t n = 0; n < im.nnodes(); ++n) {
+    int c[3] = {0, 0, 0};
+    for (int a = 0; a < m.dim; ++a) c[a] = cell_of((im.xyz[3 * n + a] - m.lo) / m.h, m.N);
+    holds[m.cell(c)] = 1;
+  }
+  m.flagged = holds;
+  for (int64_t i = 0; i < ncell; ++i) {
+    if (!holds[i]) continue;
+    int c[3] = {0, 0, 0};
+    int64_t r = i;
+    for (int a = 0; a < m.dim; ++a) c[a] = (int)(r % m.N), r /= m.N;
+    for (int a = 0; a < m.dim; ++a)
+      for (int s = -1; s <= 1; s += 2) {
+        int nb[3] = {c[0], c[1], c[2]};
+        nb[a] += s;
+        if (m.in_range(nb)) m.flagged[m.cell(nb)] = 1;
+      }
+  }
+  std::vector<std::pair<uint64_t, Leaf>> keyed;
+  for (int64_t i = 0; i < ncell; ++i) {
+    int c[3] = {0, 0, 0};
+    int64_t r = i;
+    for (int a = 0; a < m.dim; ++a) c[a] = (int)(r % m.N), r /= m.N;
+    if (!m.flagged[i]) {
+      keyed.push_back({morton3(2 * c[0], 2 * c[1], 2 * c[2]), Leaf{{c[0], c[1], c[2]}, 0}});
+      continue;
+    }
+    for (int d2 = 0; d2 < (m.dim == 3 ? 2 : 1); ++d2)
+      for (int d1 = 0; d1 < 2; ++d1)
+        for (int d0 = 0; d0 < 2; ++d0) {
+          const int f[3] = {2 * c[0] + d0, 2 * c[1] + d1, m.dim == 3 ? 2 * c[2] + d2 : 0};
+          keyed.push_back({morton3(f[0], f[1], f[2]), Leaf{{f[0], f[1], f[2]}, 1}});
+        }
+  }
+  std::sort(keyed.begin(), keyed.end(), [](const auto &x, const auto &y) { return x.first < y.first; });
+  m.leaves.reserve(keyed.size());
+  for (const auto &kl : keyed) m.leaves.push_back(kl.second);
+  return m;
+}
+
+// A degree-k space on the refined mesh.  Lattice spacing h / (2k), L points per axis.
+struct Space {
+  int dim = 2, k = 1, L = 0;
+  std::vector<int32_t> id;        // lattice point -> node (lexicographic among the points that carry one), -1 none
+  std::vector<int64_t> lat;       // node -> lattice point
+  std::vector<char> hanging, boundary;
+  std::vector<int64_t> cptr;      // constraint of node n: entries [cptr[n], cptr[n+1]) (empty unless hanging)
+  std::vector<int32_t> cnode;
+  std::vector<double> cw;
+  int64_t nnodes() const { return (int64_t)lat.size(); }
+  int64_t point(const int *x) const {
+    int64_t r = 0;
+    for (int a = dim - 1; a >= 0; --a) r = r * L + x[a];
+    return r;
+  }
+  void split(int64_t pt, int *x) const {
+    x[0] = x[1] = x[2] = 0;
+    for (int a = 0; a < dim; ++a) x[a] = (int)(pt % L), pt /= L;
+  }
+  int nlocal() const { return dim == 3 ? (k + 1) * (k + 1) * (k + 1) : (k + 1) * (k + 1); }
+  // lattice point of local node l (axis 0 fastest) of a leaf
+  int64_t local_point(const Leaf &lf, int l) const {
+    int x[3] = {0, 0, 0};
+    for (int a = 0; a < dim; ++a) {
+      const int la = l % (k + 1);
+      l /= (k + 1);
+      x[a] = lf.fine ? k * lf.c[a] + la : 2 * k * lf.c[a] + 2 * la;
+    }
+    return point(x);
+  }
+};
+
+// dirichlet: nodes on the boundary of the box are homogeneous Dirichlet nodes (not so for the pressure)
+Space make_space(const RefinedMesh &m, int k, bool dirichlet) {
+  Space S;
+  S.dim = m.dim;
+  S.k = k;
+  S.L = 2 * k * m.N + 1;
+  int64_t npts = 1;
+  for (int a = 0; a < S.dim; ++a) npts *= S.L;
+  S.id.assign(npts, -1);
+  const int nl = S.nlocal();
+  for (const Leaf &lf : m.leaves)
+    for (int l = 0; l < nl; ++l) S.id[S.local_point(lf, l)] = 0;
+  for (int64_t pt = 0; pt < npts; ++pt)
+    if (S.id[pt] == 0) {
+      S.id[pt] = (int32_t)S.lat.size();
+      S.lat.push_back(pt);
+    }
+  const int64_t n = S.nnodes();
+  S.hanging.assign(n, 0);
+  S.boundary.assign(n, 0);
+  // the lowest unrefined base cell whose closure holds the node, for nodes with an odd lattice coordinate
+  std::vector<int64_t> host(n, -1);
+  const int w = 2 * k;
+#pragma omp parallel for schedule(static)
+  for (int64_t i = 0; i < n; ++i) {
+    int x[3];
+    S.split(S.lat[i], x);
+    bool odd = false;
+    for (int a = 0; a < S.dim; ++a) {
+      if (dirichlet && (x[a] == 0 || x[a] == S.L - 1)) S.boundary[i] = 1;
+      if (x[a] & 1) odd = true;
+    }
+    if (!odd) continue;
+    int lo_c[3] = {0, 0, 0}, n_c[3] = {1, 1, 1};
+    for (int a = 0; a < S.dim; ++a) {
+      lo_c[a] = x[a] % w == 0 ? x[a] / w - 1 : x[a] / w;
+      n_c[a] = x[a] % w == 0 ? 2 : 1;
+    }
+    for (int t2 = 0; t2 < n_c[2] && host[i] < 0; ++t2)
+      for (int t1 = 0; t1 < n_c[1] && host[i] < 0; ++t1)
+        for (int t0 = 0; t0 < n_c[0] && host[i] < 0; ++t0) {
+          const int c[3] = {lo_c[0] + t0, lo_c[1] + t1, lo_c[2] + t2};
+          if (m.in_range(c) && !m.flagged[m.cell(c)]) host[i] = m.cell(c);
+        }
+    if (host[i] >= 0) S.hanging[i] = 1;
+  }
+  S.cptr.assign(n + 1, 0);
+  for (int64_t i = 0; i < n; ++i) {
+    S.cptr[i + 1] = S.cptr[i];
+    if (host[i] < 0) continue;
+    int x[3], c[3] = {0, 0, 0};
+    S.split(S.lat[i], x);
+    int64_t r = host[i];
+    for (int a = 0; a < S.dim; ++a) c[a] = (int)(r % m.N), r /= m.N;
+    double v[3][3] = {{1, 0, 0}, {1, 0, 0}, {1, 0, 0}}, d[3];
+    for (int a = 0; a < S.dim; ++a) shape1d(k, (double)(x[a] - w * c[a]) / w, v[a], d);
+    for (int l2 = 0; l2 <= (S.dim == 3 ? k : 0); ++l2)
+      for (int l1 = 0; l1 <= k; ++l1)
+        for (int l0 = 0; l0 <= k; ++l0) {
+          const double wt = v[0][l0] * v[1][l1] * (S.dim == 3 ? v[2][l2] : 1.0);
+          if (wt == 0.0) continue;
+          const int y[3] = {w * c[0] + 2 * l0, w * c[1] + 2 * l1, S.dim == 3 ? w * c[2] + 2 * l2 : 0};
+          S.cnode.push_back(S.id[S.point(y)]);
+          S.cw.push_back(wt);
+          ++S.cptr[i + 1];
+        }
+  }
+  return S;
+}
+
+// The unknowns a node stands for once constraints are applied: itself, or the masters of a hanging node with their
+// weights; nothing for a Dirichlet (boundary) node, whose value is zero, and boundary masters are dropped alike.
+typedef std::vector<std::pair<int32_t, double>> Resolved;
+inline void resolve(const Space &S, int32_t n, Resolved &out) {
+  if (S.boundary[n]) return;
+  if (!S.hanging[n]) {
+    out.emplace_back(n, 1.0);
+    return;
+  }
+  for (int64_t e = S.cptr[n]; e < S.cptr[n + 1]; ++e)
+    if (!S.boundary[S.cnode[e]]) out.emplace_back(S.cnode[e], S.cw[e]);
+}
+// resolve() for every local node of a leaf: entries of local node l are [ptr[l], ptr[l+1]) of ent
+struct LocalDofs {
+  std::vector<int> ptr;
+  Resolved ent;
+};
+inline void local_dofs(const Space &S, const Leaf &lf, LocalDofs &ld) {
+  const int nl = S.nlocal();
+  ld.ptr.assign(nl + 1, 0);
+  ld.ent.clear();
+  for (int l = 0; l < nl; ++l) {
+    resolve(S, S.id[S.local_point(lf, l)], ld.ent);
+    ld.ptr[l + 1] = (int)ld.ent.size();
+  }
+}
+
+struct Refined {
+  RefinedMesh mesh;
+  Space U, Pq;    // velocity / background space, pressure space (Stokes only)
+};
+inline int64_t refined_nodes(const Refined &R) { return R.U.nnodes(); }
+
+// Background shape functions at a physical point: the leaf holding it (lowest Morton index on a tie, which is the
+// lower cell along every tied axis), its tensor shape functions, hanging nodes condensed.
+void refined_eval(const Refined &R, const double *x, std::vector<std::pair<int64_t, double>> &out) {
+  const RefinedMesh &m = R.mesh;
+  const Space &S = R.U;
+  const int dim = m.dim, k = S.k;
+  out.clear();
+  Leaf lf{{0, 0, 0}, 1};
+  int base[3] = {0, 0, 0};
+  for (int a = 0; a < dim; ++a) {
+    lf.c[a] = cell_of((x[a] - m.lo) / (0.5 * m.h), 2 * m.N);
+    base[a] = lf.c[a] / 2;
+  }
+  if (!m.flagged[m.cell(base)]) {
+    lf.fine = 0;
+    for (int a = 0; a < dim; ++a) lf.c[a] = base[a];
+  }
+  const double hc = lf.fine ? 0.5 * m.h : m.h;
+  double v[3][3] = {{1, 0, 0}, {1, 0, 0}, {1, 0, 0}}, d[3];
+  for (int a = 0; a < dim; ++a) shape1d(k, (x[a] - m.lo) / hc - lf.c[a], v[a], d);
+  Resolved res;
+  const int nl = S.nlocal();
+  for (int l = 0; l < nl; ++l) {
+    const int l0 = l % (k + 1), l1 = (l / (k + 1)) % (k + 1), l2 = l / ((k + 1) * (k + 1));
+    const double phi = v[0][l0] * v[1][l1] * (dim == 3 ? v[2][l2] : 1.0);
+    res.clear();
+    resolve(S, S.id[S.local_point(lf, l)], res);
+    for (const auto &e : res) out.emplace_back((int64_t)e.first, e.second * phi);
+  }
+}
+
+// Local matrices of one cell of size h between a degree-kr row space (rc components) and a degree-kc column space
+// (cc components), integrated with Gauss(max degree + 2)^dim.  kind 0: -(div u, q) (rows pressure, columns velocity
+// components), 1: mass (u, v), 2: the load int phi_i (one column).
+struct LocalMatrix {
+  int nr = 0, ncol = 0;
+  std::vector<double> k;
+  double at(int i, int j) const { return k[(size_t)i * ncol + j]; }
+};
+LocalMatrix local_matrix(int dim, int kr, int kc, double h, int kind) {
+  const int nlr = dim == 3 ? (kr + 1) * (kr + 1) * (kr + 1) : (kr + 1) * (kr + 1);
+  const int nlc = dim == 3 ? (kc + 1) * (kc + 1) * (kc + 1) : (kc + 1) * (kc + 1);
+  LocalMatrix C;
+  C.nr = nlr;
+  C.ncol = kind == 0 ? nlc * dim : kind == 1 ? nlc : 1;
+  C.k.assign((size_t)C.nr * C.ncol, 0.0);
+  Gauss q(std::max(kr, kc) + 2);
+  const int nq = (int)q.x.size();
+  const double jinv = 1.0 / h;
+  double vr[3][3], dr[3][3], vc[3][3], dc[3][3];
+  for (int q2 = 0; q2 < (dim == 3 ? nq : 1); ++q2)
+    for (int q1 = 0; q1 < nq; ++q1)
+      for (int q0 = 0; q0 < nq; ++q0) {
+        const int qi[3] = {q0, q1, q2};
+        double jxw = 1.0;
+        for (int a = 0; a < dim; ++a) {
+          shape1d(kr, q.x[qi[a]], vr[a], dr[a]);
+          shape1d(kc, q.x[qi[a]], vc[a], dc[a]);
+          jxw *= q.w[qi[a]] * h;
+        }
+        for (int i = 0; i < nlr; ++i) {
+          const int i0 = i % (kr + 1), i1 = (i / (kr + 1)) % (kr + 1), i2 = i / ((kr + 1) * (kr + 1));
+          const double psi = vr[0][i0] * vr[1][i1] * (dim == 3 ? vr[2][i2] : 1.0);
+          if (kind == 2) {
+            C.k[i] += psi * jxw;
+            continue;
+          }
+          for (int j = 0; j < nlc; ++j) {
+            const int jl[3] = {j % (kc + 1), (j / (kc + 1)) % (kc + 1), j / ((kc + 1) * (kc + 1))};
+            if (kind == 1) {
+              const double phi = vc[0][jl[0]] * vc[1][jl[1]] * (dim == 3 ? vc[2][jl[2]] : 1.0);
+              C.k[(size_t)i * C.ncol + j] += psi * phi * jxw;
+              continue;
+            }
+            for (int b = 0; b < dim; ++b) {
+              double g = jinv;
+              for (int a = 0; a < dim; ++a) g *= a == b ? dc[a][jl[a]] : vc[a][jl[a]];
+              C.k[(size_t)i * C.ncol + j * dim + b] -= psi * g * jxw;
+            }
+          }
+        }
+      }
+  return C;
+}
+
+// Adds the cell contributions of every leaf into a CSR operator between two refined spaces, constraints applied on
+// the way in (what AffineConstraints::distribute_local_to_global does).  Row-parallel: each free row node walks
+// the leaves that reach it, in Morton order, so every global entry is the running sum of its contributions in the
+// order a serial loop over the leaves would add them.  Rows of Dirichlet / hanging nodes: a lone unit diagonal if
+// `square`, else empty.  local(fine, li, a, lj, b): entry of the local matrix of a child (fine) or base cell.
+template <class F>
+void assemble_refined(const RefinedMesh &m, const Space &R, const Space &Cs, int rc, int cc, bool square, Csr &A,
+                      F &&local) {
+  const int64_t nr = R.nnodes(), nleaf = (int64_t)m.leaves.size();
+  // leaves reaching each row node (ascending = Morton order)
+  std::vector<int64_t> iptr(nr + 1, 0), last(nr, -1);
+  std::vector<int32_t> inc;
+  LocalDofs ld;
+  for (int pass = 0; pass < 2; ++pass) {
+    std::fill(last.begin(), last.end(), -1);
+    std::vector<int64_t> cur(iptr.begin(), iptr.end() - 1);
+    for (int64_t e = 0; e < nleaf; ++e) {
+      local_dofs(R, m.leaves[e], ld);
+      for (const auto &d : ld.ent) {
+        if (last[d.first] == e) continue;
+        last[d.first] = e;
+        if (pass == 0)
+          ++iptr[d.first + 1];
+        else
+          inc[cur[d.first]++] = (int32_t)e;
+      }
+    }
+    if (pass == 0) {
+      for (int64_t i = 0; i < nr; ++i) iptr[i + 1] += iptr[i];
+      inc.resize(iptr[nr]);
+    }
+  }
+  // node pattern
+  std::vector<int64_t> nptr(nr + 1, 0);
+  std::vector<std::vector<int32_t>> rows(nr);
+#pragma omp parallel
+  {
+    LocalDofs lc;
+#pragma omp for schedule(dynamic, 256)
+    for (int64_t i = 0; i < nr; ++i) {
+      std::vector<int32_t> &row = rows[i];
+      for (int64_t t = iptr[i]; t < iptr[i + 1]; ++t) {
+        local_dofs(Cs, m.leaves[inc[t]], lc);
+        for (const auto &d : lc.ent) row.push_back(d.first);
+      }
+      std::sort(row.begin(), row.end());
+      row.erase(std::unique(row.begin(), row.end()), row.end());
+      row.shrink_to_fit();
+    }
+  }
+  A.nrows = nr * rc;
+  A.ncols = Cs.nnodes() * cc;
+  A.row_ptr.assign(A.nrows + 1, 0);
+  for (int64_t i = 0; i < nr; ++i) {
+    const bool free_row = !R.boundary[i] && !R.hanging[i];
+    const int64_t len = free_row ? (int64_t)rows[i].size() * cc : (square ? 1 : 0);
+    for (int a = 0; a < rc; ++a) A.row_ptr[i * rc + a + 1] = len;
+  }
+  for (int64_t r = 0; r < A.nrows; ++r) A.row_ptr[r + 1] += A.row_ptr[r];
+  A.col.resize(A.row_ptr[A.nrows]);
+  A.val.assign(A.row_ptr[A.nrows], 0.0);
+#pragma omp parallel
+  {
+    LocalDofs lr, lc;
+#pragma omp for schedule(dynamic, 256)
+    for (int64_t i = 0; i < nr; ++i) {
+      if (R.boundary[i] || R.hanging[i]) {
+        if (square)
+          for (int a = 0; a < rc; ++a) {
+            A.col[A.row_ptr[i * rc + a]] = (int32_t)(i * rc + a);
+            A.val[A.row_ptr[i * rc + a]] = 1.0;
+          }
+        continue;
+      }
+      const std::vector<int32_t> &row = rows[i];
+      for (int a = 0; a < rc; ++a) {
+        int64_t pos = A.row_ptr[i * rc + a];
+        for (int32_t j : row)
+          for (int b = 0; b < cc; ++b) A.col[pos++] = (int32_t)((int64_t)j * cc + b);
+      }
+      const int nlr = R.nlocal(), nlc = Cs.nlocal();
+      for (int64_t t = iptr[i]; t < iptr[i + 1]; ++t) {
+        const Leaf &lf = m.leaves[inc[t]];
+        local_dofs(R, lf, lr);
+        local_dofs(Cs, lf, lc);
+        for (int li = 0; li < nlr; ++li)
+          for (int ei = lr.ptr[li]; ei < lr.ptr[li + 1]; ++ei) {
+            if (lr.ent[ei].first != i) continue;
+            const double wi = lr.ent[ei].second;
+            for (int lj = 0; lj < nlc; ++lj)
+              for (int ej = lc.ptr[lj]; ej < lc.ptr[lj + 1]; ++ej) {
+                const int64_t kcol = std::lower_bound(row.begin(), row.end(), lc.ent[ej].first) - row.begin();
+                const double wj = lc.ent[ej].second;
+                for (int a = 0; a < rc; ++a)
+                  for (int b = 0; b < cc; ++b)
+                    A.val[A.row_ptr[i * rc + a] + kcol * cc + b] += wi * local(lf.fine, li, a, lj, b) * wj;
+              }
+          }
+      }
+    }
+  }
+}
+
+// One layer of local refinement: every operator of the background side from cell contributions.
+void build_refined(const Params &P, Problem &pb, Refined &R, const Immersed &im) {
+  const int dim = P.dim, nc = P.ncomp, k = P.degree;
+  R.mesh = make_refined_mesh(P, im);
+  const RefinedMesh &m = R.mesh;
+  R.U = make_space(m, k, true);
+  Grid gc, gf;   // what cell_matrix reads of a grid: one for the base cells, one for the children
+  gc.dim = gf.dim = dim;
+  gc.p = gf.p = k;
+  gc.lo = gf.lo = P.lo;
+  gc.h = m.h;
+  gf.h = (P.hi - P.lo) / (2 * P.n_cells);
+  const CellMatrix Kc = cell_matrix(P, gc), Kf = cell_matrix(P, gf);
+  assemble_refined(m, R.U, R.U, nc, nc, true, pb.mats["A"],
+                   [&](int fine, int li, int a, int lj, int b) { return (fine ? Kf : Kc).at(li, a, lj, b); });
+  auto emit_space = [&](const Space &S, const char *points, const char *hanging) {
+    std::vector<double> pts(S.nnodes() * dim), hg(S.nnodes());
+    const double hl = (P.hi - P.lo) / (S.L - 1);
+    for (int64_t i = 0; i < S.nnodes(); ++i) {
+      int x[3];
+      S.split(S.lat[i], x);
+      for (int a = 0; a < dim; ++a) pts[i * dim + a] = P.lo + hl * x[a];
+      hg[i] = S.hanging[i] ? 1.0 : 0.0;
+    }
+    pb.vecs[points] = std::move(pts);
+    pb.vecs[hanging] = std::move(hg);
+  };
+  emit_space(R.U, "u_points", "u_hanging");
+  pb.vecs["flagged_cells"] = std::vector<double>(m.flagged.begin(), m.flagged.end());
+  // f_i = body force . int phi_i, hanging nodes condensed, zero on Dirichlet and hanging rows
+  {
+    const LocalMatrix Fc = local_matrix(dim, k, k, gc.h, 2), Ff = local_matrix(dim, k, k, gf.h, 2);
+    std::vector<double> w(R.U.nnodes(), 0.0), f(R.U.nnodes() * nc, 0.0);
+    LocalDofs ld;
+    for (const Leaf &lf : m.leaves) {
+      local_dofs(R.U, lf, ld);
+      for (int l = 0; l < R.U.nlocal(); ++l)
+        for (int e = ld.ptr[l]; e < ld.ptr[l + 1]; ++e)
+          w[ld.ent[e].first] += ld.ent[e].second * (lf.fine ? Ff : Fc).at(l, 0);
+    }
+    for (int64_t i = 0; i < R.U.nnodes(); ++i)
+      for (int a = 0; a < nc; ++a) f[i * nc + a] = P.body_force[a] * w[i];
+    pb.vecs["f"] = std::move(f);
+  }
+  if (!P.stokes) return;
+  R.Pq = make_space(m, k - 1, false);
+  emit_space(R.Pq, "p_points", "p_hanging");
+  const LocalMatrix Bc = local_matrix(dim, k - 1, k, gc.h, 0), Bf = local_matrix(dim, k - 1, k, gf.h, 0);
+  const LocalMatrix Mc = local_matrix(dim, k - 1, k - 1, gc.h, 1), Mf = local_matrix(dim, k - 1, k - 1, gf.h, 1);
+  Csr B;
+  assemble_refined(m, R.Pq, R.U, 1, dim, false, B,
+                   [&](int fine, int li, int, int lj, int b) { return (fine ? Bf : Bc).at(li, lj * dim + b); });
+  assemble_refined(m, R.Pq, R.Pq, 1, 1, true, pb.mats["Mp"],
+                   [&](int fine, int li, int, int lj, int) { return (fine ? Mf : Mc).at(li, lj); });
+  pb.mats["Bt"] = csr_transpose(B);
+  pb.mats["B"] = std::move(B);
+  pb.vecs["rhs_p"] = std::vector<double>(R.Pq.nnodes(), 0.0);
+  pb.vecs["n_p_global"] = {(double)R.Pq.nnodes()};
+}
+
 // One quadrature point on an immersed cell.
 struct QPoint {
   const int *cn;      // cell node ids
@@ -799,8 +1268,10 @@ void immersed_quadrature(const Immersed &im, int nq, F &&f) {
   }
 }
 
-void build_immersed(const Params &P, const Grid &g, Problem &pb) {
+void build_immersed(const Params &P, const Grid &g, Problem &pb, const Refined *ref = nullptr) {
   const int dim = g.dim, nc = P.ncomp;
+  const int64_t n_bg = ref ? refined_nodes(*ref) : g.nnodes;   // nodes of the background space
+  std::vector<std::pair<int64_t, double>> rnodes;
   Immersed im = P.immersed_kind == 1 ? make_box_2d(P) : (dim == 2) ? make_circle(P) : make_cubed_sphere(P);
   const int64_t nl = im.nnodes();
   std::vector<Triplet> tc, tm, tk, tg;
@@ -821,6 +1292,16 @@ void build_immersed(const Params &P, const Grid &g, Problem &pb) {
             qp.gr[a][1] * (qp.minv[1] * qp.gr[b][0] + qp.minv[2] * qp.gr[b][1]);
         tk.push_back({cn[a], cn[b], gg * JxW});
       }
+    }
+    if (ref) {
+      // locally refined background: the leaf cell holding the point, its shape functions, hanging nodes condensed
+      refined_eval(*ref, x, rnodes);
+      for (const auto &nb : rnodes)
+        for (int a = 0; a < im.cell_nodes; ++a) tc.push_back({cn[a], nb.first, nb.second * sh[a] * JxW});
+      if (P.want_surface_mass)
+        for (const auto &na : rnodes)
+          for (const auto &nb : rnodes) tg.push_back({na.first, nb.first, na.second * nb.second * JxW});
+      return;
     }
     // locate background cell, evaluate tensor shape functions
     int cell[3] = {0, 0, 0};
@@ -849,7 +1330,7 @@ void build_immersed(const Params &P, const Grid &g, Problem &pb) {
       for (const auto &na : qnodes)
         for (const auto &nb : qnodes) tg.push_back({na.first, nb.first, na.second * nb.second * JxW});
   });
-  Csr Cs = csr_from_triplets(nl, g.nnodes, tc);  // scalar C
+  Csr Cs = csr_from_triplets(nl, n_bg, tc);  // scalar C
   Csr Ms = csr_from_triplets(nl, nl, tm);
   Csr Ks = csr_from_triplets(nl, nl, tk);
   // expand to nc interleaved components
@@ -874,7 +1355,7 @@ void build_immersed(const Params &P, const Grid &g, Problem &pb) {
       }
     return e;
   };
-  Csr C = expand(Cs, g.nnodes);
+  Csr C = expand(Cs, n_bg);
   Csr Ct = csr_transpose(C);
   Csr Mx = expand(Ms, nl), Kx = expand(Ks, nl);
   std::vector<double> gv(nl * nc);
@@ -882,8 +1363,8 @@ void build_immersed(const Params &P, const Grid &g, Problem &pb) {
     for (int b = 0; b < nc; ++b) gv[k * nc + b] = P.embedded_value[b] * gint[k];
   pb.vecs["n_lambda_global"] = {(double)(nl * nc)};
   if (P.want_surface_mass) {
-    Csr Gs = csr_from_triplets(g.nnodes, g.nnodes, tg);
-    pb.mats["G"] = expand(Gs, g.nnodes);
+    Csr Gs = csr_from_triplets(n_bg, n_bg, tg);
+    pb.mats["G"] = expand(Gs, n_bg);
   }
   if (P.immersed_kind == 1) {
     // elliptic_interface: A2 = (beta_2 - beta_1) (grad, grad) on Omega_2 (elliptic...:681),
@@ -1164,6 +1645,15 @@ bool generate(Problem &pb) {
   }
   if (P.elasticity && (P.ncomp != P.dim || P.dim != 3 || P.stokes || P.degree != 1))
     return pb.err = "elasticity needs dim 3, degree 1, ncomp 3, stokes off", false;
+  if (P.local_refine != 0 && P.local_refine != 1) return pb.err = "local_refine must be 0 or 1", false;
+  if (P.local_refine) {
+    if (P.elasticity) return pb.err = "local_refine does not support elasticity", false;
+    if (P.sym_grad) return pb.err = "local_refine does not support sym_grad", false;
+    if (P.immersed_kind != 0) return pb.err = "local_refine needs a surface-immersed body, not a box", false;
+    if (P.assembly != 1) return pb.err = "local_refine needs the cell-wise assembly, not the Kronecker one", false;
+    if (P.u_node0 >= 0 || P.p_node0 >= 0 || P.l0 >= 0)
+      return pb.err = "local_refine does not support row_ranges (partitioned generation)", false;
+  }
   if (P.sym_grad && (!P.stokes || P.assembly != 0))
     return pb.err = "sym_grad (2 eps:eps) needs stokes and the Kronecker assembly", false;
 
@@ -1181,6 +1671,17 @@ bool generate(Problem &pb) {
   if (part) {
     if (P.u_node1 < P.u_node0 || P.u_node1 > g.nnodes || P.l0 < 0 || P.l1 < P.l0)
       return pb.err = "bad row ranges", false;
+  }
+  if (P.local_refine) {
+    // lattice of spacing h / (2 degree): the node ids are int32
+    int64_t npts = P.ncomp;
+    for (int a = 0; a < g.dim; ++a) npts *= 2 * P.degree * P.n_cells + 1;
+    if (npts > 2147483647LL) return pb.err = "refined lattice has more than 2^31-1 points", false;
+    const Immersed im = g.dim == 2 ? make_circle(P) : make_cubed_sphere(P);
+    Refined R;
+    build_refined(P, pb, R, im);
+    build_immersed(P, g, pb, &R);
+    return true;
   }
   build_A(P, g, pb.mats["A"], part ? P.u_node0 : 0, part ? P.u_node1 : g.nnodes);
   if (P.stokes) {
@@ -1266,6 +1767,7 @@ void *alfd_synth_generate(const alfd_synth_params *sp, char *err, int errlen) {
   P.assembly = sp->assembly;
   P.elasticity = sp->elasticity;
   P.sym_grad = sp->sym_grad;
+  P.local_refine = sp->local_refine;
   P.lame_lambda = sp->lame_lambda;
   P.lame_mu = sp->lame_mu;
   P.lame2_lambda = sp->lame2_lambda;
@@ -1343,6 +1845,16 @@ int alfd_synth_permute_nodes(void *h, const int64_t *new_to_old, int64_t n_nodes
     std::vector<double> f(n);
     for (int64_t r = 0; r < n; ++r) f[r] = pb->vecs["f"][old_of(r)];
     pb->vecs["f"] = f;
+  }
+  // the per-node vectors of a locally refined problem follow their nodes
+  for (const char *name : {"u_points", "u_hanging"}) {
+    auto it = pb->vecs.find(name);
+    if (it == pb->vecs.end()) continue;
+    const int64_t w = (int64_t)it->second.size() / n_nodes;
+    std::vector<double> v(it->second.size());
+    for (int64_t k = 0; k < n_nodes; ++k)
+      for (int64_t c = 0; c < w; ++c) v[k * w + c] = it->second[new_to_old[k] * w + c];
+    it->second = v;
   }
   return 0;
 }

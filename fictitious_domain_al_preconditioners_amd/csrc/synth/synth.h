@@ -38,6 +38,18 @@ typedef struct alfd_synth_params {
    * grad u : grad v; Kronecker assembly only.  2 eps:eps = grad:grad + T, block (b,a) of T = block (a,b) of the
    * gamma_gd = 1 grad-div matrix.  The grad-div term, if on, is added after T. */
   int32_t sym_grad;
+  /* 1: ONE layer of local refinement of the background mesh near the immersed body (what `Local refinements steps
+   * near embedded domain = 1` of parameters_stokes_3d.prm asks for).  Every base cell whose closed box holds a node
+   * of the immersed mesh (a node on a shared face counts for the lower cell) and each of its face neighbours is
+   * replaced by its 2^dim children.  Unknowns sit on the lattice of spacing h / (2 degree): base cells use every
+   * second lattice point, children every one; numbering is lexicographic over the lattice points that carry a node.
+   * A node of a child that lies in the closure of an unrefined cell without being one of its nodes is HANGING: its
+   * constraint (the unrefined cell's shape functions at that point) is applied while the cell contributions are
+   * added, its own row stays as a lone diagonal with a zero right-hand side, like a Dirichlet row.  Needs
+   * assembly = 1, a surface-immersed body (immersed_kind 0), no elasticity, no sym_grad, no row ranges.
+   * Extra vectors: u_points / p_points (dim doubles per node), u_hanging / p_hanging (0 / 1 per node),
+   * flagged_cells (0 / 1 per base cell, x fastest). */
+  int32_t local_refine;
 } alfd_synth_params;
 
 /* NULL on failure (message in err). */

@@ -40,6 +40,7 @@ class _Params(C.Structure):
         ("lame2_lambda", C.c_double), ("lame2_mu", C.c_double),
         ("box_lo", C.c_double * 3), ("box_hi", C.c_double * 3),
         ("box_cells", C.c_int32 * 3), ("sym_grad", C.c_int32),
+        ("local_refine", C.c_int32),
     ]
 
 
@@ -203,7 +204,7 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
              coupling_nq=3, body_force=(0.0, 0.0, 0.0), embedded_value=(1.0, 0.0, 0.0),
              row_ranges=None, immersed_box=None, beta2=0.0, surface_mass=False,
              elasticity=None, immersed_box3d=None, immersed_segments=0, assembly="kronecker",
-             sym_grad=False) -> SyntheticProblem:
+             sym_grad=False, local_refine=0) -> SyntheticProblem:
     """immersed_box = (lo, hi, cells): the immersed domain is the 2-D box [lo,hi]^2
     with cells^2 Q1 cells (volume coupling, elliptic_interface); beta2 scales "A2".
     elasticity = (lambda, mu, lambda_jump, mu_jump): vector-Q1 linear elasticity on the background
@@ -213,7 +214,13 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
     used with `Grad-div stabilization = false`) instead of grad u : grad v; Kronecker assembly only.
     row_ranges = (u_node0, u_node1, p_node0, p_node1, l0, l1): generate only this
     rank's rows (node ranges for the background spaces, dof range for the
-    multiplier); column indices stay global.  None = the whole problem."""
+    multiplier); column indices stay global.  None = the whole problem.
+    local_refine = 1: one layer of local refinement of the background mesh near the immersed body
+    (`Local refinements steps near embedded domain = 1`, stokes_immersed_boundary.cc:468-482): every base cell
+    holding a node of the immersed mesh and its face neighbours are split once, the operators carry the
+    condensed hanging-node constraints (hanging rows stay as lone diagonals).  Needs assembly="cellwise" and a
+    circle / sphere body.  Extra vecs: "u_points", "p_points" (one support point per node), "u_hanging",
+    "p_hanging" (0 / 1 per node), "flagged_cells" (0 / 1 per base cell)."""
     lib = _load()
     p = _Params()
     p.dim, p.degree, p.ncomp, p.n_cells = dim, degree, ncomp, n_cells
@@ -230,6 +237,7 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
     p.want_surface_mass = int(surface_mass)
     p.assembly = {"kronecker": 0, "cellwise": 1}[assembly]
     p.sym_grad = int(sym_grad)
+    p.local_refine = int(local_refine)
     if immersed_box is not None:
         p.immersed_kind, p.imm_lo, p.imm_hi, p.imm_cells = 1, float(immersed_box[0]), float(immersed_box[1]), int(immersed_box[2])
         p.beta2 = beta2
@@ -252,6 +260,8 @@ def generate(dim=2, degree=1, ncomp=1, n_cells=16, lo=0.0, hi=1.0, stokes=False,
                   grad_div=grad_div, gamma_grad_div=gamma_grad_div, beta=beta, center=tuple(center),
                   radius=radius, immersed_refine=immersed_refine, coupling_nq=coupling_nq, assembly=assembly,
                   sym_grad=bool(sym_grad))
+    if local_refine:                    # the tensor-grid helpers below refuse a problem that carries this key
+        params["local_refine"] = int(local_refine)
     if immersed_box is not None:        # cells per direction of a box-meshed immersed domain (immersed_tensor_prolongators)
         params["immersed_cells"] = (int(immersed_box[2]),) * 2
     if immersed_box3d is not None:
@@ -276,7 +286,8 @@ def _fetch_views(pb: "SyntheticProblem"):
         pb.mats[name] = Csr(nr.value, nc.value, _view(rp, nr.value + 1, C.c_int64, np.int64, owner),
                             _view(col, nnz.value, C.c_int32, np.int32, owner),
                             _view(val, nnz.value, C.c_double, np.float64, owner))
-    for name in ("f", "g", "rhs_p", "f2", "immersed_xyz"):
+    for name in ("f", "g", "rhs_p", "f2", "immersed_xyz", "u_points", "p_points", "u_hanging", "p_hanging",
+                 "flagged_cells"):
         n, data = C.c_int64(), C.POINTER(C.c_double)()
         if lib.alfd_synth_vector(owner.ptr, name.encode(), C.byref(n), C.byref(data)) != 0:
             continue
@@ -300,8 +311,14 @@ def permute_background_nodes(pb: "SyntheticProblem", new_to_old) -> "SyntheticPr
 
 # ---------------------------------------------------------------------------
 # The BASELINE.json configs as concrete synthetic instances.
+def _refined(local_refine):
+    """generate() arguments of a wrapper without an `assembly` argument: a locally refined mesh is assembled
+    cell by cell, the uniform one keeps the Kronecker rows."""
+    return dict(local_refine=local_refine, assembly="cellwise") if local_refine else {}
+
+
 def laplace2d_circle(n_cells=64, immersed_refine=5, coupling_nq=3, surface_mass=False,
-                     immersed_segments=0) -> SyntheticProblem:
+                     immersed_segments=0, local_refine=0) -> SyntheticProblem:
     """cfg 1: immersed_laplace 2-D, parameters/circle/Circle_parameters_f0_g1.prm
     (f = 0, g = 1, R = 0.2, centre (0.4, 0.4)), Q1 background on [0,1]^2.
     immersed_segments = N sizes the immersed block directly: the circle is meshed with exactly N P1 segments (a closed
@@ -312,7 +329,7 @@ def laplace2d_circle(n_cells=64, immersed_refine=5, coupling_nq=3, surface_mass=
     return generate(dim=2, degree=1, ncomp=1, n_cells=n_cells, center=(0.4, 0.4, 0.0), radius=0.2,
                     immersed_refine=immersed_refine, coupling_nq=coupling_nq,
                     body_force=(0.0,), embedded_value=(1.0,), surface_mass=surface_mass,
-                    immersed_segments=immersed_segments)
+                    immersed_segments=immersed_segments, **_refined(local_refine))
 
 
 def operator_form(pb: SyntheticProblem, gamma: float = 10.0):
@@ -327,15 +344,15 @@ def operator_form(pb: SyntheticProblem, gamma: float = 10.0):
     return Csr.from_scipy(a), gamma_h, 1.0 / pb.mats["M"].diagonal()
 
 
-def laplace3d_sphere(n_cells=128, immersed_refine=5, coupling_nq=3) -> SyntheticProblem:
+def laplace3d_sphere(n_cells=128, immersed_refine=5, coupling_nq=3, local_refine=0) -> SyntheticProblem:
     """cfg 2: immersed_laplace 3-D, Q1 on n^3 cells, cubed-sphere surface R = 0.2."""
     return generate(dim=3, degree=1, ncomp=1, n_cells=n_cells, center=(0.5, 0.5, 0.5), radius=0.2,
                     immersed_refine=immersed_refine, coupling_nq=coupling_nq,
-                    body_force=(0.0,), embedded_value=(1.0,))
+                    body_force=(0.0,), embedded_value=(1.0,), **_refined(local_refine))
 
 
 def stokes3d_sphere(n_cells=64, immersed_refine=4, gamma_grad_div=10.0, coupling_nq=4,
-                    row_ranges=None, assembly="kronecker") -> SyntheticProblem:
+                    row_ranges=None, assembly="kronecker", local_refine=0) -> SyntheticProblem:
     """cfg 4 (north star): stokes_immersed_boundary + parameters_stokes_3d.prm.
     Taylor-Hood Q2/Q1 on n^3 cells, grad-div on (prm:21), sphere R = 0.1 centre
     (.5,.5,.5) (stokes_immersed_boundary.cc:427), body force (1,0,0) (prm:52),
@@ -344,16 +361,17 @@ def stokes3d_sphere(n_cells=64, immersed_refine=4, gamma_grad_div=10.0, coupling
                     gamma_grad_div=gamma_grad_div, center=(0.5, 0.5, 0.5), radius=0.1,
                     immersed_refine=immersed_refine, coupling_nq=coupling_nq,
                     body_force=(1.0, 0.0, 0.0), embedded_value=(-1.0, 1.0, 0.0), row_ranges=row_ranges,
-                    assembly=assembly)
+                    assembly=assembly, local_refine=local_refine)
 
 
-def stokes2d_circle(n_cells=32, immersed_refine=4, gamma_grad_div=10.0, coupling_nq=3) -> SyntheticProblem:
+def stokes2d_circle(n_cells=32, immersed_refine=4, gamma_grad_div=10.0, coupling_nq=3,
+                    local_refine=0) -> SyntheticProblem:
     """2-D Taylor-Hood + immersed circle (what the reference binary is compiled
     for: stokes_immersed_boundary.cc:1218-1219, parameters_stokes.prm)."""
     return generate(dim=2, degree=2, ncomp=2, n_cells=n_cells, stokes=True, grad_div=True,
                     gamma_grad_div=gamma_grad_div, center=(0.5, 0.5, 0.0), radius=0.2,
                     immersed_refine=immersed_refine, coupling_nq=coupling_nq,
-                    body_force=(1.0, 0.0), embedded_value=(-1.0, 1.0))
+                    body_force=(1.0, 0.0), embedded_value=(-1.0, 1.0), **_refined(local_refine))
 
 
 def elliptic_interface2d(n_bg=64, n_fg=16, beta1=1.0, beta2=10.0, coupling_nq=3, row_ranges=None) -> SyntheticProblem:
@@ -410,11 +428,25 @@ def cuthill_mckee_nodes(pb: "SyntheticProblem"):
     return np.ascontiguousarray(reverse_cuthill_mckee(g, symmetric_mode=True)[::-1]).astype(np.int64)
 
 
+def _tensor_grid_only(params: dict, what: str):
+    if params.get("local_refine"):
+        raise ValueError(f"{what} (the background mesh is locally refined, not a tensor grid)")
+
+
 def row_support_points(params: dict, node_range=None, node_permutation=None):
     """One support point per row of the block-(0,0) operator of a tensor-grid problem (node-major
     numbering: the ncomp rows of a node share its point) -- what DoFTools::map_dofs_to_support_points
     gives a deal.II caller; input of solver.row_blocks_from_points.  node_permutation: the new_to_old node
-    renumbering the problem carries (SyntheticProblem.node_permutation)."""
+    renumbering the problem carries (SyntheticProblem.node_permutation).
+    A locally refined problem (local_refine=1) is no tensor grid: pass the SyntheticProblem itself and get the
+    generator's points (vecs["u_points"], which follow every node renumbering of the problem)."""
+    if isinstance(params, SyntheticProblem):
+        pb = params
+        if pb.params.get("local_refine"):
+            return np.repeat(pb.vecs["u_points"].reshape(-1, pb.params["dim"]), pb.params["ncomp"], axis=0)
+        return row_support_points(pb.params, node_range, getattr(pb, "node_permutation", None)
+                                  if node_permutation is None else node_permutation)
+    _tensor_grid_only(params, "row_support_points(params): pass the problem itself")
     dim, ncomp = params["dim"], params["ncomp"]
     n1 = params["degree"] * params["n_cells"] + 1
     n0, n_end = (0, n1 ** dim) if node_range is None else (int(node_range[0]), int(node_range[1]))
@@ -432,6 +464,7 @@ def brick_row_blocks(params: dict, brick=(16, 4, 1), max_rows: int = 250, node_r
     (node-major, the numbering of the block-(0,0) operator).  node_range = (first, last+1) restricts the
     blocks to one rank's slab of nodes (rows are then numbered from that slab's first row).
     Returns (block_ptr, rows)."""
+    _tensor_grid_only(params, "brick_row_blocks: use solver.brick_blocks_from_points")
     dim, ncomp = params["dim"], params["ncomp"]
     n1 = params["degree"] * params["n_cells"] + 1
     n0, n_end = (0, n1 ** dim) if node_range is None else (int(node_range[0]), int(node_range[1]))
@@ -461,6 +494,7 @@ def geometric_aggregates(pb: SyntheticProblem, a: int = 2, min_coarse: int = 600
     if pb.row_ranges is not None:
         raise ValueError("geometric_aggregates needs the unpartitioned problem")
     P = pb.params
+    _tensor_grid_only(P, "geometric_aggregates")
     dim, ncomp = P["dim"], P["ncomp"]
     n1 = P["degree"] * P["n_cells"] + 1
     idx = np.arange(n1 ** dim, dtype=np.int64)
@@ -524,6 +558,7 @@ def tensor_prolongators(params: dict, min_coarse: int = 400, max_levels: int = 7
     FETools::get_interpolation_matrix.  node_permutation: new_to_old node renumbering of the fine space
     (SyntheticProblem.node_permutation).  Returns [(Csr P, n_coarse), ...]."""
     import scipy.sparse as sp
+    _tensor_grid_only(params, "tensor_prolongators: use refined_prolongators")
     dim, ncomp, degree = params["dim"], params["ncomp"], params["degree"]
     nf = degree * params["n_cells"]               # cells of the fine nodal grid
     nc = params["n_cells"] if degree > 1 else (params["n_cells"] + 1) // 2
@@ -552,6 +587,60 @@ def tensor_prolongators(params: dict, min_coarse: int = 400, max_levels: int = 7
         if n_coarse <= min_coarse:
             break
         nf, nc, fine_is_full = nc, (nc + 1) // 2, False
+    return levels
+
+
+def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels: int = 7):
+    """Geometric multigrid transfers for a locally refined problem (local_refine=1), as CSR prolongators for
+    Context.set_prolongator.  The refined space has no tensor-product transfers, so level 0 maps it onto the Q1
+    space of the uniform BASE grid (n_cells per direction), component by component: row i holds the multilinear
+    weights of the base grid at row i's support point (the base Q1 functions are members of the refined space,
+    so this is their nodal interpolation).  Dirichlet and hanging rows are empty, i.e. not represented; the
+    coarse unknowns are the interior nodes of the base grid, lexicographic and node-major.  The levels below are
+    those of tensor_prolongators for the base grid.  Follows the problem's node renumbering (u_points does).
+    Returns [(Csr P, n_coarse), ...]."""
+    import scipy.sparse as sp
+    P = pb.params
+    if not P.get("local_refine"):
+        raise ValueError("refined_prolongators needs a locally refined problem (local_refine=1)")
+    dim, ncomp, n = P["dim"], P["ncomp"], P["n_cells"]
+    pts = pb.vecs["u_points"].reshape(-1, dim)
+    s = (pts - P["lo"]) * (n / (P["hi"] - P["lo"]))               # position in base cells
+    cell = np.clip(np.floor(s + 1e-9).astype(np.int64), 0, n - 1)
+    k2 = 2 * P["degree"]
+    fr = np.round((s - cell) * k2) / k2                           # lattice points: exact multiples of 1 / (2 degree)
+    boundary = np.any((np.abs(s) < 1e-9) | (np.abs(s - n) < 1e-9), axis=1)
+    live = ~boundary & (pb.vecs["u_hanging"] == 0)
+    rows, cols, vals = [], [], []
+    node = np.arange(pts.shape[0])
+    for corner in range(2 ** dim):
+        w = np.ones(pts.shape[0])
+        j = np.zeros(pts.shape[0], np.int64)
+        inside = np.ones(pts.shape[0], bool)
+        for d in reversed(range(dim)):
+            up = (corner >> d) & 1
+            w = w * (fr[:, d] if up else 1.0 - fr[:, d])
+            c = cell[:, d] + up                                   # base-grid node along d; interior ones are unknowns
+            inside &= (c > 0) & (c < n)
+            j = j * (n - 1) + (c - 1)
+        keep = live & inside & (w != 0.0)
+        rows.append(node[keep]); cols.append(j[keep]); vals.append(w[keep])
+    p0 = sp.csr_matrix((np.concatenate(vals), (np.concatenate(rows), np.concatenate(cols))),
+                       shape=(pts.shape[0], (n - 1) ** dim))
+    pv = sp.kron(p0, sp.identity(ncomp)).tocsr() if ncomp > 1 else p0.tocsr()
+    pv.sort_indices()
+    levels = [(Csr.from_scipy(pv), int(pv.shape[1]))]
+    if pv.shape[1] > min_coarse and max_levels > 1:
+        base = dict(dim=dim, ncomp=ncomp, degree=1, n_cells=n)
+        # tensor_prolongators(degree 1) numbers its level-0 rows over ALL base nodes; ours are the interior ones
+        idx = np.arange((n + 1) ** dim)
+        interior = np.ones(idx.size, bool)
+        for d in range(dim):
+            c = (idx // (n + 1) ** d) % (n + 1)
+            interior &= (c > 0) & (c < n)
+        sel = (np.flatnonzero(interior)[:, None] * ncomp + np.arange(ncomp)[None, :]).ravel()
+        for k, (pc, n_coarse) in enumerate(tensor_prolongators(base, min_coarse=min_coarse, max_levels=max_levels - 1)):
+            levels.append((Csr.from_scipy(pc.to_scipy()[sel, :]), n_coarse) if k == 0 else (pc, n_coarse))
     return levels
 
 
