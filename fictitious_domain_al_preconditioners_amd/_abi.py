@@ -202,6 +202,14 @@ class StreamPlanInfo(C.Structure):
     ]
 
 
+class SideRowsInfo(C.Structure):
+    """alfd_side_rows_info: the side list of a long-row batch-major matrix (tunable "batch_major_side_rows")."""
+    _fields_ = [
+        ("rows", C.c_int64), ("nnz", C.c_int64), ("longest", C.c_int64), ("interior_rows", C.c_int64),
+        ("grid", C.c_int64),
+    ]
+
+
 def default_config(variant=AL_STOKES) -> Config:
     """Same defaults as alfd_default_config(): the reference's solver knobs
     (parameters_stokes_3d.prm:17-24,150-157; immersed_laplace.cc:907; elliptic...:863)."""

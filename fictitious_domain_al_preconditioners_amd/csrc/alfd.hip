@@ -124,6 +124,12 @@ struct DevCsr {
     int32_t seg_stride = 0;
     int64_t nb_interior = 0;     // partitioned contexts: the first nb_interior blocks read no halo column
     double *dict = nullptr;
+    // side rows ("batch_major_side_rows", spmv_side_rows_kernel): the rows beyond kVsMaxLen entries, which no block
+    // lists.  Every launch of the blocks is followed by launch_side on the same stream (VsPlan has the order of the list)
+    int64_t side_n = 0, side_nnz = 0, side_longest = 0, side_interior = 0;
+    int32_t *side_rows = nullptr, *side_col = nullptr;
+    int64_t *side_rp = nullptr;
+    double *side_val = nullptr;
   } vs;
   // bytes the kernel in use moves per launch (format bytes, x read once)
   double streamed_bytes(bool use_vi, bool use_vs = false) const {
@@ -131,7 +137,7 @@ struct DevCsr {
     if (vs.on && use_vs && use_vi)
       return (double)vs.stream_bytes + 8.0 * vs.tab_u64 * (double)vs.nbatch + 28.0 * (double)vs.nb +
              8.0 * (double)vs.nseg + 8.0 * (double)vs.dict_total + 8.0 * (double)nrows +
-             8.0 * (double)(sparse ? n_list : ncols);
+             8.0 * (double)(sparse ? n_list : ncols) + 12.0 * (double)(vs.side_nnz + vs.side_n);
     if (!win) return (double)nnz * 12.0 + vec;
     const double meta = (double)win_nblocks * 8.0 + (double)win_nseg * 8.0;
     if (!(vi && use_vi)) return (double)nnz * 10.0 + vec + meta;
@@ -406,6 +412,7 @@ struct alfd_ctx {
   int win_vi = 1;                           // dictionary-coded values in window blocks (ALFD_SPMV_VALUE_INDEX)
   int win_short_scale = 2;                  // short-row block = min(512, win_RB * scale * 64 / L) rows; 0 = off
   int vs_enable = 1, vs_NW = 4, vs_RB = 96, vs_xcd = 0, vs_share = 1, vs_wide = 1;
+  int vs_side = 0;                          // "batch_major_side_rows": rows beyond kVsMaxLen entries go to a side list (build_vs)
   int vs_small = 1;                         // "batch_major_small": level / patch operators that leave the chip under-filled get smaller row blocks (vs_small_shape)
   int vs_cus = 0;                           // compute units of the device (hipDeviceProp_t::multiProcessorCount)
   int vs_force_RB = 0, vs_force_NW = 0;     // alfd_bench_operator: the shape of the next build_vs, whatever the rule says
@@ -889,16 +896,33 @@ static void launch_vs_kernel(alfd_ctx *ctx, const DevCsr &m, const double *x, do
                      ctx->vs_xcd, base, pc, ta);
 }
 
+// ---- the side rows of a long-row batch-major operator (spmv_side_rows_kernel): behind every launch of its blocks, on
+// the same stream with the same epilogue arguments, inside the Timer of that launch.  No record: alfd_get_last_spmv_launch
+// keeps describing the batch-major launch.  part: kSideAll, or one of the two groups of a partitioned operator (the
+// rows that read no halo column, which go with the interior blocks, and the others).
+enum { kSideAll = 0, kSideInterior = 1, kSideBoundary = 2 };
+static inline int64_t side_grid(int64_t n) { return std::min<int64_t>((n + 3) / 4, 256 * 8); }   // one wave per row, grid-stride beyond
+static void launch_side(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha, const double *d,
+                        double *y2, int part = kSideAll) {
+  const DevCsr::Vs &v = m.vs;
+  const int64_t first = part == kSideBoundary ? v.side_interior : 0;
+  const int64_t n = (part == kSideInterior ? v.side_interior : v.side_n) - first;
+  if (n <= 0) return;
+  with_epi(epi, [&](auto e) {
+    hipLaunchKernelGGL((spmv_side_rows_kernel<decltype(e)::value>), dim3((unsigned)side_grid(n)), dim3(kBlock), 0, ctx->stream, n,
+                       v.side_rows + first, v.side_rp + first, v.side_col, v.side_val, x, m.halo, m.n_local_cols, y, alpha, d, y2);
+  });
+}
+
 static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha,
-                      const double *d, double *y2, int64_t first_block = 0, int64_t n_blocks = -1) {
+                      const double *d, double *y2, int64_t first_block = 0, int64_t n_blocks = -1, int side_part = kSideAll) {
   const DevCsr::Vs &v = m.vs;
   if (!vs_lds_base_ok(ctx)) return false;
   if (with_const<32, 16, 8>(v.L, [&](auto l) { launch_vss<decltype(l)::value>(ctx, m, x, y, epi, alpha, d, y2); })) return true;
   if (n_blocks < 0) n_blocks = v.nb - first_block;
-  if (n_blocks <= 0) return true;
-  const unsigned grid = (unsigned)n_blocks;
+  const unsigned grid = (unsigned)std::max<int64_t>(n_blocks, 0);
   const int32_t base = (int32_t)first_block;
-  with_epi(epi, [&](auto e) {
+  if (grid > 0) with_epi(epi, [&](auto e) {
     constexpr int EPI = decltype(e)::value;
     if (v.wide)   // 10-bit codes: one instantiation per epilogue (4 waves, tag 0)
       return launch_vs_kernel<EPI, 0, 4, 1>(ctx, m, x, y, alpha, d, y2, grid, base);
@@ -910,6 +934,7 @@ static bool launch_vs(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y
       });
     });
   });
+  launch_side(ctx, m, x, y, epi, alpha, d, y2, side_part);
   return true;
 }
 
@@ -938,12 +963,12 @@ static int spmv_m(alfd_ctx *ctx, DevCsr &m, int cls, const double *x, double *y,
   if (overlap) {
     Timer tm(ctx, cls, m.algorithmic_bytes(), m.streamed_bytes(true, true));
     HIPC(hipEventRecord(ctx->ev_x, ctx->stream));          // x is complete here
-    if (!launch_vs(ctx, m, x, y, epi, alpha, d, y2, 0, m.vs.nb_interior)) return ctx->err = "batch-major launch failed", ALFD_E_HIP;
+    if (!launch_vs(ctx, m, x, y, epi, alpha, d, y2, 0, m.vs.nb_interior, kSideInterior)) return ctx->err = "batch-major launch failed", ALFD_E_HIP;
     HIPC(hipStreamWaitEvent(ctx->xstream, ctx->ev_x, 0));
     RC(halo_exchange(ctx, m, x, ctx->xstream));
     HIPC(hipEventRecord(ctx->ev_halo, ctx->xstream));
     HIPC(hipStreamWaitEvent(ctx->stream, ctx->ev_halo, 0));
-    launch_vs(ctx, m, x, y, epi, alpha, d, y2, m.vs.nb_interior, m.vs.nb - m.vs.nb_interior);
+    launch_vs(ctx, m, x, y, epi, alpha, d, y2, m.vs.nb_interior, m.vs.nb - m.vs.nb_interior, kSideBoundary);   // with the side rows that read the halo
     HIPC(hipGetLastError());
     return ALFD_OK;
   }
@@ -1161,6 +1186,7 @@ static int launch_pair(alfd_ctx *ctx, int form, const DevCsr &A, int clsA, const
                                                                                  pc.nA + pc.nC, 0, pc);
       });
     });
+    launch_side(ctx, A, x, y, 0, 0.0, nullptr, nullptr);
   } else {   // the stream kernel at (2, 8), kBlock threads
     const PairC pc = pair_c(C, w, t, (uint32_t)stream_grid(ctx, A.nrows, 2), kBlock);
     note_spmv(ctx, ALFD_SPMV_STREAM, 64, 2, 8, false, 0, 0, (int64_t)pc.nA + pc.nC, 0);
@@ -2557,7 +2583,75 @@ struct VsPlan {
   std::vector<uint64_t> tab;
   int wide = 0;       // 1: 10-bit codes / 11-bit window columns (VsFmt<1>)
   int64_t nb_in = 0;  // blocks before the dictionary limit halved any
+  // side rows ("batch_major_side_rows"): the rows beyond kVsMaxLen entries, kept out of the blocks.  Global row numbers,
+  // longest row first, ties by row number (partitioned operators: the side_interior rows that read no halo column
+  // first, each group in that order), and their compact CSR, the entries in the row's own order
+  std::vector<int32_t> side_rows, side_col;
+  std::vector<int64_t> side_rp;
+  std::vector<double> side_val;
+  int64_t side_interior = 0;
 };
+
+// The share of a matrix's entries that side rows may hold.  Not a tuned number: a condition that keeps a matrix MADE of
+// long rows on the window forms, where the one-wave-per-row side kernel would be the whole product.
+constexpr double kVsSideMaxShare = 1.0 / 8;   // a power of two: the comparison below is exact
+
+// The rows longer than kVsMaxLen entries, or false: there are none, they hold more than kVsSideMaxShare of the entries,
+// or one has more than kSideMaxLen.  Fills the side list of pl and the row lists (optr / orows) without those rows:
+// runs of RB rows of the numbering or the caller's blocks, a block left empty dropped.
+static bool vs_take_side_rows(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int RB, int64_t nb_in,
+                              const int64_t *bptr, const int32_t *brows, int64_t n_local_cols, VsPlan &pl,
+                              std::vector<int64_t> &optr, std::vector<int32_t> &orows) {
+  std::vector<int32_t> side;
+  int64_t side_nnz = 0;
+  for (int64_t r = 0; r < nrows; ++r) {
+    const int64_t n = rp[r + 1] - rp[r];
+    if (n <= kVsMaxLen) continue;
+    if (n > kSideMaxLen) return false;
+    side.push_back((int32_t)r);
+    side_nnz += n;
+  }
+  if (side.empty() || (double)side_nnz > kVsSideMaxShare * (double)rp[nrows]) return false;
+  auto halo = [&](int32_t r) {
+    if (n_local_cols < 0) return false;
+    for (int64_t k = rp[r]; k < rp[r + 1]; ++k)
+      if (col[k] >= n_local_cols) return true;
+    return false;
+  };
+  std::vector<uint8_t> bnd(side.size(), 0);
+  std::vector<size_t> order(side.size());
+  for (size_t i = 0; i < side.size(); ++i) bnd[i] = halo(side[i]), order[i] = i;
+  std::sort(order.begin(), order.end(), [&](size_t a, size_t b) {
+    if (bnd[a] != bnd[b]) return bnd[a] < bnd[b];
+    const int64_t la = rp[side[a] + 1] - rp[side[a]], lb = rp[side[b] + 1] - rp[side[b]];
+    return la != lb ? la > lb : side[a] < side[b];
+  });
+  pl.side_rp.assign(1, 0);
+  pl.side_col.reserve((size_t)side_nnz);
+  pl.side_val.reserve((size_t)side_nnz);
+  for (size_t i : order) {
+    const int32_t r = side[i];
+    pl.side_rows.push_back(r);
+    pl.side_col.insert(pl.side_col.end(), col + rp[r], col + rp[r + 1]);
+    pl.side_val.insert(pl.side_val.end(), val + rp[r], val + rp[r + 1]);
+    pl.side_rp.push_back((int64_t)pl.side_col.size());
+    pl.side_interior += (n_local_cols >= 0 && !bnd[i]) ? 1 : 0;   // 0 where there is no halo
+  }
+  const bool nat = bptr == nullptr;
+  const int64_t nb = nat ? (nrows + RB - 1) / RB : nb_in;
+  optr.assign(1, 0);
+  orows.clear();
+  orows.reserve((size_t)nrows - side.size());
+  for (int64_t b = 0; b < nb; ++b) {
+    const int64_t lo = nat ? b * RB : bptr[b], hi = nat ? std::min<int64_t>((b + 1) * RB, nrows) : bptr[b + 1];
+    for (int64_t i = lo; i < hi; ++i) {
+      const int32_t r = nat ? (int32_t)i : brows[i];
+      if (rp[r + 1] - rp[r] <= kVsMaxLen) orows.push_back(r);
+    }
+    if ((int64_t)orows.size() > optr.back()) optr.push_back((int64_t)orows.size());
+  }
+  return true;
+}
 
 constexpr int kVsBatchRows = 16;   // rows a batch descriptor names (16 x uint64 = 128 bytes)
 constexpr int kVsRefineW = 2048;   // window a block halved for its window may keep (slots): 8 workgroups per CU; B at N = 74: 0.129 ms (4096: 0.138, 1536: 0.170, general kernel 0.414)
@@ -2800,14 +2894,21 @@ static bool vs_refine_blocks(int64_t nrows, const int64_t *rp, const double *val
 
 static void plan_vs(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int RB, int maxW,
                     int GAP, int64_t nb_in, const int64_t *bptr_in, const int32_t *brows_in, VsPlan &pl,
-                    bool share = true, int wide = 0, int64_t n_local_cols = -1) {
-  std::vector<int64_t> r_ptr;
-  std::vector<int32_t> r_rows;
+                    bool share = true, int wide = 0, int64_t n_local_cols = -1, bool side = false) {
+  std::vector<int64_t> r_ptr, s_ptr;
+  std::vector<int32_t> r_rows, s_rows;
+  int64_t n_listed = nrows;   // rows the blocks list
+  if (side && nrows > 0 && vs_take_side_rows(nrows, rp, col, val, RB, nb_in, bptr_in, brows_in, n_local_cols, pl, s_ptr, s_rows)) {
+    // the blocks without the side rows, as a caller's blocks; where the variant is refused the plan is today's
+    nb_in = (int64_t)s_ptr.size() - 1, bptr_in = s_ptr.data(), brows_in = s_rows.data();
+    n_listed = (int64_t)s_rows.size();
+    if (nb_in == 0) return;
+  }
   const int max_dict = wide ? VsFmt<1>::kMaxDict : VsFmt<0>::kMaxDict, code_shift = wide ? VsFmt<1>::kCodeShift : VsFmt<0>::kCodeShift;
   maxW = std::min(maxW, wide ? VsFmt<1>::kMaxSlots : VsFmt<0>::kMaxSlots);
   pl.wide = wide;
   pl.nb_in = nb_in > 0 ? nb_in : (nrows + RB - 1) / RB;
-  if (nrows == 0 || !vs_refine_blocks(nrows, rp, val, RB, nb_in, bptr_in, brows_in, r_ptr, r_rows, kVsMaxRows, max_dict)) return;
+  if (nrows == 0 || !vs_refine_blocks(n_listed, rp, val, RB, nb_in, bptr_in, brows_in, r_ptr, r_rows, kVsMaxRows, max_dict)) return;
   pl.dict_split = (int64_t)r_ptr.size() - 1 > pl.nb_in;
   if (n_local_cols >= 0) {
     // partitioned operator: the blocks that read no halo column (columns >= n_local_cols) first, so that they can run
@@ -3344,6 +3445,7 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
   int RB = ctx->vs_RB, NW = ctx->vs_NW;
   const bool forced = slot == kScratchSlot && ctx->vs_force_RB > 0;
   if (forced) RB = ctx->vs_force_RB, NW = ctx->vs_force_NW;
+  const bool side = ctx->vs_side != 0;
   const int64_t nlc = (ctx->nranks > 1 && !m.rep) ? (int64_t)m.n_local_cols : -1;   // columns >= nlc are halo columns
   bool hint = slot >= 0 && slot < ALFD_NSLOTS && !ctx->rb_ptr[slot].empty();
   if (hint && ctx->rb_ptr[slot].back() != m.nrows) {
@@ -3368,9 +3470,9 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
     for (size_t i = 0; good && i + 1 < bp.size(); ++i) good = bp[i] <= bp[i + 1];
     if (!good) return ctx->err = "alfd_set_row_blocks: the blocks are not a partition of the matrix rows", ALFD_E_INVALID;
     plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, (int64_t)bp.size() - 1, bp.data(),
-            br.data(), pl, ctx->vs_share != 0, 0, nlc);
+            br.data(), pl, ctx->vs_share != 0, 0, nlc, side);
   } else {
-    plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pl, ctx->vs_share != 0, 0, nlc);
+    plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pl, ctx->vs_share != 0, 0, nlc, side);
   }
   if (ctx->vs_wide && (!pl.ok || pl.dict_split)) {
     // blocks with more than 512 distinct values had to be halved (or the plan failed): the same blocks with 10-bit
@@ -3378,9 +3480,9 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
     VsPlan pw;
     if (hint)
       plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, (int64_t)ctx->rb_ptr[slot].size() - 1,
-              ctx->rb_ptr[slot].data(), ctx->rb_rows[slot].data(), pw, ctx->vs_share != 0, 1, nlc);
+              ctx->rb_ptr[slot].data(), ctx->rb_rows[slot].data(), pw, ctx->vs_share != 0, 1, nlc, side);
     else
-      plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pw, ctx->vs_share != 0, 1, nlc);
+      plan_vs(m.nrows, rp, col, val, RB, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, pw, ctx->vs_share != 0, 1, nlc, side);
     if (pw.ok && (!pl.ok || pw.stream.size() + 128 * (size_t)pw.nbatch < pl.stream.size() + 128 * (size_t)pl.nbatch)) pl = std::move(pw);
   }
   if (!pl.ok) return ALFD_OK;
@@ -3393,7 +3495,7 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
     vs_small_shape(m.nrows, pl.nb, pl.nbatch, RB, NW, ctx->vs_cus, &rs, &ws);
     if (rs != RB || ws != NW) {
       VsPlan ps;
-      plan_vs(m.nrows, rp, col, val, rs, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, ps, ctx->vs_share != 0, 0, nlc);
+      plan_vs(m.nrows, rp, col, val, rs, ctx->win_maxW, ctx->win_gap, 0, nullptr, nullptr, ps, ctx->vs_share != 0, 0, nlc, side);
       if (ps.ok && !ps.dict_split) {
         pl = std::move(ps);
         RB = rs, NW = ws, small = true;
@@ -3434,7 +3536,18 @@ static int build_vs(alfd_ctx *ctx, DevCsr &m, int slot, const int64_t *rp, const
   RC(upload_vec(ctx, m, &v.hdrb, hdrb));
   RC(upload_vec(ctx, m, &v.segx, segx));
   RC(upload_vec(ctx, m, &v.dict, pl.dict));
+  if (!pl.side_rows.empty()) {
+    RC(upload_vec(ctx, m, &v.side_rows, pl.side_rows));
+    RC(upload_vec(ctx, m, &v.side_rp, pl.side_rp));
+    RC(upload_vec(ctx, m, &v.side_col, pl.side_col));
+    RC(upload_vec(ctx, m, &v.side_val, pl.side_val));
+  }
   HIPC(hipStreamSynchronize(ctx->stream));
+  v.side_n = (int64_t)pl.side_rows.size();
+  v.side_nnz = (int64_t)pl.side_col.size();
+  v.side_longest = 0;
+  for (int64_t i = 0; i < v.side_n; ++i) v.side_longest = std::max(v.side_longest, pl.side_rp[i + 1] - pl.side_rp[i]);   // the boundary group has its own longest
+  v.side_interior = pl.side_interior;
   v.seg_stride = S;
   v.nb_interior = pl.nb_interior;
   v.nb = pl.nb;
@@ -4150,6 +4263,7 @@ static bool tail_in_form(alfd_ctx *ctx, const DevCsr &A, const DevCsr &Ct, int64
   if (!A.present || A.sparse || A.n_list == 0 || A.nrows > npad || A.nrows > INT32_MAX) return false;
   if (!(A.vs.on && ctx->vs_enable && !ctx->vi_off) || A.vs.L != 64 || A.vs.NW != 4 || A.vs.nb <= 0) return false;
   if ((size_t)(A.vs.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)A.vs.tail_lds > kVsTailLdsLimit) return false;
+  if (A.vs.side_n > 0) return false;   // side rows have no block end: the level keeps the two-launch tail
   if (!Ct.present || 2 * Ct.n_list >= A.nrows) return false;   // e.g. the patch operator: every row is Ct's, nothing to gain
   return vs_lds_base_ok(ctx);
 }
@@ -9265,6 +9379,17 @@ int alfd_get_matrix_shape(alfd_ctx_t ctx, int slot, alfd_batch_major_shape *out)
   return ALFD_OK;
 }
 
+int alfd_get_side_rows(alfd_ctx_t ctx, int slot, alfd_side_rows_info *out) {
+  CHECK_CTX();
+  if (slot < 0 || slot >= ALFD_NSLOTS || !ctx->mat[slot].present || !out) return ALFD_E_INVALID;
+  const DevCsr::Vs &v = ctx->mat[slot].vs;
+  std::memset(out, 0, sizeof(*out));
+  if (!(v.on && ctx->vs_enable) || v.side_n == 0) return ALFD_OK;
+  out->rows = v.side_n, out->nnz = v.side_nnz, out->longest = v.side_longest;
+  out->interior_rows = v.side_interior, out->grid = side_grid(v.side_n);
+  return ALFD_OK;
+}
+
 // the operators the library builds for itself (alfd_operator): null when the context has none such
 static DevCsr *own_operator(alfd_ctx *ctx, int op, int level) {
   DevCsr *m = nullptr;
@@ -9514,18 +9639,18 @@ int alfd_host_row_blocks_from_points(int64_t nrows, int32_t dim, const double *p
   return ALFD_OK;
 }
 
-int alfd_host_stream_plan(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int32_t row_block,
-                          int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows,
-                          alfd_stream_plan_info *out) {
+// the plan of alfd_host_stream_plan (side: of alfd_host_stream_plan_side), decoded back; seen: the rows the blocks list
+static int host_stream_plan(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int32_t row_block,
+                            int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows, bool side, VsPlan &pl,
+                            std::vector<uint8_t> &seen, alfd_stream_plan_info *out) {
   if (!rp || !out || nrows < 0 || row_block < 1 || row_block > kVsMaxRows) return ALFD_E_INVALID;
   std::memset(out, 0, sizeof(*out));
-  VsPlan pl;
-  if (n_blocks > 0) plan_vs(nrows, rp, col, val, row_block, 4096, 8, n_blocks, block_ptr, rows, pl);
-  else plan_vs(nrows, rp, col, val, row_block, 4096, 8, 0, nullptr, nullptr, pl);
+  if (n_blocks > 0) plan_vs(nrows, rp, col, val, row_block, 4096, 8, n_blocks, block_ptr, rows, pl, true, 0, -1, side);
+  else plan_vs(nrows, rp, col, val, row_block, 4096, 8, 0, nullptr, nullptr, pl, true, 0, -1, side);
   if (!pl.ok || pl.dict_split) {   // as build_vs: wide codes when the 512-value limit halved blocks
     VsPlan pw;
-    if (n_blocks > 0) plan_vs(nrows, rp, col, val, row_block, 4096, 8, n_blocks, block_ptr, rows, pw, true, 1);
-    else plan_vs(nrows, rp, col, val, row_block, 4096, 8, 0, nullptr, nullptr, pw, true, 1);
+    if (n_blocks > 0) plan_vs(nrows, rp, col, val, row_block, 4096, 8, n_blocks, block_ptr, rows, pw, true, 1, -1, side);
+    else plan_vs(nrows, rp, col, val, row_block, 4096, 8, 0, nullptr, nullptr, pw, true, 1, -1, side);
     if (pw.ok && (!pl.ok || pw.stream.size() + 128 * (size_t)pw.nbatch < pl.stream.size() + 128 * (size_t)pl.nbatch)) pl = std::move(pw);
   }
   const int code_shift = pl.wide ? VsFmt<1>::kCodeShift : VsFmt<0>::kCodeShift;
@@ -9540,7 +9665,7 @@ int alfd_host_stream_plan(int64_t nrows, const int64_t *rp, const int32_t *col, 
   out->dictionary_entries = (int64_t)pl.dict.size();
   out->stream_bytes = (int64_t)pl.stream.size() - 4096;
   out->shared_nnz = pl.shared_nnz;
-  std::vector<uint8_t> seen(nrows, 0);
+  seen.assign(nrows, 0);
   int64_t bad = 0, covered = 0;
   std::vector<int32_t> slot_col;
   for (int64_t b = 0; b < pl.nb; ++b) {
@@ -9594,6 +9719,44 @@ int alfd_host_stream_plan(int64_t nrows, const int64_t *rp, const int32_t *col, 
   }
   out->decode_mismatches = bad;
   out->rows_covered = covered;
+  return ALFD_OK;
+}
+
+int alfd_host_stream_plan(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int32_t row_block,
+                          int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows,
+                          alfd_stream_plan_info *out) {
+  VsPlan pl;
+  std::vector<uint8_t> seen;
+  return host_stream_plan(nrows, rp, col, val, row_block, n_blocks, block_ptr, rows, false, pl, seen, out);
+}
+
+int alfd_host_stream_plan_side(int64_t nrows, const int64_t *rp, const int32_t *col, const double *val, int32_t row_block,
+                               int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows, int64_t *n_side_out,
+                               int32_t *side_rows_out, int64_t *side_nnz_out, alfd_stream_plan_info *out) {
+  if (!n_side_out || !side_rows_out || !side_nnz_out) return ALFD_E_INVALID;
+  *n_side_out = *side_nnz_out = 0;
+  VsPlan pl;
+  std::vector<uint8_t> seen;
+  RC(host_stream_plan(nrows, rp, col, val, row_block, n_blocks, block_ptr, rows, true, pl, seen, out));
+  if (!pl.ok) return ALFD_OK;
+  // the side list: every row in the blocks or in the list, never in both; the compact CSR is the row, entry by entry
+  int64_t bad = 0;
+  const int64_t ns = (int64_t)pl.side_rows.size();
+  for (int64_t i = 0; i < ns; ++i) {
+    const int32_t r = pl.side_rows[i];
+    side_rows_out[i] = r;
+    if (r < 0 || r >= nrows || seen[r]) { ++bad; continue; }
+    seen[r] = 2;
+    const int64_t k0 = pl.side_rp[i], n = pl.side_rp[i + 1] - k0;
+    if (n != rp[r + 1] - rp[r]) { ++bad; continue; }
+    for (int64_t k = 0; k < n; ++k)
+      if (pl.side_col[k0 + k] != col[rp[r] + k] || std::memcmp(&pl.side_val[k0 + k], &val[rp[r] + k], 8) != 0) ++bad;
+  }
+  for (int64_t r = 0; r < nrows; ++r)
+    if (!seen[r]) ++bad;
+  *n_side_out = ns;
+  *side_nnz_out = (int64_t)pl.side_col.size();
+  out->decode_mismatches += bad;
   return ALFD_OK;
 }
 
@@ -9771,6 +9934,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "batch_major_wide") == 0) {   // 0: never plan 10-bit codes (at the next alfd_set_matrix)
     ctx->vs_wide = value != 0;
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "batch_major_side_rows") == 0) {   // 1: rows beyond kVsMaxLen entries go to a side list (at the next alfd_set_matrix / alfd_setup)
+    if (value != 0 && value != 1) return ctx->err = "batch_major_side_rows: 0 or 1", ALFD_E_INVALID;
+    ctx->vs_side = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "batch_major_waves") == 0) {

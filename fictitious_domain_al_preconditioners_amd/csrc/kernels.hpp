@@ -2857,4 +2857,70 @@ __global__ __launch_bounds__(kBlock) void unpack_blocks_kernel(BlockTable tab, c
   }
 }
 
+// --------------------------------------------------------------------------
+// Side rows of a long-row batch-major operator ("batch_major_side_rows"): the few rows beyond kVsMaxLen entries that
+// the planner keeps out of the row blocks, in a compact CSR of their own (rows[i]: global row of list entry i, longest
+// first; rp: 64-bit offsets into col / val, the entries in the row's own order).  One wave per row, 4 waves per
+// workgroup, list entry 4 blockIdx.x + wave first, so the longest rows start first.  Canonical arithmetic of 64-lane
+// rows: entry k belongs to lane k mod 64, one fma chain per lane in ascending k, then group_reduce<64> -- what
+// spmv_rows<64, ...> computes, bit for bit.
+// A row is 385 .. 65 535 entries, i.e. 7 or more 64-entry chunks of ONE dependent chain (col -> x -> fma), and the launch
+// has far fewer waves than the chip has slots: what bounds it is the latency of a round trip, not bandwidth.  So a pass
+// issues the column and value loads of kSideU chunks, then their x gathers, then the fmas: 2 kSideU + kSideU independent
+// loads per lane and pass instead of 3.  kSideU = 8 (20 VGPRs of loads per lane, 10 KB per wave in flight) covers the
+// 807 .. 855-entry rows of the locally refined mesh in two passes; the one accumulator keeps the order of the chain.
+constexpr int kSideU = 8;
+constexpr int kSideMaxLen = 65535;   // longest side row (the planner refuses the variant beyond)
+template <int EPI>
+__global__ __launch_bounds__(kBlock) void spmv_side_rows_kernel(
+    int64_t n_side, const int32_t *__restrict__ rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
+    const double *__restrict__ val, const double *__restrict__ x, const double *__restrict__ x_halo, int32_t n_local,
+    double *__restrict__ y, double alpha, const double *__restrict__ d, double *__restrict__ y2) {
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_side; i += (int64_t)gridDim.x * 4) {   // wave-uniform
+    const int64_t k0 = rp[i];
+    const int32_t n = (int32_t)(rp[i + 1] - k0);
+    const int32_t *cb = col + k0;
+    const double *vb = val + k0;
+    double acc = 0.0;
+    for (int32_t base = 0; base < n; base += 64 * kSideU) {
+      int32_t c[kSideU];
+      double v[kSideU], xv[kSideU];
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u) {
+        const int32_t o = base + 64 * u + lane;
+        c[u] = -1;
+        v[u] = 0.0;
+        if (o < n) {
+          c[u] = cb[o];
+          v[u] = vb[o];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u) {
+        xv[u] = 0.0;
+        if (c[u] >= 0) xv[u] = (c[u] < n_local) ? x[c[u]] : x_halo[c[u] - n_local];
+      }
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u)
+        if (c[u] >= 0) acc = fma(v[u], xv[u], acc);
+    }
+    acc = group_reduce<64>(acc);
+    if (lane == 0) {
+      const int64_t ro = rows[i];
+      if (EPI == 0)
+        y[ro] = acc;
+      else if (EPI == 1)
+        y[ro] = fma(alpha, acc, y[ro]);
+      else if (EPI == 2)
+        y[ro] = d[ro] * acc;
+      else {
+        y[ro] = acc;
+        y2[ro] = d[ro] * acc;
+      }
+    }
+  }
+}
+
 }  // namespace alfd

@@ -45,6 +45,7 @@ ABI_SYMBOLS = [
     "alfd_upload_rhs_device", "alfd_download_solution_device", "alfd_solve_device", "alfd_precond_apply_device",
     "alfd_system_apply_device", "alfd_augment_rhs_device",
     "alfd_get_matrix_shape", "alfd_get_operator_shape", "alfd_bench_operator", "alfd_host_small_shape",
+    "alfd_host_stream_plan_side", "alfd_get_side_rows",
     "alfd_host_sparse_product", "alfd_sparse_product", "alfd_smoothed_prolongator",
     "alfd_setup_coupling", "alfd_get_setup_counts",
     "alfd_set_preconditioner_values", "alfd_get_preconditioner_values", "alfd_spmv_preconditioner",
@@ -154,6 +155,9 @@ def load_library():
         "alfd_host_stream_plan": (C.c_int, [i64, vp, vp, vp, C.c_int32, i64, vp, vp, vp]),
         "alfd_host_row_blocks_from_points": (C.c_int, [i64, C.c_int32, vp, C.c_int32, vp, vp, vp]),
         "alfd_host_stream_plan_short": (C.c_int, [i64, vp, vp, vp, C.c_int32, vp]),
+        "alfd_host_stream_plan_side": (C.c_int, [i64, vp, vp, vp, C.c_int32, i64, vp, vp, C.POINTER(i64), vp,
+                                                 C.POINTER(i64), vp]),
+        "alfd_get_side_rows": (C.c_int, [vp, C.c_int, C.POINTER(_abi.SideRowsInfo)]),
         "alfd_host_numbering_from_points": (C.c_int, [i64, C.c_int32, vp, vp]),
         "alfd_host_brick_blocks_from_points": (C.c_int, [i64, C.c_int32, vp, vp, C.c_int32, vp, vp, vp]),
         "alfd_host_permute_csr": (C.c_int, [i64, vp, vp, vp, vp, vp, vp, vp, vp]),
@@ -786,6 +790,13 @@ class Context:
         out.update({k: v for k, v in shape.as_dict().items() if k not in out})
         return out
 
+    def side_rows(self, slot):
+        """alfd_get_side_rows: rows, nnz, longest, interior_rows and grid of the side list of a long-row batch-major
+        matrix (tunable "batch_major_side_rows"); all zero for a matrix without one."""
+        info = _abi.SideRowsInfo()
+        self._ck(self._lib.alfd_get_side_rows(self._h, slot, C.byref(info)))
+        return {k: getattr(info, k) for k, _ in info._fields_}
+
     def operator_info(self, op, level=0):
         """The batch-major shape of an operator the library built at setup (alfd_get_operator_shape), keys as in
         matrix_info: _abi.OPERATOR_LEVEL with level >= 1, _abi.OPERATOR_PATCH_SS, _abi.OPERATOR_PATCH_S."""
@@ -1172,14 +1183,29 @@ def row_blocks_from_points(points, max_rows=192):
     return ptr[:nb.value + 1].copy(), rows
 
 
-def host_stream_plan(m, row_block=96, blocks=None):
+def host_stream_plan(m, row_block=96, blocks=None, side_rows=False):
     """Host-only plan + decode of the batch-major format (alfd_host_stream_plan);
-    blocks = (block_ptr, rows) as for Context.set_row_blocks, or None for runs of row_block rows."""
+    blocks = (block_ptr, rows) as for Context.set_row_blocks, or None for runs of row_block rows.
+    side_rows=True: as planned under the tunable "batch_major_side_rows" (alfd_host_stream_plan_side); the result then
+    also has "side_rows" (the rows of the side list, in its order) and "side_nnz"."""
     lib = load_library()
     rp = np.ascontiguousarray(m.row_ptr, np.int64)
     col = np.ascontiguousarray(m.col, np.int32)
     val = np.ascontiguousarray(m.val, np.float64)
     info = _abi.StreamPlanInfo()
+    if side_rows:
+        bp = None if blocks is None else np.ascontiguousarray(blocks[0], np.int64)
+        rw = None if blocks is None else np.ascontiguousarray(blocks[1], np.int32)
+        n_side, side_nnz, side = C.c_int64(), C.c_int64(), np.zeros(max(m.nrows, 1), np.int32)
+        rc = lib.alfd_host_stream_plan_side(m.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, row_block,
+                                            0 if bp is None else bp.size - 1, None if bp is None else bp.ctypes.data,
+                                            None if rw is None else rw.ctypes.data, C.byref(n_side), side.ctypes.data,
+                                            C.byref(side_nnz), C.byref(info))
+        if rc != _abi.OK:
+            raise AlfdError(rc, "alfd_host_stream_plan_side failed")
+        out = {k: getattr(info, k) for k, _ in info._fields_}
+        out["side_rows"], out["side_nnz"] = side[:n_side.value].copy(), side_nnz.value
+        return out
     if blocks is None:
         rc = lib.alfd_host_stream_plan(m.nrows, rp.ctypes.data, col.ctypes.data, val.ctypes.data, row_block,
                                        0, None, None, C.byref(info))

@@ -921,6 +921,23 @@ typedef struct alfd_stream_plan_info {
 int alfd_host_stream_plan(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
                           int32_t row_block, int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows,
                           alfd_stream_plan_info *out);
+/* The same with side rows (tunable "batch_major_side_rows" = 1): plans as alfd_set_matrix would with the tunable on and
+ * decodes the blocks as alfd_host_stream_plan does; rows_covered counts the rows of the blocks only.  *n_side_out rows
+ * went to the side list, side_rows_out (capacity nrows) names them in the order of the list, *side_nnz_out is the number
+ * of their entries; a side row whose compact CSR copy does not reproduce the input row, and a row that is in both or in
+ * neither of blocks and list, count into decode_mismatches.  Where the variant is refused (no row beyond 384 entries,
+ * more than 1/8 of the entries in such rows, a row beyond 65 535 entries) the result is alfd_host_stream_plan's. */
+int alfd_host_stream_plan_side(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
+                               int32_t row_block, int64_t n_blocks, const int64_t *block_ptr, const int32_t *rows,
+                               int64_t *n_side_out, int32_t *side_rows_out, int64_t *side_nnz_out,
+                               alfd_stream_plan_info *out);
+/* The side list of a matrix slot in the long-row batch-major form (all fields 0 for a matrix without one): its rows,
+ * their entries, the longest of them, how many of them read no halo column (partitioned contexts, where these go with
+ * the interior blocks; else 0) and the workgroups of the side launch over the whole list. */
+typedef struct alfd_side_rows_info {
+  int64_t rows, nnz, longest, interior_rows, grid;
+} alfd_side_rows_info;
+int alfd_get_side_rows(alfd_ctx_t ctx, int slot, alfd_side_rows_info *out);
 /* The same for a short-row matrix (lanes = 8, 16 or 32, see alfd_matrix_lanes): the batch-major form of
  * spmv_vss_kernel -- one stored template row per batch of translate rows -- planned on runs of the numbering and
  * decoded back.  stream_bytes includes the batch descriptors. */
@@ -1057,6 +1074,15 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  patch operators the library builds whose default plan gives fewer blocks x waves than half the resident
  *                  wave slots of the device (16 per compute unit) are planned with smaller row blocks, down to one batch
  *                  per wave; 0: rows / waves above for every operator.  At the next alfd_setup.
+ *                  "batch_major_side_rows" (0/1, default 0; other values are refused with ALFD_E_INVALID; at the next
+ *                  alfd_set_matrix / alfd_setup): 1: the long-row form, which takes rows of at most 384 entries and
+ *                  otherwise refuses the whole matrix, keeps longer rows out of its row blocks and stores them in a
+ *                  side list (plain CSR, longest row first) that spmv_side_rows_kernel computes in a launch of its
+ *                  own behind every batch-major launch, timed with it; alfd_get_last_spmv_launch keeps describing the
+ *                  batch-major launch, alfd_get_side_rows the list.  Same bits.  Not used when no row is that long
+ *                  (the plan is then the one of 0), when such rows hold more than 1/8 of the entries, or when one has
+ *                  more than 65 535.  An operator with side rows keeps the two-launch tail: "ml_tail_in_spmv" does not
+ *                  apply to it (the launch with the block-end tail refuses such an operator), since a side row has no block end.
  *   "nested_mp_host_stepped" (0/1, default 0): grad_div_in_A = 0, one rank: the nested CG on Mp inside Aug is
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
