@@ -353,6 +353,7 @@ struct alfd_ctx {
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
   int ml_fuse = 2;                            // fused smoother steps: aug_tail_kernel, pair launches ("ml_fuse", ALFD_ML_FUSE)
   int ml_tail_in_spmv = 1;                    // "ml_tail_in_spmv", ALFD_ML_TAIL_IN_SPMV: the element-wise tails at the block end of the batch-major A launch
+  int ml_tail_side_rows = 0;                  // "ml_tail_side_rows" = 1: an operator with side rows runs that form too, its side rows' tails in spmv_side_rows_tail_kernel
   int64_t fused_tail_launches = 0;            // launches of that form since alfd_create (alfd_get_fused_tail_launches)
   int ml_tail_rows = 0;                       // "ml_tail_rows": levels >= 1 of hierarchy 1 with at most this many unknowns
                                               // run in one launch (ml_tail_kernel); 0 = off (the measured default)
@@ -4263,7 +4264,8 @@ static bool tail_in_form(alfd_ctx *ctx, const DevCsr &A, const DevCsr &Ct, int64
   if (!A.present || A.sparse || A.n_list == 0 || A.nrows > npad || A.nrows > INT32_MAX) return false;
   if (!(A.vs.on && ctx->vs_enable && !ctx->vi_off) || A.vs.L != 64 || A.vs.NW != 4 || A.vs.nb <= 0) return false;
   if ((size_t)(A.vs.wide ? VsFmt<1>::kWinOff : VsFmt<0>::kWinOff) + (size_t)A.vs.tail_lds > kVsTailLdsLimit) return false;
-  if (A.vs.side_n > 0) return false;   // side rows have no block end: the level keeps the two-launch tail
+  // side rows have no block end: their tails run in a launch of their own behind it ("ml_tail_side_rows", one rank)
+  if (A.vs.side_n > 0 && !(ctx->ml_tail_side_rows && ctx->nranks == 1)) return false;
   if (!Ct.present || 2 * Ct.n_list >= A.nrows) return false;   // e.g. the patch operator: every row is Ct's, nothing to gain
   return vs_lds_base_ok(ctx);
 }
@@ -4293,6 +4295,8 @@ static bool tail_writes(int mode, const AugTailArgs &p, const double *y, const d
 // y = A x with the tail of `mode` on the rows Ct does not list, tlam = w .* (C x) beside it (the second party of the
 // launch where the pair launch applies, a launch of its own where it does not).  Inside the launch other workgroups
 // still stage x while the first ones store: an output that is x would be a race, and is refused here.
+// Side rows ("ml_tail_side_rows"): a second launch behind the first, spmv_side_rows_tail_kernel, forms their sums and
+// applies their tails; the same refusal covers it.
 // vec_bytes: per element, of the element-wise kernel(s) the tail stands for (they read y back: 8 of them are not moved,
 // nor are the 8 of the y store).
 static int launch_vs_tail(alfd_ctx *ctx, const AugOp &F, const double *x, double *y, int mode, AugTailArgs p, double vec_bytes) {
@@ -4322,6 +4326,11 @@ static int launch_vs_tail(alfd_ctx *ctx, const AugOp &F, const double *x, double
         else launch_vs_kernel<0, TAG, 4, 0, false, TM>(ctx, A, x, y, 0.0, nullptr, nullptr, grid, 0, NoPair(), ta);
       });
     });
+    if (v.side_n > 0)   // kSideAll: one rank (tail_in_form).  The batch-major launch before it has finished with x.
+      with_const_or_last<TAIL_STEP, TAIL_LAST, TAIL_LAST_ADD, TAIL_RES, TAIL_RES_INIT>(mode, [&](auto tm_) {
+        hipLaunchKernelGGL((spmv_side_rows_tail_kernel<decltype(tm_)::value>), dim3((unsigned)side_grid(v.side_n)), dim3(kBlock), 0,
+                           ctx->stream, v.side_n, v.side_rows, v.side_rp, v.side_col, v.side_val, x, y, F.mask, p);
+      });
     HIPC(hipGetLastError());
     ++ctx->fused_tail_launches;
     if (pair || !F.C) return ALFD_OK;
@@ -9967,6 +9976,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "ml_fuse") == 0) {   // 0: separate launches; 1: aug_tail; 2: + pair launches; 3: + on the fine level
     ctx->ml_fuse = std::max(0, std::min(3, value));   // as ALFD_ML_FUSE: values outside 0..3 take the nearest level
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "ml_tail_side_rows") == 0) {   // 1: "ml_tail_in_spmv" also on operators with side rows; at the next alfd_setup / alfd_setup_coupling
+    if (value != 0 && value != 1) return ctx->err = "ml_tail_side_rows: 0 or 1", ALFD_E_INVALID;
+    ctx->ml_tail_side_rows = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "ml_tail_in_spmv") == 0) {   // 1: the element-wise tails of the fused smoother steps at the block end of the A launch

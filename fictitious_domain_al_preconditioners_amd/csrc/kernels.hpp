@@ -2923,4 +2923,54 @@ __global__ __launch_bounds__(kBlock) void spmv_side_rows_kernel(
   }
 }
 
+// The side rows behind the launch with the block-end tail ("ml_tail_side_rows", launch_vs_tail): a side row has no
+// block end, so its tail runs here, where its sum is formed.  The row sum is spmv_side_rows_kernel's, statement for
+// statement; lane 0 then does what vs_tail_row does with a block's row: a row Ct lists (mask) gets its y stored and is
+// finished by the rows party of aug_tail_kernel, every other row goes through aug_tail_elem<TM> and y is NOT stored.
+// Single-rank operators only (no halo).  No output of p may be x (the host refuses that): other waves still gather it.
+template <int TM>
+__global__ __launch_bounds__(kBlock) void spmv_side_rows_tail_kernel(
+    int64_t n_side, const int32_t *__restrict__ rows, const int64_t *__restrict__ rp, const int32_t *__restrict__ col,
+    const double *__restrict__ val, const double *__restrict__ x, double *__restrict__ y,
+    const uint8_t *__restrict__ mask, AugTailArgs p) {
+  static_assert(TM >= TAIL_STEP && TM <= TAIL_RES_INIT, "the modes of the block-end epilogue");
+  const int lane = threadIdx.x & 63;
+  const int wave = __builtin_amdgcn_readfirstlane(threadIdx.x >> 6);
+  for (int64_t i = (int64_t)blockIdx.x * 4 + wave; i < n_side; i += (int64_t)gridDim.x * 4) {   // wave-uniform
+    const int64_t k0 = rp[i];
+    const int32_t n = (int32_t)(rp[i + 1] - k0);
+    const int32_t *cb = col + k0;
+    const double *vb = val + k0;
+    double acc = 0.0;
+    for (int32_t base = 0; base < n; base += 64 * kSideU) {
+      int32_t c[kSideU];
+      double v[kSideU], xv[kSideU];
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u) {
+        const int32_t o = base + 64 * u + lane;
+        c[u] = -1;
+        v[u] = 0.0;
+        if (o < n) {
+          c[u] = cb[o];
+          v[u] = vb[o];
+        }
+      }
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u) {
+        xv[u] = 0.0;
+        if (c[u] >= 0) xv[u] = x[c[u]];
+      }
+#pragma unroll
+      for (int u = 0; u < kSideU; ++u)
+        if (c[u] >= 0) acc = fma(v[u], xv[u], acc);
+    }
+    acc = group_reduce<64>(acc);
+    if (lane == 0) {
+      const int64_t ro = rows[i];
+      if (mask[ro]) y[ro] = acc;
+      else aug_tail_elem<TM>(p, ro, acc);
+    }
+  }
+}
+
 }  // namespace alfd

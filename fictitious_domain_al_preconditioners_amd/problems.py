@@ -590,7 +590,7 @@ def tensor_prolongators(params: dict, min_coarse: int = 400, max_levels: int = 7
     return levels
 
 
-def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels: int = 7):
+def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels: int = 7, q1_level: bool = False):
     """Geometric multigrid transfers for a locally refined problem (local_refine=1), as CSR prolongators for
     Context.set_prolongator.  The refined space has no tensor-product transfers, so level 0 maps it onto the Q1
     space of the uniform BASE grid (n_cells per direction), component by component: row i holds the multilinear
@@ -598,12 +598,22 @@ def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels
     so this is their nodal interpolation).  Dirichlet and hanging rows are empty, i.e. not represented; the
     coarse unknowns are the interior nodes of the base grid, lexicographic and node-major.  The levels below are
     those of tensor_prolongators for the base grid.  Follows the problem's node renumbering (u_points does).
+    q1_level=True (degree 2; degree 1 IS the Q1 space of the refined mesh: ValueError) puts the Q1 space of the REFINED
+    mesh between the two: [(P0, n1), (P1, n_base), the tensor levels as before] with P0 P1 = the level 0 above, value
+    for value.  Its unknowns are the leaf-cell vertices that are neither on the boundary nor hanging for Q1
+    (refined_q1_vertices), in ascending node number; a row of P0 holds the multilinear weights of the node's leaf cell,
+    a hanging vertex replaced by its masters; P1 the base-grid weights at the Q1 unknowns.  Neither carries explicit
+    zeros.
     Returns [(Csr P, n_coarse), ...]."""
     import scipy.sparse as sp
     P = pb.params
     if not P.get("local_refine"):
         raise ValueError("refined_prolongators needs a locally refined problem (local_refine=1)")
     dim, ncomp, n = P["dim"], P["ncomp"], P["n_cells"]
+    if q1_level:
+        if P["degree"] != 2:
+            raise ValueError("refined_prolongators(q1_level=True) needs degree 2: the degree-1 space is Q1 on the refined mesh")
+        return _refined_q1_transfers(pb) + _base_grid_levels(dim, ncomp, n, min_coarse, max_levels - 2)
     pts = pb.vecs["u_points"].reshape(-1, dim)
     s = (pts - P["lo"]) * (n / (P["hi"] - P["lo"]))               # position in base cells
     cell = np.clip(np.floor(s + 1e-9).astype(np.int64), 0, n - 1)
@@ -629,8 +639,14 @@ def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels
                        shape=(pts.shape[0], (n - 1) ** dim))
     pv = sp.kron(p0, sp.identity(ncomp)).tocsr() if ncomp > 1 else p0.tocsr()
     pv.sort_indices()
-    levels = [(Csr.from_scipy(pv), int(pv.shape[1]))]
-    if pv.shape[1] > min_coarse and max_levels > 1:
+    return [(Csr.from_scipy(pv), int(pv.shape[1]))] + _base_grid_levels(dim, ncomp, n, min_coarse, max_levels - 1)
+
+
+def _base_grid_levels(dim, ncomp, n, min_coarse, max_levels):
+    """The levels below the Q1 space on the interior nodes of the uniform base grid of n cells per direction: those of
+    tensor_prolongators, none if that space is small enough already."""
+    levels = []
+    if ncomp * (n - 1) ** dim > min_coarse and max_levels > 0:
         base = dict(dim=dim, ncomp=ncomp, degree=1, n_cells=n)
         # tensor_prolongators(degree 1) numbers its level-0 rows over ALL base nodes; ours are the interior ones
         idx = np.arange((n + 1) ** dim)
@@ -639,9 +655,135 @@ def refined_prolongators(pb: SyntheticProblem, min_coarse: int = 400, max_levels
             c = (idx // (n + 1) ** d) % (n + 1)
             interior &= (c > 0) & (c < n)
         sel = (np.flatnonzero(interior)[:, None] * ncomp + np.arange(ncomp)[None, :]).ravel()
-        for k, (pc, n_coarse) in enumerate(tensor_prolongators(base, min_coarse=min_coarse, max_levels=max_levels - 1)):
+        for k, (pc, n_coarse) in enumerate(tensor_prolongators(base, min_coarse=min_coarse, max_levels=max_levels)):
             levels.append((Csr.from_scipy(pc.to_scipy()[sel, :]), n_coarse) if k == 0 else (pc, n_coarse))
     return levels
+
+
+def refined_q1_vertices(pb: SyntheticProblem):
+    """The vertices of the leaf cells of a locally refined degree-2 problem among its velocity nodes, on the lattice of
+    h / 4 (h: base cell size; a base cell is 4 units, a leaf of a flagged cell 2).  Returns a dict of
+      t         integer lattice coordinates of u_points, [node, axis]
+      boundary  node on the boundary of the domain
+      leaf      node is a leaf vertex: all coordinates = 0 mod 4, or all even and in the closure of a flagged cell
+      hanging   leaf vertex with a coordinate = 2 mod 4 in the closure of an UNFLAGGED cell: hanging for Q1 (not for
+                Q2, where it coincides with a node of the coarse neighbour; u_hanging does not list it)
+      coarse    number of the node among the Q1 unknowns (leaf, not hanging, not on the boundary; ascending node
+                number), -1 for every other node
+      flagged   the base cells that are split, [n ** dim] with x fastest."""
+    P = pb.params
+    dim, n = P["dim"], P["n_cells"]
+    if not P.get("local_refine") or P["degree"] != 2:
+        raise ValueError("refined_q1_vertices needs a locally refined problem of degree 2")
+    s = (pb.vecs["u_points"].reshape(-1, dim) - P["lo"]) * (4 * n / (P["hi"] - P["lo"]))
+    t = np.rint(s).astype(np.int64)
+    if np.abs(s - t).max() > 1e-9:
+        raise ValueError("refined_q1_vertices: u_points are not on the lattice of h / 4")
+    flagged = pb.vecs["flagged_cells"] != 0
+    # the base cells whose closure holds the node: per axis (t + 3) // 4 - 1 and t // 4, the same unless t = 0 mod 4
+    lo_hi = (np.clip((t + 3) // 4 - 1, 0, n - 1), np.clip(t // 4, 0, n - 1))
+    in_flagged = np.zeros(t.shape[0], bool)
+    in_unflagged = np.zeros(t.shape[0], bool)
+    for corner in range(2 ** dim):
+        cell = np.zeros(t.shape[0], np.int64)
+        for d in reversed(range(dim)):
+            cell = cell * n + lo_hi[(corner >> d) & 1][:, d]
+        in_flagged |= flagged[cell]
+        in_unflagged |= ~flagged[cell]
+    leaf = np.all(t % 4 == 0, axis=1) | (np.all(t % 2 == 0, axis=1) & in_flagged)
+    hanging = leaf & np.any(t % 4 == 2, axis=1) & in_unflagged
+    boundary = np.any((t == 0) | (t == 4 * n), axis=1)
+    unknown = leaf & ~hanging & ~boundary
+    coarse = np.where(unknown, np.cumsum(unknown) - 1, -1)
+    return dict(t=t, boundary=boundary, leaf=leaf, hanging=hanging, coarse=coarse, flagged=flagged)
+
+
+def _refined_q1_transfers(pb: SyntheticProblem):
+    """(P0, n1), (P1, n_base) of refined_prolongators(q1_level=True)."""
+    import scipy.sparse as sp
+    P = pb.params
+    dim, ncomp, n = P["dim"], P["ncomp"], P["n_cells"]
+    V = refined_q1_vertices(pb)
+    t, coarse, flagged = V["t"], V["coarse"], V["flagged"]
+    nn, span = t.shape[0], 4 * n + 1
+
+    def key_of(tt):
+        k = np.zeros(tt.shape[0], np.int64)
+        for d in reversed(range(dim)):
+            k = k * span + tt[:, d]
+        return k
+
+    order = np.argsort(key_of(t), kind="stable")
+    keys = key_of(t)[order]
+
+    def node_at(tt):
+        k = key_of(tt)
+        pos = np.minimum(np.searchsorted(keys, k), nn - 1)
+        if np.any(keys[pos] != k):
+            raise ValueError("refined_prolongators: a leaf vertex is no velocity node")
+        return order[pos]
+
+    # P0: the multilinear weights of the node's leaf cell; 16ths are exact
+    rows = np.flatnonzero(~V["boundary"] & (pb.vecs["u_hanging"] == 0))
+    tr = t[rows]
+    b = np.clip(tr // 4, 0, n - 1)
+    cell = np.zeros(rows.size, np.int64)
+    for d in reversed(range(dim)):
+        cell = cell * n + b[:, d]
+    split = flagged[cell]
+    size = np.where(split, 2, 4)[:, None]
+    origin = 4 * b + np.where(split[:, None], 2 * np.clip((tr - 4 * b) // 2, 0, 1), 0)
+    fr = (tr - origin) / size
+    rr, vt, ww = [], [], []
+    for corner in range(2 ** dim):
+        up = (corner >> np.arange(dim)) & 1
+        w = np.prod(np.where(up[None, :] == 1, fr, 1.0 - fr), axis=1)
+        keep = w != 0.0
+        rr.append(rows[keep]); vt.append((origin + size * up[None, :])[keep]); ww.append(w[keep])
+    rr, vt, ww = np.concatenate(rr), np.concatenate(vt), np.concatenate(ww)
+    hang = V["hanging"][node_at(vt)]
+    # a hanging vertex stands for its masters: +-2 along each of its k coordinates = 2 mod 4, weight 2^-k each
+    hr, ht, hw = rr[hang], vt[hang], ww[hang]
+    half = ht % 4 == 2
+    hw = hw * 0.5 ** half.sum(axis=1)
+    rr, vt, ww = [rr[~hang]], [vt[~hang]], [ww[~hang]]
+    for corner in range(2 ** dim):
+        up = (corner >> np.arange(dim)) & 1
+        keep = np.all(half | (up[None, :] == 0), axis=1)          # one pass over the axes that are not split
+        rr.append(hr[keep]); ww.append(hw[keep])
+        vt.append((ht + np.where(half, 4 * up[None, :] - 2, 0))[keep])
+    rr, vt, ww = np.concatenate(rr), np.concatenate(vt), np.concatenate(ww)
+    cc = coarse[node_at(vt)]
+    if np.any((cc < 0) & ~V["boundary"][node_at(vt)]):
+        raise ValueError("refined_prolongators: a master vertex is hanging (more than one refinement layer?)")
+    keep = cc >= 0                                                # boundary vertices are no unknowns
+    n1 = int(coarse.max()) + 1
+    p0 = sp.csr_matrix((ww[keep], (rr[keep], cc[keep])), shape=(nn, n1))      # sums duplicates
+
+    # P1: the multilinear weights of the base grid at the Q1 unknowns, as level 0 of q1_level=False takes them at u_points
+    own = np.flatnonzero(coarse >= 0)
+    tc = t[own]
+    b = np.clip(tc // 4, 0, n - 1)
+    fr = (tc - 4 * b) / 4
+    rr, cc, ww = [], [], []
+    for corner in range(2 ** dim):
+        up = (corner >> np.arange(dim)) & 1
+        w = np.prod(np.where(up[None, :] == 1, fr, 1.0 - fr), axis=1)
+        c = b + up[None, :]
+        j = np.zeros(own.size, np.int64)
+        for d in reversed(range(dim)):
+            j = j * (n - 1) + (c[:, d] - 1)
+        keep = (w != 0.0) & np.all((c > 0) & (c < n), axis=1)
+        rr.append(np.flatnonzero(keep)); cc.append(j[keep]); ww.append(w[keep])
+    p1 = sp.csr_matrix((np.concatenate(ww), (np.concatenate(rr), np.concatenate(cc))), shape=(n1, (n - 1) ** dim))
+
+    out = []
+    for p in (p0, p1):
+        pv = sp.kron(p, sp.identity(ncomp)).tocsr() if ncomp > 1 else p.tocsr()
+        pv.eliminate_zeros()
+        pv.sort_indices()
+        out.append((Csr.from_scipy(pv), int(pv.shape[1])))
+    return out
 
 
 def immersed_tensor_prolongators(params: dict, min_coarse: int = 100, max_levels: int = 7):

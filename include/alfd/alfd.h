@@ -738,8 +738,9 @@ typedef struct alfd_tail_step {
 /* form 0: the A launch with the block-end epilogue, then the rows party of the tail launch.  form 1: y = A x (with
  * slot_c: the solver's pair launch or its two launches), then the whole tail launch.  Same bits.  Form 0 does not ask
  * the tunable; it returns ALFD_E_UNSUPPORTED when slot_a has no epilogue instantiation (not on the long-row batch-major
- * kernel with 4 waves, its largest block beyond 20 KB of LDS with the row buffer, half or more of the rows in Ct, or
- * mode 5), and ALFD_E_INVALID, with nothing launched, when a vector the mode stores (y included) was passed at x's
+ * kernel with 4 waves, its largest block beyond 20 KB of LDS with the row buffer, half or more of the rows in Ct,
+ * side rows while the tunable "ml_tail_side_rows" is 0 -- that one it does obey, like the solver; with 1 the side rows
+ * get their tails from spmv_side_rows_tail_kernel behind the A launch -- or mode 5), and ALFD_E_INVALID, with nothing launched, when a vector the mode stores (y included) was passed at x's
  * address: inside one launch that would be a race.  Both forms: ALFD_E_UNSUPPORTED on a partitioned context, with
  * w_inverse != diagonal, aug_assembled, grad_div_in_A = 0, or a Ct that does not stay plain CSR rows. */
 int alfd_spmv_tail_step(alfd_ctx_t ctx, int slot_a, int form, const alfd_tail_step *s);
@@ -1081,8 +1082,8 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  own behind every batch-major launch, timed with it; alfd_get_last_spmv_launch keeps describing the
  *                  batch-major launch, alfd_get_side_rows the list.  Same bits.  Not used when no row is that long
  *                  (the plan is then the one of 0), when such rows hold more than 1/8 of the entries, or when one has
- *                  more than 65 535.  An operator with side rows keeps the two-launch tail: "ml_tail_in_spmv" does not
- *                  apply to it (the launch with the block-end tail refuses such an operator), since a side row has no block end.
+ *                  more than 65 535.  A side row has no block end: what "ml_tail_in_spmv" does with such an operator is
+ *                  the subject of "ml_tail_side_rows" below.
  *   "nested_mp_host_stepped" (0/1, default 0): grad_div_in_A = 0, one rank: the nested CG on Mp inside Aug is
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
@@ -1113,6 +1114,15 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  A sweep step that has to deliver into the vector its own product reads (the only step of a
  *                  degree-2 sweep without a target to add to) keeps the two launches.  Costs two more vectors per
  *                  level that qualifies.
+ *   "ml_tail_side_rows" (0/1, default 0; other values are refused with ALFD_E_INVALID): what "ml_tail_in_spmv" does with
+ *                  an operator that has side rows ("batch_major_side_rows" = 1 and rows beyond 384 entries; one rank).
+ *                  1: the launch with the block-end tail is followed, on the same stream and timed with it, by
+ *                  spmv_side_rows_tail_kernel: one wave per side row forms the row sum of spmv_side_rows_kernel and
+ *                  lane 0 stores y for a row of Ct, or applies the tail and stores no y, as the block end does for the
+ *                  other rows.  0: such an operator keeps the two-launch tail (the launch with the block-end tail
+ *                  refuses it).  Same bits either way.  A level qualifies at alfd_setup / alfd_setup_coupling (its two
+ *                  extra vectors are allocated there) with the value of that moment; afterwards 0 / 1 switch the form
+ *                  of a level that qualified at the next apply.  No launch of a context without side rows depends on it.
  *   "ml_gpu_galerkin" (0/1, default 1; environment ALFD_ML_GPU_GALERKIN, read at alfd_create): the Galerkin products of
  *                  alfd_setup with CSR prolongators and of the builders run on the device (alfd_sparse_product; inside
  *                  the builders and on replicated levels only for operators with more than 200 000 entries).  0: all
