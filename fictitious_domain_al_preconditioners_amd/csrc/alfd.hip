@@ -420,6 +420,17 @@ struct alfd_ctx {
   int vs_lds_base_ok = -1;                  // -1 unknown; the absolute LDS addressing of kernels_vs.hpp needs base 0   // batch-major format (alfd_set_tunable "batch_major")
   std::vector<int64_t> rb_ptr[ALFD_NSLOTS + 1];   // row-block hint per slot (alfd_set_row_blocks)
   std::vector<int32_t> rb_rows[ALFD_NSLOTS + 1];
+  // alfd_set_numbering: internal index k of block 0 is the caller's index n2o[k] (empty: none).  The device copies are
+  // int32, padded with zeros to whole chunks (the index loads of pack / unpack); stage: one block-0 vector in the
+  // caller's order, the stop of the host-pointer calls on their way through the same kernels.
+  struct Numbering {
+    std::vector<int64_t> n2o, o2n;
+    int32_t *perm = nullptr, *inv = nullptr;
+    double *stage = nullptr;
+    int64_t n() const { return (int64_t)n2o.size(); }
+    bool on() const { return !n2o.empty(); }
+  } num;
+  int num_unpack_scatter = 0;               // "numbering_unpack_scatter": unpack_blocks_perm_scatter_kernel instead of the gather form
   int win_short_min_blocks = 256;           // the same for short-row matrices (ALFD_SPMV_WINDOW_SHORT_MIN_BLOCKS; 64 costs cfg 3 30 %, 1024 leaves its 262 k-row level operator out)
   int win_min_blocks = 256;                 // long-row window formats need this many row blocks (ALFD_SPMV_WINDOW_MIN_BLOCKS; 1 per CU: the level-2 operator of the bench, 152 k rows, gains 2 % of the solve, the 36.7 k-row patch matrix another 1 %; 128: slower)
   int win_enable = 1, win_RB = 96, win_maxW = 4096, win_gap = 8, win_xcd = 0;  // win_xcd: XCD-contiguous block order (measured neutral on MI355X)
@@ -7093,6 +7104,8 @@ static int setup(alfd_ctx *ctx) {
     return ctx->err = "A, CT (and C) and INVW must be set", ALFD_E_NOT_SETUP;
   ctx->n[0] = ctx->mat[ALFD_A].nrows;
   ctx->n[last] = ctx->mat[ALFD_C].nrows;
+  if (ctx->num.on() && ctx->num.n() != ctx->n[0])
+    return ctx->err = "the numbering (alfd_set_numbering) does not have the size of block 0", ALFD_E_INVALID;
   if (rat) {
     const HostCsr &K = ctx->h_K, &M = ctx->h_M;
     if (K.rp.empty() || M.rp.empty()) return ctx->err = "KIMM and M must be set for the rational variant", ALFD_E_NOT_SETUP;
@@ -7353,17 +7366,66 @@ static int setup_coupling(alfd_ctx *ctx) {
   return ALFD_OK;
 }
 
-// host blocks <-> padded device block vector
+// at most 2048 workgroups, every one with the same number of chunks (up to one): 2527 chunks -> 1264 x 2
+static unsigned block_grid(int64_t nchunks) {
+  const int64_t per = (nchunks + 2047) / 2048;
+  return (unsigned)((nchunks + per - 1) / per);
+}
+
+// alfd_set_numbering: every block-vector call checks that the numbering still fits block 0
+static int numbering_fits(alfd_ctx *ctx) {
+  if (ctx->num.on() && ctx->num.n() != ctx->n[0])
+    return ctx->err = "the numbering (alfd_set_numbering) has " + std::to_string((long long)ctx->num.n()) +
+                      " entries, block 0 has " + std::to_string((long long)ctx->n[0]), ALFD_E_INVALID;
+  return ALFD_OK;
+}
+// the table of block 0 alone, its caller side the device stage (host-pointer calls under a numbering)
+static BlockTable stage_table(alfd_ctx *ctx) {
+  BlockTable t;
+  std::memset(&t, 0, sizeof(t));
+  t.nblocks = 1;
+  t.p[0] = ctx->num.stage;
+  t.n[0] = ctx->n[0];
+  for (int b = 1; b <= kMaxBlocks; ++b) t.off[b] = ctx->off[1];
+  return t;
+}
+static void launch_unpack_perm(alfd_ctx *ctx, const BlockTable &t, const double *dev, int64_t nchunks) {
+  if (ctx->num_unpack_scatter)
+    hipLaunchKernelGGL(unpack_blocks_perm_scatter_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream, t,
+                       ctx->num.perm, dev, nchunks);
+  else
+    hipLaunchKernelGGL(unpack_blocks_perm_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream, t,
+                       ctx->num.inv, dev, nchunks);
+}
+
+// host blocks <-> padded device block vector.  Under a numbering block 0 stops at the device stage in the caller's
+// order and moves between there and the internal vector in the permuting pack / unpack kernels.
 static int to_device(alfd_ctx *ctx, const double *const *blocks, double *dev) {
+  RC(numbering_fits(ctx));
+  const bool perm = ctx->num.on() && ctx->n[0] > 0;
   HIPC(hipMemsetAsync(dev, 0, ctx->ntot() * sizeof(double), ctx->stream));
-  for (int b = 0; b < ctx->nblocks; ++b)
+  for (int b = perm ? 1 : 0; b < ctx->nblocks; ++b)
     HIPC(hipMemcpyAsync(dev + ctx->off[b], blocks[b], ctx->n[b] * sizeof(double), hipMemcpyHostToDevice,
                         ctx->stream));
+  if (perm) {
+    HIPC(hipMemcpyAsync(ctx->num.stage, blocks[0], ctx->n[0] * sizeof(double), hipMemcpyHostToDevice, ctx->stream));
+    const int64_t nchunks = ctx->off[1] / kChunk;
+    hipLaunchKernelGGL(pack_blocks_perm_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                       stage_table(ctx), ctx->num.perm, dev, nchunks);
+    HIPC(hipGetLastError());
+  }
   HIPC(hipStreamSynchronize(ctx->stream));
   return ALFD_OK;
 }
 static int to_host(alfd_ctx *ctx, const double *dev, double *const *blocks) {
-  for (int b = 0; b < ctx->nblocks; ++b)
+  RC(numbering_fits(ctx));
+  const bool perm = ctx->num.on() && ctx->n[0] > 0;
+  if (perm) {
+    launch_unpack_perm(ctx, stage_table(ctx), dev, ctx->off[1] / kChunk);
+    HIPC(hipGetLastError());
+    HIPC(hipMemcpyAsync(blocks[0], ctx->num.stage, ctx->n[0] * sizeof(double), hipMemcpyDeviceToHost, ctx->stream));
+  }
+  for (int b = perm ? 1 : 0; b < ctx->nblocks; ++b)
     HIPC(hipMemcpyAsync(blocks[b], dev + ctx->off[b], ctx->n[b] * sizeof(double), hipMemcpyDeviceToHost,
                         ctx->stream));
   HIPC(hipStreamSynchronize(ctx->stream));
@@ -7432,27 +7494,31 @@ static BlockTable block_table(alfd_ctx *ctx, const double *const *blocks) {
   for (int b = ctx->nblocks; b <= kMaxBlocks; ++b) t.off[b] = ctx->ntot();
   return t;
 }
-// at most 2048 workgroups, every one with the same number of chunks (up to one): 2527 chunks -> 1264 x 2
-static unsigned block_grid(int64_t nchunks) {
-  const int64_t per = (nchunks + 2047) / 2048;
-  return (unsigned)((nchunks + per - 1) / per);
-}
-
-// dev (ntot() doubles) <- blocks, padding zeroed; enqueued on ctx->stream, no synchronisation
+// dev (ntot() doubles) <- blocks, padding zeroed; enqueued on ctx->stream, no synchronisation.  Under a numbering
+// (alfd_set_numbering) block 0 is gathered through it in the same launch.
 static int pack_device(alfd_ctx *ctx, const double *const *blocks, double *dev) {
+  RC(numbering_fits(ctx));
   const int64_t nchunks = ctx->ntot() / kChunk;
   if (nchunks == 0) return ALFD_OK;
-  hipLaunchKernelGGL(pack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
-                     block_table(ctx, blocks), dev, nchunks);
+  if (ctx->num.on())
+    hipLaunchKernelGGL(pack_blocks_perm_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                       block_table(ctx, blocks), ctx->num.perm, dev, nchunks);
+  else
+    hipLaunchKernelGGL(pack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                       block_table(ctx, blocks), dev, nchunks);
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
 // blocks <- dev, the first n[b] entries of every block; synchronises: on return the blocks are complete
 static int unpack_device(alfd_ctx *ctx, const double *dev, double *const *blocks) {
+  RC(numbering_fits(ctx));
   const int64_t nchunks = ctx->ntot() / kChunk;
   if (nchunks > 0) {
-    hipLaunchKernelGGL(unpack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
-                       block_table(ctx, blocks), dev, nchunks);
+    if (ctx->num.on())
+      launch_unpack_perm(ctx, block_table(ctx, blocks), dev, nchunks);
+    else
+      hipLaunchKernelGGL(unpack_blocks_kernel, dim3(block_grid(nchunks)), dim3(kBlock), 0, ctx->stream,
+                         block_table(ctx, blocks), dev, nchunks);
     HIPC(hipGetLastError());
   }
   HIPC(hipStreamSynchronize(ctx->stream));
@@ -7589,8 +7655,18 @@ int alfd_destroy(alfd_ctx_t ctx) {
   if (ctx->ev_x) hipEventDestroy(ctx->ev_x);
   if (ctx->ev_halo) hipEventDestroy(ctx->ev_halo);
   if (ctx->ev_in) hipEventDestroy(ctx->ev_in);
+  if (ctx->num.perm) hipFree(ctx->num.perm);
+  if (ctx->num.inv) hipFree(ctx->num.inv);
+  if (ctx->num.stage) hipFree(ctx->num.stage);
   hipStreamDestroy(ctx->stream);
   delete ctx;
+  return ALFD_OK;
+}
+
+// renumbering across a row partition is not implemented: a context has a numbering or more than one rank
+static int numbering_bars_partition(alfd_ctx *ctx) {
+  if (ctx->num.on())
+    return ctx->err = "a context with a numbering (alfd_set_numbering) cannot be partitioned", ALFD_E_UNSUPPORTED;
   return ALFD_OK;
 }
 
@@ -7607,6 +7683,7 @@ int alfd_comm_unique_id(void *id_out, size_t bytes) {
 int alfd_comm_init(alfd_ctx_t ctx, int rank, int nranks, const void *id, size_t bytes) {
   CHECK_CTX();
   if (nranks < 1 || rank < 0 || rank >= nranks) return ALFD_E_INVALID;
+  if (nranks > 1) RC(numbering_bars_partition(ctx));
   ctx->rank = rank;
   ctx->nranks = nranks;
   if (nranks == 1) return ALFD_OK;
@@ -7641,6 +7718,7 @@ int alfd_local_group_destroy(alfd_local_group *g) {
 int alfd_comm_init_local(alfd_ctx_t ctx, alfd_local_group *g, int rank) {
   CHECK_CTX();
   if (!g || rank < 0 || rank >= g->n) return ALFD_E_INVALID;
+  if (g->n > 1) RC(numbering_bars_partition(ctx));
   ctx->rank = rank;
   ctx->nranks = g->n;
   ctx->local = g->n > 1 ? g : nullptr;
@@ -7651,6 +7729,7 @@ int alfd_comm_init_host(alfd_ctx_t ctx, int rank, int nranks, alfd_host_allgathe
                         alfd_host_alltoallv_fn alltoallv, void *user) {
   CHECK_CTX();
   if (nranks < 1 || rank < 0 || rank >= nranks || !allgather || !alltoallv) return ALFD_E_INVALID;
+  if (nranks > 1) RC(numbering_bars_partition(ctx));
   ctx->rank = rank;
   ctx->nranks = nranks;
   if (nranks == 1) return ALFD_OK;
@@ -7663,6 +7742,7 @@ int alfd_comm_init_host(alfd_ctx_t ctx, int rank, int nranks, alfd_host_allgathe
 int alfd_set_partition(alfd_ctx_t ctx, int nblocks, const int64_t *const *offsets) {
   CHECK_CTX();
   if (nblocks < 2 || nblocks > ALFD_MAX_BLOCKS || !offsets) return ALFD_E_INVALID;
+  if (ctx->nranks > 1) RC(numbering_bars_partition(ctx));
   ctx->part.assign(nblocks, {});
   for (int b = 0; b < nblocks; ++b) {
     ctx->part[b].assign(offsets[b], offsets[b] + ctx->nranks + 1);
@@ -7685,6 +7765,28 @@ int alfd_set_matrix(alfd_ctx_t ctx, int slot, int64_t nrows, int64_t ncols, cons
     if (row_ptr[r + 1] < row_ptr[r]) return ctx->err = "row_ptr not monotone", ALFD_E_INVALID;
   for (int64_t k = 0; k < nnz; ++k)
     if (col[k] < 0 || col[k] >= ncols) return ctx->err = "column index out of range", ALFD_E_INVALID;
+  // alfd_set_numbering: the caller's operator becomes the internal one before anything below sees it -- rows of A, BT,
+  // CT in the new order, columns of A, B, C renamed, a row's entries sorted by new column (alfd_host_permute_csr)
+  std::vector<int64_t> prp;
+  std::vector<int32_t> pcol;
+  std::vector<double> pval;
+  if (ctx->num.on()) {
+    const bool by_row = slot == ALFD_A || slot == ALFD_BT || slot == ALFD_CT;
+    const bool by_col = slot == ALFD_A || slot == ALFD_B || slot == ALFD_C;
+    if ((by_row && nrows != ctx->num.n()) || (by_col && ncols != ctx->num.n()))
+      return ctx->err = "alfd_set_matrix: the numbering (alfd_set_numbering) has " +
+                        std::to_string((long long)ctx->num.n()) + " entries, the block-0 side of this operator " +
+                        std::to_string((long long)(by_row ? nrows : ncols)), ALFD_E_INVALID;
+    if (by_row || by_col) {
+      prp.resize((size_t)nrows + 1);
+      pcol.resize((size_t)nnz);
+      pval.resize((size_t)nnz);
+      if (alfd_host_permute_csr(nrows, row_ptr, col, val, by_row ? ctx->num.n2o.data() : nullptr,
+                                by_col ? ctx->num.o2n.data() : nullptr, prp.data(), pcol.data(), pval.data()) != ALFD_OK)
+        return ctx->err = "alfd_set_matrix: permuting the operator failed", ALFD_E_INVALID;
+      row_ptr = prp.data(), col = pcol.data(), val = pval.data();
+    }
+  }
   ctx->is_setup = false;
   ctx->gen[slot]++;
   if (ctx->nranks > 1 && ctx->nblocks == 0)
@@ -7783,11 +7885,18 @@ int alfd_set_aggregates(alfd_ctx_t ctx, int level, int64_t n_fine, const int32_t
   if (level < 0 || level >= ALFD_MAX_LEVELS || n_fine < 1 || n_coarse < 1 || !agg) return ALFD_E_INVALID;
   for (int64_t i = 0; i < n_fine; ++i)
     if (agg[i] < -1 || agg[i] >= n_coarse) return ctx->err = "aggregate id out of range", ALFD_E_INVALID;
+  if (level == 0 && ctx->num.on() && n_fine != ctx->num.n())
+    return ctx->err = "alfd_set_aggregates: level 0 does not have the size of the numbering (alfd_set_numbering)", ALFD_E_INVALID;
   ctx->hier[0].agg[level].assign(agg, agg + n_fine);
   if (weight)
     ctx->hier[0].wgt[level].assign(weight, weight + n_fine);
   else
     ctx->hier[0].wgt[level].clear();
+  if (level == 0 && ctx->num.on()) {   // the fine unknowns of level 0 are block 0: stored in the internal order
+    for (int64_t k = 0; k < n_fine; ++k) ctx->hier[0].agg[0][k] = agg[ctx->num.n2o[k]];
+    if (weight)
+      for (int64_t k = 0; k < n_fine; ++k) ctx->hier[0].wgt[0][k] = weight[ctx->num.n2o[k]];
+  }
   ctx->hier[0].ncoarse[level] = n_coarse;
   ctx->hier[0].P[level] = HostCsr();
   ctx->hier[0].built_partitioned = false;
@@ -7822,11 +7931,22 @@ int alfd_set_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t n_f
         return ctx->err = fn + ": columns must be ascending and inside [0, n_coarse)", ALFD_E_INVALID;
   alfd_ctx::Hierarchy &H = ctx->hier[block];
   HostCsr &P = H.P[level];
+  if (block == 0 && level == 0 && ctx->num.on() && n_fine != ctx->num.n())
+    return ctx->err = fn + ": level 0 does not have the size of the numbering (alfd_set_numbering)", ALFD_E_INVALID;
   P.nrows = n_fine;
   P.ncols = n_coarse;
-  P.rp.assign(row_ptr, row_ptr + n_fine + 1);
-  P.col.assign(col, col + nnz);
-  P.val.assign(val, val + nnz);
+  if (block == 0 && level == 0 && ctx->num.on()) {   // the rows of level 0 are block 0: stored in the internal order
+    P.rp.resize((size_t)n_fine + 1);
+    P.col.resize((size_t)nnz);
+    P.val.resize((size_t)nnz);
+    if (alfd_host_permute_csr(n_fine, row_ptr, col, val, ctx->num.n2o.data(), nullptr, P.rp.data(), P.col.data(),
+                              P.val.data()) != ALFD_OK)
+      return ctx->err = fn + ": permuting the rows failed", ALFD_E_INVALID;
+  } else {
+    P.rp.assign(row_ptr, row_ptr + n_fine + 1);
+    P.col.assign(col, col + nnz);
+    P.val.assign(val, val + nnz);
+  }
   H.agg[level].clear();
   H.wgt[level].clear();
   H.ncoarse[level] = n_coarse;
@@ -8016,7 +8136,10 @@ int alfd_get_aggregates_block(alfd_ctx_t ctx, int block, int level, int32_t *agg
   if (n_coarse) *n_coarse = ctx->hier[block].ncoarse[level];
   if (agg) {
     if (capacity < (int64_t)a.size()) return ALFD_E_INVALID;
-    std::copy(a.begin(), a.end(), agg);
+    if (block == 0 && level == 0 && ctx->num.on() && (int64_t)a.size() == ctx->num.n())   // back to the caller's order
+      for (size_t i = 0; i < a.size(); ++i) agg[i] = a[(size_t)ctx->num.o2n[i]];
+    else
+      std::copy(a.begin(), a.end(), agg);
   }
   return ALFD_OK;
 }
@@ -8472,6 +8595,20 @@ int alfd_get_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t *ro
   if (n_fine) *n_fine = P.nrows;
   if (n_coarse) *n_coarse = P.ncols;
   if (nnz) *nnz = P.nnz();
+  if (block == 0 && level == 0 && ctx->num.on() && P.nrows == ctx->num.n()) {   // rows back in the caller's order
+    const std::vector<int64_t> &o2n = ctx->num.o2n;
+    if ((col || val) && capacity < P.nnz()) return ALFD_E_INVALID;
+    int64_t o = 0;
+    for (int64_t i = 0; i < P.nrows; ++i) {
+      const int64_t k0 = P.rp[o2n[i]], len = P.rp[o2n[i] + 1] - k0;
+      if (row_ptr) row_ptr[i] = o;
+      if (col) std::copy(P.col.begin() + k0, P.col.begin() + k0 + len, col + o);
+      if (val) std::copy(P.val.begin() + k0, P.val.begin() + k0 + len, val + o);
+      o += len;
+    }
+    if (row_ptr) row_ptr[P.nrows] = o;
+    return ALFD_OK;
+  }
   if (row_ptr) std::copy(P.rp.begin(), P.rp.end(), row_ptr);
   if (col || val) {
     if (capacity < P.nnz()) return ALFD_E_INVALID;
@@ -9916,6 +10053,113 @@ int alfd_host_permute_csr(int64_t nrows, const int64_t *rp, const int32_t *col, 
   return ALFD_OK;
 }
 
+int alfd_host_check_numbering(int64_t n, const int64_t *new_to_old, int64_t *old_to_new) {
+  if (n < 0 || (n > 0 && !new_to_old)) return ALFD_E_INVALID;
+  std::vector<bool> seen((size_t)n, false);
+  for (int64_t k = 0; k < n; ++k) {
+    const int64_t o = new_to_old[k];
+    if (o < 0 || o >= n || seen[(size_t)o]) return ALFD_E_INVALID;
+    seen[(size_t)o] = true;
+  }
+  if (old_to_new)
+    for (int64_t k = 0; k < n; ++k) old_to_new[new_to_old[k]] = k;
+  return ALFD_OK;
+}
+
+static void numbering_release(alfd_ctx *ctx) {
+  alfd_ctx::Numbering &N = ctx->num;
+  if (N.perm) hipFree(N.perm);
+  if (N.inv) hipFree(N.inv);
+  if (N.stage) hipFree(N.stage);
+  N = alfd_ctx::Numbering();
+}
+
+int alfd_set_numbering(alfd_ctx_t ctx, int64_t n, const int64_t *new_to_old) {
+  CHECK_CTX();
+  const std::string fn = "alfd_set_numbering: ";
+  if (n < 0 || (n > 0 && !new_to_old)) return ctx->err = fn + "bad arguments", ALFD_E_INVALID;
+  if (n > 2147483000LL) return ctx->err = fn + "more than 2^31 rows", ALFD_E_INVALID;
+  if (ctx->nranks > 1) return ctx->err = fn + "not available on a partitioned context", ALFD_E_UNSUPPORTED;
+  // what was taken in under the numbering in force (or under none) would meet vectors translated by the new one
+  const int slots[5] = {ALFD_A, ALFD_BT, ALFD_B, ALFD_CT, ALFD_C};
+  const char *names[5] = {"A", "BT", "B", "CT", "C"};
+  for (int i = 0; i < 5; ++i) {
+    if (ctx->mat[slots[i]].present)
+      return ctx->err = fn + "slot " + names[i] + " is already uploaded (the numbering must precede it)", ALFD_E_INVALID;
+    if (slots[i] != ALFD_B && slots[i] != ALFD_C && !ctx->rb_ptr[slots[i]].empty())
+      return ctx->err = fn + "a row-block hint for " + names[i] + " is already set", ALFD_E_INVALID;
+  }
+  if (!ctx->hier[0].P[0].rp.empty()) return ctx->err = fn + "a level-0 prolongator of block 0 is already set", ALFD_E_INVALID;
+  if (!ctx->hier[0].agg[0].empty()) return ctx->err = fn + "level-0 aggregates are already set", ALFD_E_INVALID;
+  if (n == 0) {
+    HIPC(hipStreamSynchronize(ctx->stream));
+    numbering_release(ctx);
+    return ALFD_OK;
+  }
+  std::vector<int64_t> o2n((size_t)n);
+  if (alfd_host_check_numbering(n, new_to_old, o2n.data()) != ALFD_OK)
+    return ctx->err = fn + "new_to_old is not a permutation of [0, n) (entry out of range or repeated)", ALFD_E_INVALID;
+  HIPC(hipStreamSynchronize(ctx->stream));
+  numbering_release(ctx);
+  alfd_ctx::Numbering &N = ctx->num;
+  const int64_t npad = pad_chunk(n);
+  std::vector<int32_t> h((size_t)npad, 0);
+  int32_t **dst[2] = {&N.perm, &N.inv};
+  const int64_t *src[2] = {new_to_old, o2n.data()};
+  for (int a = 0; a < 2; ++a) {
+    for (int64_t k = 0; k < n; ++k) h[(size_t)k] = (int32_t)src[a][k];
+    if (hipMalloc((void **)dst[a], npad * sizeof(int32_t)) != hipSuccess ||
+        hipMemcpy(*dst[a], h.data(), npad * sizeof(int32_t), hipMemcpyHostToDevice) != hipSuccess) {
+      numbering_release(ctx);
+      return ctx->err = fn + "device allocation failed", ALFD_E_HIP;
+    }
+  }
+  if (hipMalloc((void **)&N.stage, npad * sizeof(double)) != hipSuccess) {
+    numbering_release(ctx);
+    return ctx->err = fn + "device allocation failed", ALFD_E_HIP;
+  }
+  N.n2o.assign(new_to_old, new_to_old + n);
+  N.o2n.swap(o2n);
+  return ALFD_OK;
+}
+
+int alfd_set_numbering_from_points(alfd_ctx_t ctx, int64_t n, int32_t dim, const double *points, const int32_t *brick) {
+  CHECK_CTX();
+  const std::string fn = "alfd_set_numbering_from_points: ";
+  if (n < 1 || dim < 1 || dim > 3 || !points) return ctx->err = fn + "bad arguments", ALFD_E_INVALID;
+  for (int64_t i = 0; i < n * dim; ++i)
+    if (!std::isfinite(points[i])) return ctx->err = fn + "non-finite coordinate", ALFD_E_INVALID;
+  static const int32_t default_brick[3] = {16, 4, 1};
+  const int32_t *bk = brick ? brick : default_brick;
+  for (int d = 0; d < dim; ++d)
+    if (bk[d] < 1) return ctx->err = fn + "brick sizes must be positive", ALFD_E_INVALID;
+  std::vector<int64_t> n2o((size_t)n), ptr((size_t)n + 1);
+  std::vector<double> sorted((size_t)n * dim);
+  std::vector<int32_t> rows((size_t)n);
+  RC(alfd_host_numbering_from_points(n, dim, points, n2o.data()));
+  for (int64_t k = 0; k < n; ++k)
+    for (int d = 0; d < dim; ++d) sorted[(size_t)k * dim + d] = points[(size_t)n2o[k] * dim + d];
+  int64_t nb = 0;
+  if (alfd_host_brick_blocks_from_points(n, dim, sorted.data(), bk, 250, &nb, ptr.data(), rows.data()) != ALFD_OK)
+    return ctx->err = fn + "alfd_host_brick_blocks_from_points refused the points", ALFD_E_INVALID;
+  RC(alfd_set_numbering(ctx, n, n2o.data()));
+  // the blocks come from the sorted points: they are in the new numbering already
+  ctx->rb_ptr[ALFD_A].assign(ptr.begin(), ptr.begin() + nb + 1);
+  ctx->rb_rows[ALFD_A].assign(rows.begin(), rows.end());
+  ctx->needs_full = "a prolongator, aggregates or a row-block hint was set";
+  return ALFD_OK;
+}
+
+int alfd_get_numbering(alfd_ctx_t ctx, int64_t *new_to_old, int64_t capacity, int64_t *n) {
+  if (!ctx) return ALFD_E_INVALID;
+  if (n) *n = ctx->num.n();
+  if (new_to_old) {
+    if (capacity < ctx->num.n()) return ALFD_E_INVALID;
+    std::copy(ctx->num.n2o.begin(), ctx->num.n2o.end(), new_to_old);
+  }
+  return ALFD_OK;
+}
+
 int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_bytes) {
   CHECK_CTX();
   size_t f = 0, t = 0;
@@ -10016,6 +10260,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
     ctx->spec_host_stepped = value != 0;
     return ALFD_OK;
   }
+  if (std::strcmp(name, "numbering_unpack_scatter") == 0) {   // 1: block 0 leaves through unpack_blocks_perm_scatter_kernel (same bits)
+    if (value != 0 && value != 1) return ctx->err = "numbering_unpack_scatter: 0 or 1", ALFD_E_INVALID;
+    ctx->num_unpack_scatter = value;
+    return ALFD_OK;
+  }
   return ctx->err = std::string("unknown tunable ") + name, ALFD_E_INVALID;
 }
 
@@ -10078,8 +10327,16 @@ int alfd_set_row_blocks(alfd_ctx_t ctx, int slot, int64_t n_blocks, const int64_
   for (int64_t b = 0; b < n_blocks; ++b)
     if (block_ptr[b + 1] < block_ptr[b]) return ctx->err = "alfd_set_row_blocks: block_ptr must be monotone", ALFD_E_INVALID;
   if (block_ptr[n_blocks] > 2147483000LL) return ctx->err = "alfd_set_row_blocks: more than 2^31 rows", ALFD_E_INVALID;
+  // alfd_set_numbering: the row ids of A / BT / CT are block-0 unknowns in the caller's numbering; a block keeps its order
+  const bool renum = ctx->num.on() && (slot == ALFD_A || slot == ALFD_BT || slot == ALFD_CT);
+  if (renum)
+    for (int64_t i = 0; i < block_ptr[n_blocks]; ++i)
+      if (rows[i] < 0 || rows[i] >= ctx->num.n())
+        return ctx->err = "alfd_set_row_blocks: row id outside the numbering (alfd_set_numbering)", ALFD_E_INVALID;
   ctx->rb_ptr[slot].assign(block_ptr, block_ptr + n_blocks + 1);
   ctx->rb_rows[slot].assign(rows, rows + block_ptr[n_blocks]);
+  if (renum)
+    for (int32_t &r : ctx->rb_rows[slot]) r = (int32_t)ctx->num.o2n[r];
   return ALFD_OK;
 }
 

@@ -2857,6 +2857,123 @@ __global__ __launch_bounds__(kBlock) void unpack_blocks_kernel(BlockTable tab, c
   }
 }
 
+// ---- the same two moves under a block-0 numbering (alfd_set_numbering): internal element k of block 0 is the caller's
+// element perm[k].  perm is int32 (block 0 has fewer than 2^31 rows), a bijection of [0, n[0]) checked on the host, and
+// its device copy is padded to whole chunks, so the 8-byte index load of a pair never leaves the array; the indices past
+// n[0] are not used.  Same chunk and thread map on the internal side as above (16-byte accesses, the whole chunk
+// written, zero padding); the chunks of block 0 are those below off[1] (off[0] == 0), the other blocks take the straight
+// path.  A thread issues the index loads of its 16 elements before the first gather / scatter, so the 16 dependent
+// accesses are in flight together: on the caller side the launch is bound by the latency of a round trip.
+__device__ __forceinline__ void perm_pairs(const int32_t *__restrict__ q, int2 (&j)[8]) {
+#pragma unroll
+  for (int e = 0; e < 8; ++e) j[e] = *reinterpret_cast<const int2 *>(q + e * 512 + 2 * (int)threadIdx.x);
+}
+
+__global__ __launch_bounds__(kBlock) void pack_blocks_perm_kernel(BlockTable tab, const int32_t *__restrict__ perm,
+                                                                  double *__restrict__ dst, int64_t nchunks) {
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t base = c * kChunk;
+    double *p;
+    int64_t m;
+    block_of_chunk(tab, base, p, m);
+    double2 v[8];
+    if (base < tab.off[1]) {   // block 0: gather through the numbering
+      const double *__restrict__ src = tab.p[0];
+      int2 j[8];
+      perm_pairs(perm + base, j);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i = e * 512 + 2 * (int)threadIdx.x;
+        v[e].x = i < m ? src[j[e].x] : 0.0;
+        v[e].y = i + 1 < m ? src[j[e].y] : 0.0;
+      }
+    } else {
+      const double *__restrict__ src = p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i = e * 512 + 2 * (int)threadIdx.x;
+        v[e].x = i < m ? src[i] : 0.0;
+        v[e].y = i + 1 < m ? src[i + 1] : 0.0;
+      }
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      *reinterpret_cast<double2 *>(dst + base + e * 512 + 2 * (int)threadIdx.x) = v[e];
+  }
+}
+
+// Scatter form of the unpack (tunable "numbering_unpack_scatter"; kept for the A/B measurement of profiles/numbering/,
+// where it is the slower one): coalesced 16-byte reads of the internal vector, 8-byte writes at perm[k].  perm is a
+// bijection, so no two lanes write the same element.
+__global__ __launch_bounds__(kBlock) void unpack_blocks_perm_scatter_kernel(BlockTable tab, const int32_t *__restrict__ perm,
+                                                                    const double *__restrict__ src, int64_t nchunks) {
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t base = c * kChunk;
+    double *p;
+    int64_t m;
+    block_of_chunk(tab, base, p, m);
+    const bool first = base < tab.off[1];
+    int2 j[8];
+    if (first) perm_pairs(perm + base, j);
+    double2 v[8];
+#pragma unroll
+    for (int e = 0; e < 8; ++e)
+      v[e] = *reinterpret_cast<const double2 *>(src + base + e * 512 + 2 * (int)threadIdx.x);
+    if (first) {
+      double *__restrict__ dst = tab.p[0];
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i = e * 512 + 2 * (int)threadIdx.x;
+        if (i < m) dst[j[e].x] = v[e].x;
+        if (i + 1 < m) dst[j[e].y] = v[e].y;
+      }
+    } else {
+      double *__restrict__ dst = p;
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i = e * 512 + 2 * (int)threadIdx.x;
+        if (i < m) dst[i] = v[e].x;
+        if (i + 1 < m) dst[i + 1] = v[e].y;
+      }
+    }
+  }
+}
+
+// The unpack that runs by default, in gather form: a chunk of block 0 is a chunk of the CALLER's index space, element
+// i <- src[inv[i]] with inv the inverse numbering; coalesced 8-byte writes, scattered 8-byte reads.  The same bits as the
+// scatter form, since both copy every element once; measured 0.35 against 0.38 ms per solve call at 6.4 M rows.
+__global__ __launch_bounds__(kBlock) void unpack_blocks_perm_kernel(BlockTable tab, const int32_t *__restrict__ inv,
+                                                                    const double *__restrict__ src, int64_t nchunks) {
+  for (int64_t c = blockIdx.x; c < nchunks; c += gridDim.x) {
+    const int64_t base = c * kChunk;
+    double *p;
+    int64_t m;
+    block_of_chunk(tab, base, p, m);
+    double *__restrict__ dst = p;
+    double2 v[8];
+    if (base < tab.off[1]) {
+      int2 j[8];
+      perm_pairs(inv + base, j);
+#pragma unroll
+      for (int e = 0; e < 8; ++e) {
+        const int i = e * 512 + 2 * (int)threadIdx.x;
+        v[e].x = i < m ? src[j[e].x] : 0.0;
+        v[e].y = i + 1 < m ? src[j[e].y] : 0.0;
+      }
+    } else {
+#pragma unroll
+      for (int e = 0; e < 8; ++e)
+        v[e] = *reinterpret_cast<const double2 *>(src + base + e * 512 + 2 * (int)threadIdx.x);
+    }
+#pragma unroll
+    for (int e = 0; e < 8; ++e) {
+      const int i = e * 512 + 2 * (int)threadIdx.x;
+      if (i < m) dst[i] = v[e].x;
+      if (i + 1 < m) dst[i + 1] = v[e].y;
+    }
+  }
+}
+
 // --------------------------------------------------------------------------
 // Side rows of a long-row batch-major operator ("batch_major_side_rows"): the few rows beyond kVsMaxLen entries that
 // the planner keeps out of the row blocks, in a compact CSR of their own (rows[i]: global row of list entry i, longest

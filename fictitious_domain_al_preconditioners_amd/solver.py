@@ -51,6 +51,7 @@ ABI_SYMBOLS = [
     "alfd_set_preconditioner_values", "alfd_get_preconditioner_values", "alfd_spmv_preconditioner",
     "alfd_bench_spmv_preconditioner",
     "alfd_spmv_tail_step", "alfd_get_fused_tail_launches",
+    "alfd_host_check_numbering", "alfd_set_numbering", "alfd_set_numbering_from_points", "alfd_get_numbering",
 ]
 
 
@@ -188,6 +189,11 @@ def load_library():
         "alfd_get_preconditioner_values": (C.c_int, [vp, C.POINTER(_abi.PrecValuesInfo)]),
         "alfd_spmv_preconditioner": (C.c_int, [vp, vp, vp, C.c_int, dbl]),
         "alfd_bench_spmv_preconditioner": (C.c_int, [vp, i32, C.POINTER(dbl), C.POINTER(dbl)]),
+        # numbering of block 0: declared once, the caller keeps its own numbering
+        "alfd_host_check_numbering": (C.c_int, [i64, vp, vp]),
+        "alfd_set_numbering": (C.c_int, [vp, i64, vp]),
+        "alfd_set_numbering_from_points": (C.c_int, [vp, i64, i32, vp, vp]),
+        "alfd_get_numbering": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -268,6 +274,37 @@ class Context:
     def set_partition(self, offsets):
         arrs = [np.ascontiguousarray(o, np.int64) for o in offsets]
         self._ck(self._lib.alfd_set_partition(self._h, len(arrs), _blocks(arrs)))
+
+    # -- numbering of block 0 (alfd_set_numbering): before the uploads; operators, level-0 transfers, row blocks and
+    # every block vector are then taken and returned in the caller's numbering
+    def set_numbering(self, new_to_old):
+        """Internal index k of block 0 is the caller's index new_to_old[k] (alfd_set_numbering); None or an empty
+        array clears it."""
+        p = np.ascontiguousarray([] if new_to_old is None else new_to_old, np.int64)
+        if p.ndim != 1:
+            raise ValueError("set_numbering: a 1-D permutation is required")
+        self._ck(self._lib.alfd_set_numbering(self._h, p.size, p.ctypes.data if p.size else None))
+
+    def set_numbering_from_points(self, points, brick=(16, 4, 1)):
+        """Numbering and brick row blocks of A from one support point per block-0 unknown
+        (alfd_set_numbering_from_points)."""
+        pts = np.ascontiguousarray(points, np.float64)
+        if pts.ndim != 2:
+            raise ValueError("set_numbering_from_points: points must be [n][dim]")
+        b = np.ones(3, np.int32)
+        b[:len(brick)] = brick
+        self._ck(self._lib.alfd_set_numbering_from_points(self._h, pts.shape[0], pts.shape[1], pts.ctypes.data,
+                                                          b.ctypes.data))
+
+    def numbering(self):
+        """new_to_old of the numbering in force (alfd_get_numbering), or None."""
+        n = C.c_int64(0)
+        self._ck(self._lib.alfd_get_numbering(self._h, None, 0, C.byref(n)))
+        if n.value == 0:
+            return None
+        out = np.empty(n.value, np.int64)
+        self._ck(self._lib.alfd_get_numbering(self._h, out.ctypes.data, out.size, C.byref(n)))
+        return out
 
     # -- upload
     def set_matrix(self, slot, m):
@@ -1134,6 +1171,20 @@ def numbering_from_points(points):
     return out
 
 
+def check_numbering(new_to_old):
+    """old_to_new of a permutation new_to_old of [0, n) (alfd_host_check_numbering); AlfdError (E_INVALID) when an entry
+    is out of range or repeated."""
+    p = np.ascontiguousarray(new_to_old, np.int64)
+    if p.ndim != 1:
+        raise ValueError("check_numbering: a 1-D permutation is required")
+    inv = np.empty(p.size, np.int64)
+    rc = load_library().alfd_host_check_numbering(p.size, p.ctypes.data if p.size else None,
+                                                  inv.ctypes.data if p.size else None)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_check_numbering: not a permutation of [0, n)")
+    return inv
+
+
 def brick_blocks_from_points(points, brick=(16, 4, 1), max_rows=250):
     """(block_ptr, rows) for Context.set_row_blocks: mesh bricks found from support points alone
     (alfd_host_brick_blocks_from_points)."""
@@ -1219,7 +1270,8 @@ def host_stream_plan(m, row_block=96, blocks=None, side_rows=False):
     return {k: getattr(info, k) for k, _ in info._fields_}
 
 
-def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_blocks=None, immersed_levels=None) -> Context:
+def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_blocks=None, immersed_levels=None,
+                   numbering=None) -> Context:
     """Upload a problems.SyntheticProblem (whole, or this rank's rows) with the
     reference's diagonal choices: W^-1 = 1/M_ii^2 (stokes...:976-978), lumped
     pressure mass (stokes...:946-954).  aggregates: [(agg, n_coarse), ...] for
@@ -1228,7 +1280,15 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
     thread while the operators are uploaded).  row_blocks: (block_ptr, rows)
     for the SpMV on A (Context.set_row_blocks, e.g. problems.brick_row_blocks).  immersed_levels:
     [(Csr P, n_coarse), ...] of the immersed block of an elliptic-interface problem (block 1:
-    problems.immersed_tensor_prolongators); None leaves whatever the context holds for that block."""
+    problems.immersed_tensor_prolongators); None leaves whatever the context holds for that block.  numbering: a
+    new_to_old permutation of block 0 (Context.set_numbering) or an [n][dim] array of support points
+    (Context.set_numbering_from_points), declared before the uploads: pb, aggregates and row_blocks stay in the problem's
+    own numbering."""
+    if numbering is not None:
+        if np.ndim(numbering) == 2:
+            ctx.set_numbering_from_points(numbering)
+        else:
+            ctx.set_numbering(numbering)
     if row_blocks is not None:
         ctx.set_row_blocks(_abi.A, *row_blocks)
     for level, entry in enumerate(immersed_levels or []):
@@ -1331,8 +1391,8 @@ def update_coupling(ctx: Context, Ct, inv_w=None, M=None, C=None, gamma=None) ->
 
 
 def context_from_problem(pb, cfg: _abi.Config, device_id=0, aggregates=None, row_blocks=None,
-                         immersed_levels=None) -> Context:
-    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks, immersed_levels)
+                         immersed_levels=None, numbering=None) -> Context:
+    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks, immersed_levels, numbering)
 
 
 # ---------------------------------------------------------------------------

@@ -1039,9 +1039,8 @@ int alfd_host_row_blocks_from_points(int64_t nrows, int32_t dim, const double *p
  * (DoFTools::map_dofs_to_support_points):
  *   alfd_host_numbering_from_points: new_to_old[nrows] = the unknowns in lexicographic order of their points (last
  *     coordinate slowest), unknowns with the same point -- the components of a node -- kept together in their order.
- *     The front end (include/alfd/dealii_adapter.hpp, solver.py) permutes the operators and vectors with it BEFORE the
- *     upload and the solution back after the download: results live in the permuted numbering, the library itself
- *     never sees the caller's one.
+ *     alfd_set_numbering (below) takes it: the library then permutes the operators at upload and the vectors on the
+ *     device, and the caller keeps its own numbering.
  *   alfd_host_brick_blocks_from_points: row blocks for alfd_set_row_blocks = bricks of brick[0] x brick[1] x brick[2]
  *     grid nodes, a node's grid index along an axis being the rank of its coordinate among the distinct coordinates
  *     of that axis (exact on tensor grids, consistent on locally refined ones); blocks above max_rows rows are split.
@@ -1054,6 +1053,47 @@ int alfd_host_brick_blocks_from_points(int64_t nrows, int32_t dim, const double 
 int alfd_host_permute_csr(int64_t nrows, const int64_t *row_ptr, const int32_t *col, const double *val,
                           const int64_t *row_new_to_old, const int64_t *col_old_to_new, int64_t *out_row_ptr,
                           int32_t *out_col, double *out_val);
+
+/* ------------------------------------------------ numbering of block 0 (additive within ABI 12)
+ * A caller whose block-0 unknowns (velocity / background space) are not numbered the way the SpMV formats like declares
+ * a permutation ONCE and keeps its own numbering for everything it hands in or gets back; the library permutes the
+ * operators at upload and the vectors on the device, inside the pack / unpack launch that moves the caller's blocks
+ * into the padded internal vector.  Internal index k of block 0 is the caller's index new_to_old[k].
+ *
+ *   alfd_host_check_numbering: host only.  ALFD_E_INVALID unless new_to_old is a bijection of [0, n) (an entry out of
+ *     range or repeated, a null pointer with n > 0, n < 0); old_to_new (may be NULL) receives the inverse.
+ *   alfd_set_numbering: fixes the permutation (n == 0 clears it).  It must precede every upload it affects: with slot
+ *     A, BT, B, CT or C, a level-0 prolongator or aggregates of block 0, or a row-block hint for A / BT / CT present it
+ *     returns ALFD_E_INVALID and alfd_last_error names what is in the way -- clearing included.  ALFD_E_UNSUPPORTED on a
+ *     partitioned context (nranks > 1), and alfd_comm_init* / alfd_set_partition refuse the same way after it.  n must
+ *     be the size of block 0 at every later use: a mismatch at an upload, at alfd_setup or at a vector call is
+ *     ALFD_E_INVALID.  n < 2^31 (columns are int32; the device copy is 32-bit).
+ *   alfd_set_numbering_from_points: from one support point per block-0 unknown ([n][dim], dim 1..3; a non-finite
+ *     coordinate is ALFD_E_INVALID): the numbering of alfd_host_numbering_from_points, and as the row-block hint of A
+ *     the blocks alfd_host_brick_blocks_from_points(.., brick, 250, ..) forms of the points sorted by it (brick NULL:
+ *     16, 4, 1).
+ *   alfd_get_numbering: *n = entries (0: none); new_to_old != NULL: the permutation, ALFD_E_INVALID when capacity < *n.
+ *
+ * THE RULE: with a numbering, whatever crosses the calls below is in the CALLER's numbering.
+ *   alfd_set_matrix: rows of A, BT, CT are taken in the new order, columns of A, B, C renamed and a row's entries
+ *     sorted by new column (the arithmetic of alfd_host_permute_csr); the derived transposes follow from the permuted
+ *     operand; every later re-upload (the new CT of alfd_setup_coupling) is permuted the same way.
+ *   alfd_set_prolongator / alfd_set_prolongator_block(block 0) at level 0: rows; alfd_set_aggregates at level 0: agg[]
+ *     and weight[].  alfd_get_prolongator[_block] / alfd_get_aggregates[_block] (block 0, level 0) answer in the
+ *     caller's numbering, whoever made the level.
+ *   alfd_set_row_blocks for A, BT, CT: row ids are mapped; the order inside a block stays.
+ *   Block vectors -- alfd_solve, alfd_precond_apply, alfd_system_apply, alfd_augment_rhs, alfd_upload_rhs,
+ *     alfd_download_solution, alfd_constraint_residual and the six *_device calls: block 0 is translated on the way in
+ *     and on the way out (the *_device calls keep their aliasing rules: all inputs are packed before any output).
+ * NOT translated -- these speak the internal numbering, alfd_get_numbering is the key: the single-vector primitives and
+ * diagnostics (alfd_spmv*, alfd_spmv_tail_step, alfd_inner_prec_apply, alfd_spmv_preconditioner, alfd_bench_*), the
+ * strength-graph getters, and everything the alfd_build_* builders produce below level 0.
+ * Without a numbering every call behaves as before and launches the same kernels. */
+int alfd_host_check_numbering(int64_t n, const int64_t *new_to_old, int64_t *old_to_new /* may be NULL */);
+int alfd_set_numbering(alfd_ctx_t ctx, int64_t n, const int64_t *new_to_old);
+int alfd_set_numbering_from_points(alfd_ctx_t ctx, int64_t n, int32_t dim, const double *points,
+                                   const int32_t *brick /* [3], NULL: 16,4,1 */);
+int alfd_get_numbering(alfd_ctx_t ctx, int64_t *new_to_old, int64_t capacity, int64_t *n);
 
 /* Free / total bytes of the context's device (hipMemGetInfo): leak checks, capacity planning. */
 int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_bytes);
@@ -1091,6 +1131,10 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *   "spectrum_host_stepped" (0/1, default 0): alfd_estimate_spectrum steps its CG on the host (one synchronisation
  *                  per iteration, through the inner CG's own loop) instead of on the device.  Same bits either way.
  *                  "spectrum_group" (1..1000, default 16): device-stepped iterations enqueued per state read.
+ *   "numbering_unpack_scatter" (0/1, default 0): under alfd_set_numbering block 0 leaves the internal vector through
+ *                  the scatter form of the unpack kernel (coalesced reads, writes at new_to_old[k]) instead of the
+ *                  gather form (reads at old_to_new[i], coalesced writes).  Same bits; the gather form measured
+ *                  faster (profiles/numbering/).
  *   "ml_fuse"      0..3 (default 2; environment ALFD_ML_FUSE, read at alfd_create): how many launches one application
  *                  of a factored operator A + gamma Ct invW C takes inside ALFD_PREC_MULTILEVEL.  0: separate
  *                  launches.  1: the product y += gamma Ct t that ends it and the element-wise kernel after it
