@@ -111,10 +111,10 @@ class MatrixInfo(C.Structure):
 
 # enum alfd_spmv_family (alfd_get_last_spmv_launch)
 SPMV_PLAIN, SPMV_SPARSE_ROWS, SPMV_STREAM, SPMV_WINDOW, SPMV_WINDOW_VI, SPMV_WINDOW_VIB, SPMV_WINDOW_GROUP, \
-    SPMV_BATCH_MAJOR, SPMV_BATCH_MAJOR_SHORT, SPMV_PLAIN_F32, SPMV_STREAM_F32, SPMV_WINDOW_F32 = range(12)
-SPMV_NFAMILIES = 12
+    SPMV_BATCH_MAJOR, SPMV_BATCH_MAJOR_SHORT, SPMV_PLAIN_F32, SPMV_STREAM_F32, SPMV_WINDOW_F32, SPMV_ROW_LANE = range(13)
+SPMV_NFAMILIES = 13
 SPMV_FAMILY_NAMES = ("plain", "sparse_rows", "stream", "window", "window_vi", "window_vib", "window_group",
-                     "batch_major", "batch_major_short", "plain_f32", "stream_f32", "window_f32")
+                     "batch_major", "batch_major_short", "plain_f32", "stream_f32", "window_f32", "row_lane")
 
 
 class SpmvLaunch(C.Structure):

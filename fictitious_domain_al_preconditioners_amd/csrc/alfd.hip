@@ -71,6 +71,7 @@ struct DevCsr {
   bool rep = false;  // replicated on every rank (coarse multigrid levels): never exchanges a halo
   bool derived = false;  // C / B built by the library as the transpose of an uploaded CT / BT
   int L = 64;
+  int64_t longest = -1;                   // entries of the longest row, counted at upload (-1: not counted)
   int32_t n_local_cols = 0;               // columns < n_local_cols read x, others the halo
   int64_t *rp = nullptr;
   int32_t *col = nullptr;
@@ -352,6 +353,7 @@ struct alfd_ctx {
   bool dots_replicated = false;               // reductions over REPLICATED vectors (every rank holds the whole vector): no exchange
   int64_t ml_rep_threshold = 300000;          // replicate levels with at most this many unknowns (ALFD_ML_REPLICATE)
   int ml_fuse = 2;                            // fused smoother steps: aug_tail_kernel, pair launches ("ml_fuse", ALFD_ML_FUSE)
+  int short_rows_per_thread = 1;              // "short_rows_per_thread": 4- and 8-lane operators with rows of at most 2 L entries run on spmv_rowlane_kernel (0: spmv_kernel<L>)
   int ml_tail_in_spmv = 1;                    // "ml_tail_in_spmv", ALFD_ML_TAIL_IN_SPMV: the element-wise tails at the block end of the batch-major A launch
   int ml_tail_side_rows = 0;                  // "ml_tail_side_rows" = 1: an operator with side rows runs that form too, its side rows' tails in spmv_side_rows_tail_kernel
   int64_t fused_tail_launches = 0;            // launches of that form since alfd_create (alfd_get_fused_tail_launches)
@@ -720,6 +722,24 @@ static void launch_spmv(alfd_ctx *ctx, const DevCsr &m, const double *x, double 
   with_lanes(m.L, [&](auto l) { launch_spmv_L<decltype(l)::value>(ctx, m, x, y, epi, alpha, d, y2); });
 }
 
+// ---- one thread per row (spmv_rowlane_kernel): taken exactly where spmv_launch_local would launch
+// spmv_kernel<L, EPI, false> with L 4 or 8 and EPI 0 or 1, when no row has more than 2 L entries.  Same bits.
+static inline bool rowlane_form(const alfd_ctx *ctx, const DevCsr &m, int epi) {
+  return ctx->short_rows_per_thread && !m.sparse && (m.L == 4 || m.L == 8) && (epi == 0 || epi == 1) && m.longest >= 0 &&
+         m.longest <= 2 * m.L && m.n_list <= (int64_t)INT32_MAX * kBlock;
+}
+static void launch_rowlane(alfd_ctx *ctx, const DevCsr &m, const double *x, double *y, int epi, double alpha) {
+  const int64_t grid = (m.n_list + kBlock - 1) / kBlock;   // one row per thread
+  with_const<4, 8>(m.L, [&](auto l) {
+    with_flag(epi, [&](auto e) {
+      constexpr int L = decltype(l)::value, EPI = decltype(e)::value;
+      note_spmv(ctx, ALFD_SPMV_ROW_LANE, L, 0, 0, false, EPI, 0, grid, 0);
+      hipLaunchKernelGGL((spmv_rowlane_kernel<L, EPI>), dim3((unsigned)grid), dim3(kBlock), 0, ctx->stream, m.n_list, m.rp, m.col,
+                         m.val, x, m.halo, m.n_local_cols, y, alpha);
+    });
+  });
+}
+
 // workgroups of the stream kernel: 4 waves, a batch of R rows per wave and pass
 static inline int stream_grid(const alfd_ctx *ctx, int64_t nrows, int R) {
   const int64_t nbatches = (nrows + R - 1) / R;
@@ -1014,7 +1034,10 @@ static int spmv_launch_local(alfd_ctx *ctx, DevCsr &m, const double *x, double *
       return ALFD_OK;
     }
   }
-  launch_spmv(ctx, m, x, y, epi, alpha, d, y2);
+  if (rowlane_form(ctx, m, epi))
+    launch_rowlane(ctx, m, x, y, epi, alpha);
+  else
+    launch_spmv(ctx, m, x, y, epi, alpha, d, y2);
   HIPC(hipGetLastError());
   return ALFD_OK;
 }
@@ -3638,7 +3661,11 @@ static int upload_matrix(alfd_ctx *ctx, int slot, int64_t nrows, int64_t ncols, 
   m.ncols = ncols;
   m.nnz = rp[nrows];
   int64_t nonempty = 0;
-  for (int64_t r = 0; r < nrows; ++r) nonempty += rp[r + 1] > rp[r];
+  m.longest = 0;
+  for (int64_t r = 0; r < nrows; ++r) {
+    nonempty += rp[r + 1] > rp[r];
+    m.longest = std::max(m.longest, rp[r + 1] - rp[r]);
+  }
   m.sparse = nonempty * 2 < nrows;
   if (ctx->nranks > 1) {
     // lanes-per-row follows the GLOBAL matrix (so every rank, and the oracle, use one L)
@@ -4960,6 +4987,8 @@ static int upload_plain(alfd_ctx *ctx, DevCsr &m, const HostCsr &h, int L) {
   m.n_local_cols = (int32_t)h.ncols;
   m.nnz = h.nnz();
   m.L = L;
+  m.longest = 0;
+  for (int64_t r = 0; r < h.nrows; ++r) m.longest = std::max(m.longest, h.rp[r + 1] - h.rp[r]);
   m.tag = 1;
   RC(csr_alloc(ctx, m, &m.rp, h.nrows + 1));
   RC(csr_alloc(ctx, m, &m.col, m.nnz));
@@ -10220,6 +10249,11 @@ int alfd_set_tunable(alfd_ctx_t ctx, const char *name, int value) {
   }
   if (std::strcmp(name, "ml_fuse") == 0) {   // 0: separate launches; 1: aug_tail; 2: + pair launches; 3: + on the fine level
     ctx->ml_fuse = std::max(0, std::min(3, value));   // as ALFD_ML_FUSE: values outside 0..3 take the nearest level
+    return ALFD_OK;
+  }
+  if (std::strcmp(name, "short_rows_per_thread") == 0) {   // 0: spmv_kernel<L> for every 4- and 8-lane operator (same bits); at the next launch
+    if (value != 0 && value != 1) return ctx->err = "short_rows_per_thread: 0 or 1", ALFD_E_INVALID;
+    ctx->short_rows_per_thread = value;
     return ALFD_OK;
   }
   if (std::strcmp(name, "ml_tail_side_rows") == 0) {   // 1: "ml_tail_in_spmv" also on operators with side rows; at the next alfd_setup / alfd_setup_coupling

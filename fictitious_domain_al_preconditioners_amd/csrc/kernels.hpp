@@ -263,6 +263,68 @@ __global__ __launch_bounds__(kBlock) void spmv_kernel(int64_t nrows, const int64
 }
 
 // --------------------------------------------------------------------------
+// CSR SpMV of very short rows, ONE THREAD per row (L = 4 or 8, rows of at most 2 L entries, EPI 0 or 1): 64 rows per
+// wave where spmv_kernel<L> has 64 / L, and the 2 L (col, val) loads of a row are independent of each other, so a wave
+// keeps 64 x 2 L entries in flight instead of 64.  The arithmetic is spmv_kernel<L>'s, emulated in registers: accumulator
+// a[l] is lane l of the L-lane group (entries l, l + L in that order; a lane without entries keeps +0.0 and is added all
+// the same), the tree adds the partners l^(L/2), ..., l^1 as lane 0 of group_reduce<L> sees them.  Same bits.
+// One row per thread, no grid stride: gridDim.x * kBlock >= nrows.
+// rowlane_row is the row of the kernel below: entry(j, c, v) loads entry j < n of the row.
+template <int L, int EPI, class Entry>
+__device__ __forceinline__ void rowlane_row(int64_t r, int n, Entry entry, const double *__restrict__ x,
+                                            const double *__restrict__ x_halo, int32_t n_local,
+                                            double *__restrict__ y, double alpha) {
+  static_assert(L == 4 || L == 8, "row-per-thread SpMV: 4 or 8 emulated lanes");
+  static_assert(EPI == 0 || EPI == 1, "row-per-thread SpMV: epilogues 0 and 1");
+  double y0 = 0.0;
+  if (EPI == 1) y0 = y[r];
+  int32_t c[2 * L];
+  double v[2 * L], xv[2 * L];
+#pragma unroll
+  for (int j = 0; j < 2 * L; ++j) {
+    c[j] = 0;
+    v[j] = 0.0;
+    if (j < n) entry(j, c[j], v[j]);
+  }
+#pragma unroll
+  for (int j = 0; j < 2 * L; ++j) {
+    xv[j] = 0.0;
+    if (j < n) xv[j] = (c[j] < n_local) ? x[c[j]] : x_halo[c[j] - n_local];
+  }
+  double a[L];
+#pragma unroll
+  for (int l = 0; l < L; ++l) a[l] = 0.0;
+#pragma unroll
+  for (int j = 0; j < 2 * L; ++j)
+    if (j < n) a[j % L] = fma(v[j], xv[j], a[j % L]);   // not fma(0, 0, a): that would turn a -0.0 into +0.0
+  double s;
+  if constexpr (L == 4)
+    s = (a[0] + a[2]) + (a[1] + a[3]);
+  else
+    s = ((a[0] + a[4]) + (a[2] + a[6])) + ((a[1] + a[5]) + (a[3] + a[7]));
+  if (EPI == 0)
+    y[r] = s;
+  else
+    y[r] = fma(alpha, s, y0);
+}
+
+// ... on the CSR arrays as uploaded: neighbouring threads read neighbouring CSR segments
+template <int L, int EPI>
+__global__ __launch_bounds__(kBlock) void spmv_rowlane_kernel(int64_t nrows, const int64_t *__restrict__ rp,
+                                                              const int32_t *__restrict__ col,
+                                                              const double *__restrict__ val,
+                                                              const double *__restrict__ x,
+                                                              const double *__restrict__ x_halo, int32_t n_local,
+                                                              double *__restrict__ y, double alpha) {
+  const int64_t r = (int64_t)blockIdx.x * kBlock + threadIdx.x;
+  if (r >= nrows) return;
+  const int64_t k0 = rp[r];
+  const int n = (int)(rp[r + 1] - k0);   // <= 2 L (the launcher's condition)
+  rowlane_row<L, EPI>(r, n, [&](int j, int32_t &c, double &v) { c = col[k0 + j], v = val[k0 + j]; }, x, x_halo, n_local, y,
+                      alpha);
+}
+
+// --------------------------------------------------------------------------
 // Pair launch: t = d .* (C x) of a factored operator A + gamma Ct W^-1 C as extra workgroups of the grid that computes
 // y = A x (PAIR instantiations of spmv_vs_kernel and spmv_stream_kernel).  Workgroups [0, nA) are the A kernel as it
 // is, with nA where it reads gridDim.x; workgroups [nA, nA + nC) run spmv_rows<L, 2, false> on the CSR arrays of C and

@@ -773,7 +773,8 @@ enum alfd_spmv_family {
   ALFD_SPMV_PLAIN_F32 = 9,          /* the single-precision copy of slot A on the three families it has */
   ALFD_SPMV_STREAM_F32 = 10,
   ALFD_SPMV_WINDOW_F32 = 11,
-  ALFD_SPMV_NFAMILIES = 12
+  ALFD_SPMV_ROW_LANE = 12,          /* spmv_rowlane_kernel<L>: one thread per row, rows of at most 2 L entries, L 4 or 8 */
+  ALFD_SPMV_NFAMILIES = 13
 };
 typedef struct alfd_spmv_launch {
   int32_t family;   /* enum alfd_spmv_family */
@@ -1124,6 +1125,12 @@ int alfd_get_device_memory(alfd_ctx_t ctx, int64_t *free_bytes, int64_t *total_b
  *                  (the plan is then the one of 0), when such rows hold more than 1/8 of the entries, or when one has
  *                  more than 65 535.  A side row has no block end: what "ml_tail_in_spmv" does with such an operator is
  *                  the subject of "ml_tail_side_rows" below.
+ *   "short_rows_per_thread" (0/1, default 1; other values are refused with ALFD_E_INVALID; at the next launch): 1: an
+ *                  operator with 4 or 8 lanes per row that would run on spmv_kernel<L> (no window or batch-major form,
+ *                  not the sparse-row list) and whose longest row has at most 2 L entries runs y = A x and
+ *                  y = fma(alpha, A x, y) on spmv_rowlane_kernel<L>, one thread per row (the prolongators of a tensor
+ *                  grid hierarchy); the longest row is counted at alfd_set_matrix.  0: spmv_kernel<L>.
+ *                  Same bits; alfd_get_last_spmv_launch says which ran (ALFD_SPMV_ROW_LANE).
  *   "nested_mp_host_stepped" (0/1, default 0): grad_div_in_A = 0, one rank: the nested CG on Mp inside Aug is
  *                  device-stepped (stop rule on the device, one state read per group); 1 steps it on the host (one
  *                  synchronisation per iteration), as partitioned contexts always do.  Same bits either way.
