@@ -4,7 +4,8 @@ prints both iteration counts side by side -- the one route by which parity with 
 pinned (needs a deal.II install, which this repository's pipeline does not have).
 
     python bench/reference_cmake/replay.py run/stokes_immersed_boundary.alfd [--reference-log run/stokes.log]
-                                           [--inner-prec multilevel|sa-multilevel|chebyshev] [--support-points points.npy]
+                                           [--inner-prec multilevel|sa-multilevel|gmg|chebyshev] [--support-points points.npy]
+                                           [--base-cells N]
                                            [--sa-drop-tolerance TAU] [--sa-max-row-entries K]
 
 A dump with grad_div_in_A = 0 (`Grad-div stabilization = false`) replays with the identity inner preconditioner, the
@@ -13,7 +14,10 @@ reference's, or with --inner-prec chebyshev; never multilevel.
 The inner preconditioner differs from the reference's by construction (Trilinos ML there; here the algebraic aggregation
 of alfd_build_aggregates on the dumped A, or geometric transfers when the caller supplies them; sa-multilevel builds
 ML's algorithm, smoothed aggregation, from the dumped operators with alfd_build_smoothed_aggregation;
---sa-drop-tolerance / --sa-max-row-entries truncate its prolongators as ML does, e.g. --sa-max-row-entries 4), so OUTER counts
+--sa-drop-tolerance / --sa-max-row-entries truncate its prolongators as ML does, e.g. --sa-max-row-entries 4; gmg is the
+preconditioner bench.py measures -- the geometric hierarchy, built by alfd_build_geometric_from_points from the
+--support-points and the lone-diagonal rows of the dumped A, with the interface patch and the explicit coarsest inverse
+of the bench; a locally refined mesh also needs --base-cells, its `Initial refinement` cells per axis), so OUTER counts
 are the comparable quantity: both inner solvers stop at the same absolute tolerance (parameters_stokes_3d.prm:23-24)."""
 import argparse
 import json
@@ -29,7 +33,7 @@ def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("alfd_file")
     ap.add_argument("--reference-log", help="stdout of the reference run (scrape_deallog.py)")
-    ap.add_argument("--inner-prec", choices=["multilevel", "sa-multilevel", "chebyshev"], default="multilevel")
+    ap.add_argument("--inner-prec", choices=["multilevel", "sa-multilevel", "gmg", "chebyshev"], default="multilevel")
     ap.add_argument("--inner-max", type=int, default=0, help="override the inner CG cap of the dump (0 = keep)")
     ap.add_argument("--support-points", help=".npy with one support point per row of block 0: front-end renumbering + mesh bricks")
     ap.add_argument("--block-size", type=int, default=0, help="components per node of block 0 (default: 3 for Stokes dumps, else 1)")
@@ -37,7 +41,11 @@ def main():
                     help="sa-multilevel: drop the entries of P below this fraction of their row's maximum (0 = none)")
     ap.add_argument("--sa-max-row-entries", type=int, default=0,
                     help="sa-multilevel: keep at most this many entries per row of P (0 = no cap)")
+    ap.add_argument("--base-cells", type=int, default=0,
+                    help="gmg: cells per axis of the uniform base grid (needed when the mesh is locally refined)")
     args = ap.parse_args()
+    if args.inner_prec == "gmg" and not args.support_points:
+        ap.error("--inner-prec gmg needs --support-points")
     import numpy as np
     from fictitious_domain_al_preconditioners_amd import _abi, opfile, solver
     import scrape_deallog
@@ -70,11 +78,17 @@ def main():
     for slot, d in diags.items():
         ctx.set_diag(slot, d)
     gd_off = cfg.variant in (_abi.AL_STOKES, _abi.AL_STOKES_DIAG) and not cfg.grad_div_in_A
-    if gd_off and args.inner_prec in ("multilevel", "sa-multilevel"):
+    if gd_off and args.inner_prec in ("multilevel", "sa-multilevel", "gmg"):
         # Aug = A + gamma Ct invW C + gamma_gd Bt Mp^-1 B has no multilevel preconditioner (ExcNotImplemented in the
         # reference): such dumps replay with the identity inner preconditioner of the reference, or --inner-prec chebyshev
         print("grad_div_in_A = 0: no multilevel inner preconditioner; replaying with the identity inner preconditioner")
         cfg.inner_prec = _abi.PREC_IDENTITY
+    elif args.inner_prec == "gmg" and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
+        _abi.bench_multilevel_settings(cfg, geometric=True)
+        levels, cells = ctx.build_geometric_from_points(pts[perm], base=args.base_cells or None,
+                                                        min_coarse=_abi.BENCH_MIN_COARSE, return_cells=True)
+        print(f"geometric hierarchy from the support points: lattice {cells[0].tolist()} cells, coarse grids "
+              f"{cells[1:].tolist()}, levels {[nc for _, nc in levels]}")
     elif args.inner_prec in ("multilevel", "sa-multilevel") and cfg.variant in (_abi.AL2, _abi.AL_STOKES, _abi.AL_STOKES_DIAG):
         cfg.inner_prec = _abi.PREC_MULTILEVEL
         cfg.ml_smooth_degree, cfg.ml_smooth_ratio, cfg.ml_coarse_degree = 4, 256.0, 10

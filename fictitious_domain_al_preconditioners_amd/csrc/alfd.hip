@@ -41,6 +41,7 @@
 #include "alfd/alfd.h"
 #include "kernels.hpp"
 #include "kernels_vs.hpp"
+#include "point_hierarchy.hpp"
 
 namespace alfd {
 
@@ -8644,6 +8645,171 @@ int alfd_get_prolongator_block(alfd_ctx_t ctx, int block, int level, int64_t *ro
     if (col) std::copy(P.col.begin(), P.col.end(), col);
     if (val) std::copy(P.val.begin(), P.val.end(), val);
   }
+  return ALFD_OK;
+}
+
+// ---- geometric hierarchies from support points (point_hierarchy.hpp; the rule: alfd.h)
+// the two-call protocol of the CSR results on a point_hierarchy::Csr
+static int point_csr_result(const point_hierarchy::Csr &P, int64_t *row_ptr, int32_t *col, double *val, int64_t capacity,
+                            int64_t *nnz) {
+  *nnz = P.rp.back();
+  if (row_ptr) std::copy(P.rp.begin(), P.rp.end(), row_ptr);
+  if (col || val) {
+    if (capacity < P.rp.back()) return ALFD_E_INVALID;
+    if (col) std::copy(P.col.begin(), P.col.end(), col);
+    if (val) std::copy(P.val.begin(), P.val.end(), val);
+  }
+  return ALFD_OK;
+}
+
+int alfd_host_point_lattice(int64_t n, int32_t dim, const double *points, int32_t *cells, double *lo, double *delta,
+                            int32_t *index, int32_t *complete) {
+  point_hierarchy::Lattice L;
+  if (!point_hierarchy::lattice(n, dim, points, L)) return ALFD_E_INVALID;
+  for (int d = 0; d < dim; ++d) {
+    if (cells) cells[d] = (int32_t)L.m[d];
+    if (lo) lo[d] = L.lo[d];
+    if (delta) delta[d] = L.delta[d];
+  }
+  if (index) std::copy(L.idx.begin(), L.idx.end(), index);
+  if (complete) *complete = L.complete ? 1 : 0;
+  return ALFD_OK;
+}
+
+int alfd_host_point_prolongator(int64_t n, int32_t dim, const double *points, int32_t ncomp, const int32_t *component,
+                                const uint8_t *constrained, const int32_t *base, int32_t boundary_unknowns,
+                                int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz,
+                                int64_t *n_coarse) {
+  if (!nnz || ncomp < 1) return ALFD_E_INVALID;
+  point_hierarchy::Lattice L;
+  point_hierarchy::Csr P;
+  int64_t cells[3];
+  if (!point_hierarchy::lattice(n, dim, points, L) ||
+      !point_hierarchy::point_prolongator(n, L, ncomp, component, constrained, base, boundary_unknowns != 0, P, cells))
+    return ALFD_E_INVALID;
+  if (n_coarse) *n_coarse = P.ncols;
+  return point_csr_result(P, p_row_ptr, p_col, p_val, capacity, nnz);
+}
+
+int alfd_host_grid_prolongator(int32_t dim, int32_t ncomp, const int32_t *fine_cells, const int32_t *coarse_cells,
+                               int32_t boundary_unknowns, int64_t *p_row_ptr, int32_t *p_col, double *p_val,
+                               int64_t capacity, int64_t *n_fine, int64_t *n_coarse, int64_t *nnz) {
+  if (!nnz || dim < 1 || dim > 3 || !fine_cells || !coarse_cells) return ALFD_E_INVALID;
+  const int64_t fine[3] = {fine_cells[0], dim > 1 ? fine_cells[1] : 1, dim > 2 ? fine_cells[2] : 1};
+  const int64_t coarse[3] = {coarse_cells[0], dim > 1 ? coarse_cells[1] : 1, dim > 2 ? coarse_cells[2] : 1};
+  point_hierarchy::Csr P;
+  if (!point_hierarchy::grid_prolongator(dim, ncomp, fine, coarse, boundary_unknowns != 0, P)) return ALFD_E_INVALID;
+  if (n_fine) *n_fine = P.nrows;
+  if (n_coarse) *n_coarse = P.ncols;
+  return point_csr_result(P, p_row_ptr, p_col, p_val, capacity, nnz);
+}
+
+int alfd_host_point_hierarchy_cells(int32_t dim, int32_t ncomp, const int32_t *lattice_cells, const int32_t *base,
+                                    int32_t boundary_unknowns, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
+                                    int32_t *cells_out) {
+  if (dim < 1 || dim > 3 || ncomp < 1 || ncomp > 64 || !lattice_cells || min_coarse < 1 || !levels_out) return ALFD_E_INVALID;
+  if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
+  int64_t m[3] = {0, 0, 0};
+  for (int d = 0; d < dim; ++d) {
+    if (lattice_cells[d] < 0) return ALFD_E_INVALID;
+    m[d] = lattice_cells[d];
+  }
+  std::vector<int64_t> cells;
+  if (!point_hierarchy::level_cells(dim, ncomp, m, base, boundary_unknowns != 0, min_coarse, max_levels, cells))
+    return ALFD_E_INVALID;
+  *levels_out = (int32_t)(cells.size() / dim);
+  if (cells_out)
+    for (size_t k = 0; k < cells.size(); ++k) cells_out[k] = (int32_t)cells[k];
+  return ALFD_OK;
+}
+
+int alfd_build_geometric_from_points(alfd_ctx_t ctx, int block, int64_t n, int32_t dim, const double *points,
+                                     const int32_t *component, const uint8_t *constrained, const int32_t *base,
+                                     int64_t min_coarse, int32_t max_levels, int32_t *levels_out, int32_t *cells_out) {
+  CHECK_CTX();
+  const std::string fn = "alfd_build_geometric_from_points: ";
+  if (ctx->nranks > 1) return ctx->err = fn + "not available on a partitioned context", ALFD_E_UNSUPPORTED;
+  RC(check_block(ctx, block));
+  const DevCsr &A = ctx->mat[block == 0 ? ALFD_A : ALFD_A2];
+  if (!A.present) return ctx->err = fn + (block == 0 ? "upload slot A first" : "upload slot A2 first"), ALFD_E_NOT_SETUP;
+  if (n != A.nrows) return ctx->err = fn + "n is not the row count of the block's operator", ALFD_E_INVALID;
+  if (dim < 1 || dim > 3 || !points || min_coarse < 1) return ctx->err = fn + "bad arguments", ALFD_E_INVALID;
+  if (block == 1 && constrained) return ctx->err = fn + "block 1 has no constrained unknowns", ALFD_E_INVALID;
+  if (max_levels < 1 || max_levels > ALFD_MAX_LEVELS - 1) max_levels = ALFD_MAX_LEVELS - 1;
+  const bool renum = block == 0 && ctx->num.on();
+  if (renum && n != ctx->num.n()) return ctx->err = fn + "n is not the size of the numbering (alfd_set_numbering)", ALFD_E_INVALID;
+  point_hierarchy::Lattice L;
+  if (!point_hierarchy::lattice(n, dim, points, L))
+    return ctx->err = fn + "the points are not finite or no lattice", ALFD_E_INVALID;
+  std::vector<uint8_t> lone;
+  if (block == 0 && !constrained) {   // the rows of the resident A that hold nothing but their diagonal, in the caller's numbering
+    std::vector<int32_t> fixed((size_t)n);
+    int32_t *d_fixed = nullptr;
+    double *d_diag = nullptr;
+    auto release = [&]() {
+      if (d_fixed) hipFree(d_fixed);
+      if (d_diag) hipFree(d_diag);
+    };
+    auto flags = [&]() -> int {
+      HIPC(hipMalloc((void **)&d_fixed, n * sizeof(int32_t)));
+      HIPC(hipMalloc((void **)&d_diag, n * sizeof(double)));
+      hipLaunchKernelGGL(sa_node_diag_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, ctx->stream, n, 1, (int64_t)0,
+                         A.rp, A.col, A.val, (int32_t)A.ncols, (int64_t)0, (const int32_t *)nullptr, d_diag, d_fixed);
+      HIPC(hipGetLastError());
+      HIPC(hipMemcpyAsync(fixed.data(), d_fixed, n * sizeof(int32_t), hipMemcpyDeviceToHost, ctx->stream));
+      HIPC(hipStreamSynchronize(ctx->stream));
+      return ALFD_OK;
+    };
+    if (A.sparse) {   // rows kept as a list (more than half of them empty): the host routine on a copy
+      HostCsr h;
+      std::vector<double> d;
+      RC(download_csr(ctx, A, h));
+      node_diag_host(h, 0, 1, d, fixed);
+    } else {
+      const int rc = flags();
+      release();
+      RC(rc);
+    }
+    lone.resize((size_t)n);
+    for (int64_t i = 0; i < n; ++i) lone[(size_t)i] = fixed[(size_t)(renum ? ctx->num.o2n[i] : i)] != 0;
+    constrained = lone.data();
+  }
+  std::vector<point_hierarchy::Csr> levels;
+  std::vector<int64_t> cells;
+  if (!point_hierarchy::hierarchy(n, L, 0, component, constrained, base, block == 1, min_coarse, max_levels, levels, cells))
+    return ctx->err = fn + "the unknowns per node, the components or the base grid do not fit the lattice (an incomplete "
+                           "lattice needs base)", ALFD_E_INVALID;
+  // the inputs the block had are kept aside until every level is in: a refusal below hands them back untouched
+  alfd_ctx::Hierarchy &H = ctx->hier[block];
+  struct Kept {
+    std::vector<int32_t> agg[ALFD_MAX_LEVELS];
+    std::vector<double> wgt[ALFD_MAX_LEVELS];
+    HostCsr P[ALFD_MAX_LEVELS];
+    int64_t ncoarse[ALFD_MAX_LEVELS];
+    bool built_partitioned, is_setup;
+    const char *needs_full;
+  } kept;
+  auto exchange = [&]() {
+    for (int l = 0; l < ALFD_MAX_LEVELS; ++l)
+      kept.agg[l].swap(H.agg[l]), kept.wgt[l].swap(H.wgt[l]), std::swap(kept.P[l], H.P[l]), std::swap(kept.ncoarse[l], H.ncoarse[l]);
+  };
+  for (int l = 0; l < ALFD_MAX_LEVELS; ++l) kept.ncoarse[l] = 0;
+  kept.built_partitioned = H.built_partitioned, kept.is_setup = ctx->is_setup, kept.needs_full = ctx->needs_full;
+  exchange();   // H is now empty, as after clear_input()
+  H.built_partitioned = false;
+  for (size_t l = 0; l < levels.size(); ++l) {
+    const point_hierarchy::Csr &P = levels[l];
+    const int rc = alfd_set_prolongator_block(ctx, block, (int)l, P.nrows, P.ncols, P.rp.data(), P.col.data(), P.val.data());
+    if (rc != ALFD_OK) {
+      exchange();
+      H.built_partitioned = kept.built_partitioned, ctx->is_setup = kept.is_setup, ctx->needs_full = kept.needs_full;
+      return rc;
+    }
+  }
+  hierarchy_input_changed(ctx);
+  if (levels_out) *levels_out = (int32_t)levels.size();
+  if (cells_out)
+    for (size_t k = 0; k < cells.size(); ++k) cells_out[k] = (int32_t)cells[k];
   return ALFD_OK;
 }
 

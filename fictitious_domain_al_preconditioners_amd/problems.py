@@ -458,6 +458,15 @@ def row_support_points(params: dict, node_range=None, node_permutation=None):
     return np.repeat(pts, ncomp, axis=0)
 
 
+def immersed_support_points(pb: "SyntheticProblem"):
+    """One support point per row of the immersed operator A2 of a box-meshed immersed space (node-major: the ncomp rows
+    of a node share its point): the points Context.build_geometric_from_points(block=1) takes."""
+    if pb.params.get("immersed_cells") is None:
+        raise ValueError("immersed_support_points needs a box-meshed immersed domain (params['immersed_cells'])")
+    pts = pb.vecs["immersed_xyz"].reshape(-1, 3)[:, :pb.params["dim"]]
+    return np.repeat(pts, pb.params["ncomp"], axis=0)
+
+
 def brick_row_blocks(params: dict, brick=(16, 4, 1), max_rows: int = 250, node_range=None):
     """Row blocks for Context.set_row_blocks (alfd_set_row_blocks) on the tensor-grid background space:
     the nodes of a brick[0] x brick[1] (x brick[2]) patch of the grid, all components of a node together

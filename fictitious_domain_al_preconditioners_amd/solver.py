@@ -52,6 +52,8 @@ ABI_SYMBOLS = [
     "alfd_bench_spmv_preconditioner",
     "alfd_spmv_tail_step", "alfd_get_fused_tail_launches",
     "alfd_host_check_numbering", "alfd_set_numbering", "alfd_set_numbering_from_points", "alfd_get_numbering",
+    "alfd_host_point_lattice", "alfd_host_point_prolongator", "alfd_host_grid_prolongator",
+    "alfd_build_geometric_from_points", "alfd_host_point_hierarchy_cells",
 ]
 
 
@@ -194,6 +196,14 @@ def load_library():
         "alfd_set_numbering": (C.c_int, [vp, i64, vp]),
         "alfd_set_numbering_from_points": (C.c_int, [vp, i64, i32, vp, vp]),
         "alfd_get_numbering": (C.c_int, [vp, vp, i64, C.POINTER(i64)]),
+        # geometric hierarchies from support points
+        "alfd_host_point_lattice": (C.c_int, [i64, i32, vp, vp, vp, vp, vp, C.POINTER(i32)]),
+        "alfd_host_point_prolongator": (C.c_int, [i64, i32, vp, i32, vp, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64),
+                                                  C.POINTER(i64)]),
+        "alfd_host_grid_prolongator": (C.c_int, [i32, i32, vp, vp, i32, vp, vp, vp, i64, C.POINTER(i64), C.POINTER(i64),
+                                                 C.POINTER(i64)]),
+        "alfd_host_point_hierarchy_cells": (C.c_int, [i32, i32, vp, vp, i32, i64, i32, C.POINTER(i32), vp]),
+        "alfd_build_geometric_from_points": (C.c_int, [vp, C.c_int, i64, i32, vp, vp, vp, vp, i64, i32, C.POINTER(i32), vp]),
     }
     for name, (res, args) in sig.items():
         fn = getattr(lib, name)
@@ -400,6 +410,33 @@ class Context:
             P = self.prolongator(level, block)
             out.append((P, int(P.ncols)))
         return (out, omega[:nlev.value].copy()) if return_omega else out
+
+    def build_geometric_from_points(self, points, block=0, component=None, constrained=None, base=None, min_coarse=None,
+                                    max_levels=7, return_cells=False, return_levels=True):
+        """The geometric hierarchy of a block from one support point per unknown (alfd_build_geometric_from_points; the
+        rule: include/alfd/alfd.h).  block 0: points [rows of A][dim]; constrained (flags per unknown) defaults to the
+        rows of the uploaded A that hold nothing but their diagonal.  block 1: the points of the immersed unknowns (rows
+        of A2), all nodes are unknowns.  component: per unknown, default the rank among the unknowns of its lattice node.
+        base: cells per axis of the uniform base grid, needed on a locally refined mesh.  min_coarse defaults to 400
+        (block 0) / 100 (block 1), those of problems.tensor_prolongators / immersed_tensor_prolongators.  The levels stay
+        in the context for the next setup.  Returns [(Csr P, n_coarse), ...] (with return_cells also the cells per axis
+        of the lattice and of every level's coarse grid, [levels + 1][dim]); return_levels=False returns the number of
+        levels instead and copies nothing out."""
+        pts, comp, con, b = _point_args(points, component, constrained, base)
+        if min_coarse is None:
+            min_coarse = 400 if block == 0 else 100
+        nlev = C.c_int32(0)
+        cells = np.zeros(8 * pts.shape[1], np.int32)
+        ptr = lambda a: None if a is None else a.ctypes.data
+        self._ck(self._lib.alfd_build_geometric_from_points(self._h, int(block), pts.shape[0], pts.shape[1], pts.ctypes.data,
+                                                            ptr(comp), ptr(con), ptr(b), int(min_coarse), int(max_levels),
+                                                            C.byref(nlev), cells.ctypes.data))
+        out = nlev.value
+        if return_levels:
+            out = [(P, int(P.ncols)) for P in (self.prolongator(level, block) for level in range(nlev.value))]
+        if return_cells:
+            return out, cells[:(nlev.value + 1) * pts.shape[1]].reshape(-1, pts.shape[1]).copy()
+        return out
 
     def build_strength_graph(self, block_size=1, threshold=0.02):
         """The node graph of the algebraic aggregation from the resident rows of slot A, on the device
@@ -1160,6 +1197,120 @@ def host_stream_plan_short(m, lanes):
     return {k: getattr(info, k) for k, _ in info._fields_}
 
 
+def _point_args(points, component, constrained, base):
+    """The arrays of the point-hierarchy calls: points [n][dim] float64, component int32 / constrained uint8 per unknown
+    or None, base int32 [dim] or None (a scalar stands for every axis)."""
+    pts = np.ascontiguousarray(points, np.float64)
+    if pts.ndim != 2 or pts.shape[0] < 1 or not 1 <= pts.shape[1] <= 3:
+        raise ValueError("points must be [n][dim], dim 1..3")
+    comp = None if component is None else np.ascontiguousarray(component, np.int32)
+    con = None if constrained is None else np.ascontiguousarray(np.asarray(constrained) != 0, np.uint8)
+    for a, what in ((comp, "component"), (con, "constrained")):
+        if a is not None and a.shape != (pts.shape[0],):
+            raise ValueError(what + " must have one entry per point")
+    b = None
+    if base is not None:
+        b = np.ascontiguousarray(np.broadcast_to(np.asarray(base, np.int32), (pts.shape[1],)))
+    return pts, comp, con, b
+
+
+def point_lattice(points):
+    """Host-only: the lattice of a set of support points (alfd_host_point_lattice; the rule: include/alfd/alfd.h).
+    Returns a dict: cells [dim] (m_d), lo [dim], delta [dim], index [n][dim], complete.  AlfdError (E_INVALID) for
+    points that are not finite or no lattice."""
+    pts = _point_args(points, None, None, None)[0]
+    n, dim = pts.shape
+    cells = np.zeros(dim, np.int32)
+    lo, delta = np.zeros(dim), np.zeros(dim)
+    index = np.empty((n, dim), np.int32)
+    complete = C.c_int32(0)
+    rc = load_library().alfd_host_point_lattice(n, dim, pts.ctypes.data, cells.ctypes.data, lo.ctypes.data,
+                                                delta.ctypes.data, index.ctypes.data, C.byref(complete))
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_point_lattice: the points are not finite or no lattice")
+    return dict(cells=cells, lo=lo, delta=delta, index=index, complete=bool(complete.value))
+
+
+def point_prolongator(points, ncomp=1, component=None, constrained=None, base=None, boundary_unknowns=False):
+    """Host-only: level 0 of the geometric hierarchy from support points (alfd_host_point_prolongator): the unknowns at
+    the points from the Q1 space of the base grid (base=None: (cells + 1) // 2 per axis on a complete lattice).  Returns a
+    problems.Csr (n x n_coarse)."""
+    from .problems import Csr
+    pts, comp, con, b = _point_args(points, component, constrained, base)
+    n, dim = pts.shape
+    ptr = lambda a: None if a is None else a.ctypes.data
+    rp = np.empty(n + 1, np.int64)
+    nnz, nc = C.c_int64(0), C.c_int64(0)
+
+    def call(oc, ov, cap):
+        rc = load_library().alfd_host_point_prolongator(n, dim, pts.ctypes.data, int(ncomp), ptr(comp), ptr(con), ptr(b),
+                                                        int(bool(boundary_unknowns)), rp.ctypes.data, oc, ov, cap,
+                                                        C.byref(nnz), C.byref(nc))
+        if rc != _abi.OK:
+            raise AlfdError(rc, "alfd_host_point_prolongator refused the points, the components or the base grid")
+    call(None, None, 0)
+    col = np.empty(nnz.value, np.int32)
+    val = np.empty(nnz.value, np.float64)
+    call(col.ctypes.data, val.ctypes.data, col.size)
+    return Csr(n, int(nc.value), rp, col, val)
+
+
+def grid_prolongator(dim, ncomp, fine_cells, coarse_cells, boundary_unknowns=False):
+    """Host-only: one lower level of the geometric hierarchy (alfd_host_grid_prolongator): the unknowns of a grid of
+    fine_cells per axis from those of a grid of coarse_cells.  Returns a problems.Csr."""
+    from .problems import Csr
+    fine = np.ascontiguousarray(np.broadcast_to(np.asarray(fine_cells, np.int32), (dim,)))
+    coarse = np.ascontiguousarray(np.broadcast_to(np.asarray(coarse_cells, np.int32), (dim,)))
+    nf, nc, nnz = C.c_int64(0), C.c_int64(0), C.c_int64(0)
+
+    def call(orp, oc, ov, cap):
+        rc = load_library().alfd_host_grid_prolongator(int(dim), int(ncomp), fine.ctypes.data, coarse.ctypes.data,
+                                                       int(bool(boundary_unknowns)), orp, oc, ov, cap, C.byref(nf),
+                                                       C.byref(nc), C.byref(nnz))
+        if rc != _abi.OK:
+            raise AlfdError(rc, "alfd_host_grid_prolongator refused the grids")
+    call(None, None, None, 0)
+    rp = np.empty(nf.value + 1, np.int64)
+    col = np.empty(nnz.value, np.int32)
+    val = np.empty(nnz.value, np.float64)
+    call(rp.ctypes.data, col.ctypes.data, val.ctypes.data, col.size)
+    return Csr(int(nf.value), int(nc.value), rp, col, val)
+
+
+def point_hierarchy_cells(lattice_cells, ncomp=1, base=None, boundary_unknowns=False, min_coarse=400, max_levels=7):
+    """Host-only: the level rule of the geometric hierarchy (alfd_host_point_hierarchy_cells): the cells per axis of every
+    level's coarse grid, [levels][dim], for a lattice of lattice_cells."""
+    m = np.ascontiguousarray(lattice_cells, np.int32)
+    dim = m.size
+    b = None if base is None else np.ascontiguousarray(np.broadcast_to(np.asarray(base, np.int32), (dim,)))
+    nlev = C.c_int32(0)
+    cells = np.zeros(8 * dim, np.int32)
+    rc = load_library().alfd_host_point_hierarchy_cells(dim, int(ncomp), m.ctypes.data, None if b is None else b.ctypes.data,
+                                                        int(bool(boundary_unknowns)), int(min_coarse), int(max_levels),
+                                                        C.byref(nlev), cells.ctypes.data)
+    if rc != _abi.OK:
+        raise AlfdError(rc, "alfd_host_point_hierarchy_cells refused the base grid")
+    return cells[:nlev.value * dim].reshape(nlev.value, dim).copy()
+
+
+def point_hierarchy(points, ncomp=1, component=None, constrained=None, base=None, boundary_unknowns=False,
+                    min_coarse=400, max_levels=7):
+    """Host-only: the levels Context.build_geometric_from_points stores, e.g. for the oracle or for another solver
+    instance: the grids of point_hierarchy_cells, level 0 from point_prolongator, the levels below from grid_prolongator
+    between consecutive grids.  Returns [(Csr P, n_coarse), ...]; with boundary unknowns a lattice direction of one cell
+    gives []."""
+    lat = point_lattice(points)
+    cells = point_hierarchy_cells(lat["cells"], ncomp, base, boundary_unknowns, min_coarse, max_levels)
+    levels = []
+    for level in range(cells.shape[0]):
+        if level == 0:
+            P = point_prolongator(points, ncomp, component, constrained, base, boundary_unknowns)
+        else:
+            P = grid_prolongator(cells.shape[1], ncomp, cells[level - 1], cells[level], boundary_unknowns)
+        levels.append((P, int(P.ncols)))
+    return levels
+
+
 def numbering_from_points(points):
     """new_to_old permutation that puts unknowns into the lexicographic order of their support points
     (alfd_host_numbering_from_points); the components of a node stay together."""
@@ -1271,7 +1422,7 @@ def host_stream_plan(m, row_block=96, blocks=None, side_rows=False):
 
 
 def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_blocks=None, immersed_levels=None,
-                   numbering=None) -> Context:
+                   numbering=None, hierarchy_from_points=None) -> Context:
     """Upload a problems.SyntheticProblem (whole, or this rank's rows) with the
     reference's diagonal choices: W^-1 = 1/M_ii^2 (stokes...:976-978), lumped
     pressure mass (stokes...:946-954).  aggregates: [(agg, n_coarse), ...] for
@@ -1283,7 +1434,10 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
     problems.immersed_tensor_prolongators); None leaves whatever the context holds for that block.  numbering: a
     new_to_old permutation of block 0 (Context.set_numbering) or an [n][dim] array of support points
     (Context.set_numbering_from_points), declared before the uploads: pb, aggregates and row_blocks stay in the problem's
-    own numbering."""
+    own numbering.  hierarchy_from_points: a dict that asks the library for the geometric hierarchy once the operators are
+    uploaded (Context.build_geometric_from_points) -- "points" (block 0) and / or "immersed_points" (block 1), with
+    "base", "min_coarse", "max_levels", "component", "constrained" for block 0 and "immersed_min_coarse" for block 1;
+    it replaces what aggregates / immersed_levels set for that block."""
     if numbering is not None:
         if np.ndim(numbering) == 2:
             ctx.set_numbering_from_points(numbering)
@@ -1329,6 +1483,14 @@ def upload_problem(ctx: Context, pb, cfg: _abi.Config, aggregates=None, row_bloc
             if "error" in box:
                 raise box["error"]
             set_hierarchy(box["levels"])
+        if hierarchy_from_points is not None:
+            ph = dict(hierarchy_from_points)
+            pts0, pts1, mc1 = ph.pop("points", None), ph.pop("immersed_points", None), ph.pop("immersed_min_coarse", None)
+            if pts0 is not None:
+                ctx.build_geometric_from_points(pts0, block=0, return_levels=False, **ph)
+            if pts1 is not None:
+                ctx.build_geometric_from_points(pts1, block=1, min_coarse=mc1, max_levels=ph.get("max_levels", 7),
+                                                return_levels=False)
 
     ctx.set_matrix(_abi.A, pb.mats["A"])
     # C before CT (and B before BT): an explicitly uploaded transpose is left alone, otherwise alfd_set_matrix(CT) would
@@ -1391,8 +1553,8 @@ def update_coupling(ctx: Context, Ct, inv_w=None, M=None, C=None, gamma=None) ->
 
 
 def context_from_problem(pb, cfg: _abi.Config, device_id=0, aggregates=None, row_blocks=None,
-                         immersed_levels=None, numbering=None) -> Context:
-    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks, immersed_levels, numbering)
+                         immersed_levels=None, numbering=None, hierarchy_from_points=None) -> Context:
+    return upload_problem(Context(device_id), pb, cfg, aggregates, row_blocks, immersed_levels, numbering, hierarchy_from_points)
 
 
 # ---------------------------------------------------------------------------

@@ -531,6 +531,77 @@ int alfd_smoothed_prolongator(alfd_ctx_t ctx, int64_t nrows, const int64_t *row_
                               const double *w_inv, double gamma, const int32_t *agg, int64_t n_coarse, double omega,
                               int32_t block_size, double drop_tolerance, int32_t max_row_entries, int64_t *p_row_ptr,
                               int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz, int32_t *on_device);
+/* Geometric multigrid transfers from support points (DoFTools::map_dofs_to_support_points) and constraint flags: the
+ * hierarchy of problems.tensor_prolongators / refined_prolongators / immersed_tensor_prolongators for callers that have
+ * points, not the generator's parameters.  ONE rule, so that the results can be compared entry for entry.
+ * Lattice.  Per axis d: lo, hi = smallest and largest coordinate; coordinates closer than 1e-9 (hi - lo) count as equal;
+ *   delta_d = the smallest gap between distinct coordinates; m_d = round((hi - lo) / delta_d) cells; a point has the lattice
+ *   index i_d = round((x_d - lo) / delta_d).  |x_d - lo - i_d delta_d| > 1e-6 delta_d or a non-finite coordinate:
+ *   ALFD_E_INVALID (no lattice mesh).  An axis on which all points agree has m_d = 0, delta_d = 0.  The lattice is
+ *   COMPLETE when every lattice node carries an unknown.
+ * Components.  The unknowns that share a lattice node are its components: component[i] when given, else the rank of i
+ *   among them by ascending index (node-major and component-wise block numberings alike).  Every occupied node carries
+ *   exactly ncomp unknowns (1 <= ncomp <= 64), each component once, else ALFD_E_INVALID.
+ * Level 0: the points onto the Q1 space of a base grid of base_d cells per axis.  Its unknowns are the interior nodes,
+ *   lexicographic with x fastest, node-major, ncomp per node; with boundary_unknowns = 1 all base_d + 1 nodes per axis (the
+ *   immersed spaces, which have no Dirichlet rows).  Per axis, in integers: num = i_d * base_d, j = num / m_d,
+ *   rem = num % m_d; rem == 0 gives weight 1 on node j, else fr = (double)rem / (double)m_d with weight 1.0 - fr on j and
+ *   fr on j + 1.  The entry is w_z * (w_y * w_x); entries onto nodes that are no unknowns are dropped (a weight is never
+ *   zero); columns ascend within a row.  Rows with constrained[i] != 0 are empty, and with boundary_unknowns = 0 so are
+ *   the rows on the lattice boundary (i_d == 0 or i_d == m_d on any axis).
+ *   base == NULL needs a complete lattice and takes base_d = (m_d + 1) / 2: for Q2 points the Q1 space of the same mesh, for
+ *   Q1 points the next coarser grid.  An incomplete lattice (a locally refined mesh) needs base from the caller, the cells
+ *   of its uniform base grid ("Initial refinement"): ALFD_E_INVALID without.  base_d < 2 (< 1 with boundary unknowns) or
+ *   base_d > m_d: ALFD_E_INVALID.
+ * Levels below: cur_d cells to next_d = (cur_d + 1) / 2 cells by the same integer rule between the two node grids, the same
+ *   unknowns on both sides.  While the last n_coarse > min_coarse and fewer than max_levels levels exist a level is added,
+ *   provided every next_d >= 2 (interior unknowns) or every cur_d >= 2 (boundary unknowns: a direction down to one cell
+ *   ends the hierarchy, level 0 included, so a (2, 1, 1) box gives no level at all).
+ * Host-only (no device, no context):
+ *   alfd_host_point_lattice     cells[dim] = m_d, lo[dim], delta[dim], index[n * dim] = i_d, *complete (any may be NULL).
+ *   alfd_host_point_prolongator level 0 (n x *n_coarse) in the two-call protocol of alfd_host_smoothed_prolongator:
+ *                               p_col == p_val == NULL returns *nnz, *n_coarse (and p_row_ptr[n + 1] if given), then
+ *                               arrays with capacity >= nnz.  component / constrained / base may be NULL.
+ *   alfd_host_grid_prolongator  one lower level between the grids of fine_cells[dim] and coarse_cells[dim] (any
+ *                               1 <= coarse_d <= fine_d, 2 <= coarse_d with interior unknowns), same protocol; *n_fine and
+ *                               *n_coarse are the unknowns of the two grids.
+ *   alfd_host_point_hierarchy_cells
+ *                               the level rule alone: from the lattice cells m_d, ncomp, base (NULL: (m_d + 1) / 2),
+ *                               min_coarse and max_levels (as alfd_build_geometric_from_points takes them) the number
+ *                               of levels and the cells of every level's coarse grid, cells_out[levels * dim] (room
+ *                               for ALFD_MAX_LEVELS * dim; may be NULL).  Level 0 of alfd_host_point_prolongator, then
+ *                               alfd_host_grid_prolongator between consecutive grids, are the levels the context
+ *                               build stores. */
+int alfd_host_point_lattice(int64_t n, int32_t dim, const double *points, int32_t *cells, double *lo, double *delta,
+                            int32_t *index, int32_t *complete);
+int alfd_host_point_prolongator(int64_t n, int32_t dim, const double *points, int32_t ncomp, const int32_t *component,
+                                const uint8_t *constrained, const int32_t *base, int32_t boundary_unknowns,
+                                int64_t *p_row_ptr, int32_t *p_col, double *p_val, int64_t capacity, int64_t *nnz,
+                                int64_t *n_coarse);
+int alfd_host_grid_prolongator(int32_t dim, int32_t ncomp, const int32_t *fine_cells, const int32_t *coarse_cells,
+                               int32_t boundary_unknowns, int64_t *p_row_ptr, int32_t *p_col, double *p_val,
+                               int64_t capacity, int64_t *n_fine, int64_t *n_coarse, int64_t *nnz);
+int alfd_host_point_hierarchy_cells(int32_t dim, int32_t ncomp, const int32_t *lattice_cells, const int32_t *base,
+                                    int32_t boundary_unknowns, int64_t min_coarse, int32_t max_levels, int32_t *levels_out,
+                                    int32_t *cells_out);
+/* The whole hierarchy of a block by that rule, stored as alfd_set_prolongator[_block] would store its levels
+ * (alfd_get_prolongator[_block] returns them; alfd_setup and alfd_setup_coupling treat them as caller-supplied CSR
+ * prolongators); the aggregates and prolongators the block had are cleared, as the smoothed-aggregation builders do.
+ *   block 0: interior unknowns; n = the rows of slot A; constrained == NULL takes the rows of the RESIDENT slot A that
+ *            hold nothing but their diagonal (explicit zeros do not count: the fixed flags of alfd_host_strength_graph) --
+ *            Dirichlet and condensed hanging-node rows as the adapter uploads them.  Under alfd_set_numbering points,
+ *            component and constrained are in the caller's numbering, like every level-0 input.
+ *   block 1: boundary unknowns, no constraints (constrained must be NULL); n = the rows of slot A2.
+ * ncomp is the number of unknowns on the first point's node.  min_coarse >= 1; max_levels outside 1 .. ALFD_MAX_LEVELS - 1
+ * means ALFD_MAX_LEVELS - 1.  *levels_out (may be NULL) = the levels built (0 is possible on block 1, see the rule);
+ * cells_out (may be NULL; room for ALFD_MAX_LEVELS * dim entries) = the cells of the lattice, then of every level's coarse
+ * grid.  ALFD_E_UNSUPPORTED on a partitioned context, ALFD_E_NOT_SETUP without the slot, ALFD_E_INVALID for another block,
+ * a bad size or argument and everything the rule refuses.  The levels are formed before the block is touched and the
+ * inputs it had are handed back if storing one fails, so after any refusal the context stays usable and keeps the
+ * hierarchy it had. */
+int alfd_build_geometric_from_points(alfd_ctx_t ctx, int block, int64_t n, int32_t dim, const double *points,
+                                     const int32_t *component, const uint8_t *constrained, const int32_t *base,
+                                     int64_t min_coarse, int32_t max_levels, int32_t *levels_out, int32_t *cells_out);
 int alfd_configure(alfd_ctx_t ctx, const alfd_config *cfg);
 /* New stop rules for the following solves WITHOUT a new alfd_setup (alfd_configure invalidates the setup): the
  * reference's SolverControl objects are plain members that a caller may change between two solve() calls

@@ -201,6 +201,34 @@ class System {
     if (omega) omega->assign(w.begin(), w.begin() + levels);
     return levels;
   }
+  // Geometric multigrid hierarchy built by the library from one support point per unknown of the block
+  // (alfd_build_geometric_from_points; the preconditioner the benchmark measures): after set_matrix, before setup.
+  //   std::map<types::global_dof_index, Point<dim>> sp;  DoFTools::map_dofs_to_support_points(mapping, dh, sp);
+  // restricted to the block, in the caller's numbering (also under set_numbering_from_support_points).  constrained:
+  // one flag per unknown (AffineConstraints::is_constrained, Dirichlet rows included); empty = the rows of the uploaded
+  // A that hold nothing but their diagonal, which is what condense() leaves of them.  base: cells per axis of the
+  // uniform grid before local refinement (`Initial refinement`), needed when hanging nodes exist; empty on a uniform
+  // mesh.  block = 1: the immersed space (rows of A2), no constraints.  Returns the number of levels.
+  template <class PointContainer>
+  int build_geometric_hierarchy_from_support_points(const PointContainer &points, int dim,
+                                                    const std::vector<uint8_t> &constrained = {},
+                                                    const std::vector<int32_t> &base = {}, int64_t min_coarse = 400,
+                                                    int32_t max_levels = 7, int block = 0) {
+    const int64_t n = (int64_t)points.size();
+    std::vector<double> xyz((size_t)n * dim);
+    int64_t i = 0;
+    for (const auto &p : points) {
+      for (int d = 0; d < dim; ++d) xyz[(size_t)i * dim + d] = p[d];
+      ++i;
+    }
+    if (!constrained.empty() && (int64_t)constrained.size() != n) check(ALFD_E_INVALID);
+    if (!base.empty() && (int)base.size() != dim) check(ALFD_E_INVALID);
+    int32_t levels = 0;
+    check(alfd_build_geometric_from_points(ctx_, block, n, dim, xyz.data(), nullptr,
+                                           constrained.empty() ? nullptr : constrained.data(),
+                                           base.empty() ? nullptr : base.data(), min_coarse, max_levels, &levels, nullptr));
+    return levels;
+  }
   // `Use diagonal inverse = false` / `Diagonal mass immersed = false` (immersed_laplace.cc:859-877,
   // stokes...:979-985, elliptic_interface.cc:713-737): the exact W^-1 = (M^-1)^2 (mode
   // ALFD_W_MASS_INV_SQUARED) or M^-1 (ALFD_W_MASS_INV) from the immersed mass matrix; applied to the
